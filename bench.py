@@ -5,6 +5,13 @@ Metric (BASELINE.json): complex MSa/s through the full demod chain (batched
 streams), whole job over all ranks, inputs resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it synthesises
+the batch, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the result line.  Everything else below
+(parity against the CPU oracle, cpu_baseline, BER, the FIR phase legs, framer,
+host ring, sub_records, drop-in shapes, split/gather) runs with --full only.
 
 One step = one DeModulate call (QPSKDeModulator.cs:345-425) on every stream of
 the rank's batch: matched-filter FIR -> Mueller-Muller + Costas + differential
@@ -15,18 +22,23 @@ BASELINE.json (4096 streams x 2^20 complex samples per GPU, sps 4, 129-tap
 RRC).  Streams are independent (QPSKDeModulator.cs:20-73), so ranks shard
 streams with no data-path collective ("scaling": "weak": every rank owns its
 own C3-shaped batch); the only collectives are the MAX of the timed region and
-the sums of the parity / BER counters after it.  The other configs run after
-the headline as `sub_records` (N=1: C2, the C4 shard, C5 and C3 with the
+the sums of the parity / BER counters after it.  With --full the other configs
+run after the headline as `sub_records` (N=1: C2, the C4 shard, C5 and C3 with the
 glibc-exact Costas trig; N>1: the C4 shard shape, 4096 streams/GPU at sps 8,
 plus the RCCL scatter/gather leg of SURVEY.md 8e).
 
 stdout carries ONE compact JSON line (<= LINE_MAX_BYTES: the driver's keys,
 roofline, cpu_baseline, parity counts, GPU and CPU BER, per sub-record the
 same); the full record (per-launch statistics, clocks, FIR phase samples,
-framer, host ring) goes to the --detail side file, named in the line.
+framer, host ring) goes to the --detail side file, named in the line (a plain
+run writes it only where --detail names one).
 
-After each config's timed region (never inside it) the timed handle itself is
-checked: one call from the initial state on every stream, whose bit rows are
+--dump-outputs DIR writes what the last timed call left in the caller's
+buffers (dump_outputs below); the inputs are seeded, so two builds run with
+the same arguments can be compared file for file.
+
+With --full, after each config's timed region (never inside it) the timed
+handle itself is checked: one call from the initial state on every stream, whose bit rows are
 compared with the CPU oracle run on the host cores (glibc trig, what .NET on
 Linux calls) -- the same run is the `cpu_baseline` -- over as many streams as
 fit the CPU time budget, always including the last 64 rows of the batch
@@ -192,6 +204,47 @@ def pick_streams(S, n_cover, tail=64):
         return list(range(S))
     head = max(1, n_cover - tail)
     return list(range(head)) + list(range(S - tail, S))
+
+
+DUMP_SEED = 0x5159534B
+DUMP_BITS_BYTES = 48 << 20    # float32 budget of bits.npy (the three files stay under 64 MB)
+
+
+def dump_rows(S, row_bytes):
+    """Stream indices --dump-outputs keeps: all of them when their bit rows fit
+    DUMP_BITS_BYTES as float32, else a fixed seeded sample that always holds
+    the first and the last stream.  Depends on the shape alone."""
+    import numpy as np
+    k = max(2, DUMP_BITS_BYTES // (4 * row_bytes))
+    if k >= S:
+        return list(range(S))
+    mid = np.random.default_rng(DUMP_SEED).choice(np.arange(1, S - 1), k - 2, replace=False)
+    return [0] + sorted(int(i) for i in mid) + [S - 1]
+
+
+def dump_outputs(out_dir, bits_dev, nbits_dev):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    call, as float32 / float64 .npy files.
+      n_bits.npy     [S] float64: valid bits of every stream's row
+      bits_rows.npy  [K] float64: the streams whose rows bits.npy holds
+      bits.npy       [K, B] float32: their packed bit rows, one byte (0..255,
+                     MSB first) per element; bits past n_bits are zeroed, so
+                     the file holds nothing but the call's own output"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    S, B = bits_dev.shape
+    idx = dump_rows(S, B)
+    nb = nbits_dev.cpu().numpy().astype(np.int64)
+    rows = rows_to_host(bits_dev, idx).astype(np.float32)
+    for j, i in enumerate(idx):
+        full, rem = divmod(int(nb[i]), 8)
+        if rem and full < B:
+            rows[j, full] = int(rows[j, full]) & (0xFF << (8 - rem)) & 0xFF
+            full += 1
+        rows[j, full:] = 0
+    np.save(os.path.join(out_dir, "n_bits.npy"), nb.astype(np.float64))
+    np.save(os.path.join(out_dir, "bits_rows.npy"), np.asarray(idx, dtype=np.float64))
+    np.save(os.path.join(out_dir, "bits.npy"), rows)
 
 
 BER_STREAMS = 32      # leading streams of every rank's shard that BER is counted on
@@ -874,6 +927,9 @@ def run_config(key, args, rank, world, dev, steps, warmup, headline):
     lt = demod.launch_times()
     kclk = demod.kernel_clocks()
     demod.enable_timing(False)
+    if headline and args.dump_outputs and rank == 0:
+        # the last timed call's rows, before anything overwrites them
+        dump_outputs(args.dump_outputs, bits, nbits)
 
     rec = {}
     errs = total_bits = lost = slips = 0
@@ -1215,8 +1271,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS),
                     help="headline workload (default C3, the largest single-GPU config)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: parity against the CPU oracle, "
+                         "cpu_baseline, BER, FIR phase legs, framer, host ring, sub_records, drop-in "
+                         "shapes, split/gather (each has its own --no-* switch).  Without it the run "
+                         "is --timed-only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the last step's outputs (rank 0: n_bits.npy, "
+                         "bits_rows.npy, bits.npy; a fixed seeded sample of the bit rows when they "
+                         "exceed 48 MB as float32) into DIR")
     ap.add_argument("--sub-configs", default="auto",
-                    help="comma list run after the headline as sub_records; 'auto' = c2,c4,c5,c3_glibc at N=1 "
+                    help="with --full: comma list run after the headline as sub_records; 'auto' = c2,c4,c5,c3_glibc at N=1 "
                          "(c4: the per-GPU shard of BASELINE's 8-GPU config, the N = 1 point of its "
                          "curve), c4 at N>1; 'none' = headline only")
     ap.add_argument("--sub-steps", type=int, default=20)
@@ -1236,7 +1301,8 @@ def main():
     ap.add_argument("--timed-only", action="store_true",
                     help="warmup + timed steps of the headline only (no parity, BER, framer, "
                          "split/gather, host ring, CPU baseline, sub-records): the command rocprofv3 "
-                         "traces, so its kernel averages are the timed region's")
+                         "traces, so its kernel averages are the timed region's.  The default; "
+                         "given with --full it wins")
     ap.add_argument("--no-host-ring", action="store_true",
                     help="skip the PCIe-inclusive host-ring pass (N=1, batches <= 4 GiB: C2)")
     ap.add_argument("--no-drop-in", action="store_true",
@@ -1252,9 +1318,12 @@ def main():
                     help="every rank uses cuda:0 (rehearsal only; numbers meaningless)")
     ap.add_argument("--detail", default="",
                     help="side file for the full record (launch stats, clocks, FIR phases, framer, "
-                         "host ring); default bench_detail.json next to bench.py")
+                         "host ring); with --full the default is bench_detail.json next to bench.py")
     args = ap.parse_args()
-    if args.timed_only:
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.timed_only or not args.full:
+        args.timed_only = True
         args.no_parity = args.no_framer = args.no_split_gather = True
         args.no_host_ring = args.no_cpu_baseline = args.no_drop_in = True
         args.sub_configs = "none"
@@ -1310,13 +1379,15 @@ def main():
         out["split_gather"] = split_gather_leg(args, rank, world, dev)
     sys.stdout.flush()
     if rank == 0:
-        detail = os.path.abspath(args.detail or os.path.join(ROOT, "bench_detail.json"))
-        try:
-            with open(detail, "w") as f:
-                json.dump(out, f, indent=1)
-            name = os.path.relpath(detail, ROOT) if detail.startswith(ROOT + os.sep) else detail
-        except OSError as e:
-            name = f"not written ({e})"
+        name = None
+        if args.full or args.detail:    # a plain run writes the side file only where --detail names one
+            detail = os.path.abspath(args.detail or os.path.join(ROOT, "bench_detail.json"))
+            try:
+                with open(detail, "w") as f:
+                    json.dump(out, f, indent=1)
+                name = os.path.relpath(detail, ROOT) if detail.startswith(ROOT + os.sep) else detail
+            except OSError as e:
+                name = f"not written ({e})"
         os.write(json_fd, (dump_line(compact_record(out, name)) + "\n").encode())
     if world > 1:
         dist.destroy_process_group()

@@ -7,7 +7,7 @@ set -e
 rounds=$1; shift
 for i in $(seq 1 "$rounds"); do
   for lib in qpsk-modulator-demodulator_amd/_build/ab/lib*.so; do
-    QPSK_DEMOD_LIB=$PWD/$lib timeout -k 10 300 python bench.py --no-parity --no-cpu-baseline --no-framer \
+    QPSK_DEMOD_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --no-parity --no-cpu-baseline --no-framer \
           --no-host-ring --sub-configs none --detail /tmp/ab_phases_detail.json "$@" > /dev/null
     echo "$(basename "$lib") $(python3 -c '
 import json

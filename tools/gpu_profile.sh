@@ -21,8 +21,8 @@ esac
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_${ROUND}_${CFG}" -o run \
   -- python3 "$R/bench.py" --config "$CFG" --steps 6 --warmup 2 --timed-only > "$O/prof_${ROUND}_${CFG}.log" 2>&1
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch_${CFG}" -o run \
-  -- python3 "$R/bench.py" --config "$CFG" --steps 2 --warmup 1 --no-cpu-baseline --no-parity > "$O/pmc_fetch_${CFG}.log" 2>&1
+  -- python3 "$R/bench.py" --config "$CFG" --steps 2 --warmup 1 --full --no-cpu-baseline --no-parity > "$O/pmc_fetch_${CFG}.log" 2>&1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/pmc_write_${CFG}" -o run \
-  -- python3 "$R/bench.py" --config "$CFG" --steps 2 --warmup 1 --no-cpu-baseline --no-parity > "$O/pmc_write_${CFG}.log" 2>&1
+  -- python3 "$R/bench.py" --config "$CFG" --steps 2 --warmup 1 --full --no-cpu-baseline --no-parity > "$O/pmc_write_${CFG}.log" 2>&1
 python3 "$R/tools/pmc_traffic.py" --fetch "$O/pmc_fetch_${CFG}" --write "$O/pmc_write_${CFG}" \
   --kernel fir_tile_kernel --algo-bytes "$ALGO" --out "$O/pmc_fir_${CFG}.json"

@@ -4,7 +4,7 @@
 # steps:
 #   tests            GPU suite (-m gpu) + smoke
 #   tests:EXPR       GPU suite restricted with -k EXPR
-#   bench            default bench line (driver flags: --steps 20 --warmup 5)
+#   bench            the whole bench line, every leg (--steps 20 --warmup 5 --full)
 #   bench:ARGS       bench with extra args (commas become spaces)
 #   prof:CFG         rocprofv3 --kernel-trace --stats of the timed region of CFG
 #   pmc:CFG:KERNEL:BYTES  FETCH_SIZE / WRITE_SIZE passes for KERNEL at CFG -> traffic json
@@ -28,7 +28,7 @@ for step in "$@"; do
       timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1
       echo "tests ok" ;;
     bench)
-      a=${arg//,/ }; [ -z "$a" ] && a="--steps 20 --warmup 5"
+      a=${arg//,/ }; [ -z "$a" ] && a="--steps 20 --warmup 5 --full"
       n=$(ls "$O" | grep -c '^bench' || true)
       timeout -k 10 600 python bench.py $a --detail "$O/bench${n}_detail.json" > "$O/bench$n.json" 2> "$O/bench$n.err" \
         || { tail -20 "$O/bench$n.err"; exit 1; }

@@ -13,6 +13,6 @@ for c in c2 c3; do
   echo "profiled $c"
 done
 for c in c2 c3 c5; do
-  timeout -k 10 300 python3 "$R/bench.py" --config "$c" --steps 6 --warmup 2 > "$O/${ROUND}_${c}_bench.json" 2> "$O/${ROUND}_${c}_bench.err"
+  timeout -k 10 300 python3 "$R/bench.py" --config "$c" --steps 6 --warmup 2 --full > "$O/${ROUND}_${c}_bench.json" 2> "$O/${ROUND}_${c}_bench.err"
   echo "bench $c"; cat "$O/${ROUND}_${c}_bench.json"
 done
