@@ -111,6 +111,13 @@ __device__ __forceinline__ void fir_core(const f2 *row, int r, const float *hrev
     // Lane accumulator l of every output: sum_j hrev[jW+l] * x[t-T+1+jW+l],
     // j ascending (FIRFilter.cs:165-174); u_i = x[t0 + l + W i] is shared by
     // the Q outputs of this thread.  RD(i) reads u_i.
+    // The reference seeds the lane accumulators and the lane sum with +0
+    // (FIRFilter.cs:150,161-162), so a finite output of it is never -0; here
+    // the first product seeds its lane and lane 0 the sum, which would return
+    // -0 for a window whose products are all -0.  Lane 0's first product
+    // enters as +0 + p: equal to p for every p but -0, and a sum with a term
+    // that is not -0 is not -0, so neither lane 0's accumulator nor the lane
+    // sum nor the tail after it can be (Q packed adds per thread and tile).
     auto lane_phase = [&](int l, auto rdu) __attribute__((always_inline)) {
         asm volatile("" ::: "memory");
         f2 A[Q];
@@ -126,7 +133,7 @@ __device__ __forceinline__ void fir_core(const f2 *row, int r, const float *hrev
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
                 const int j = i - q;
-                if (j >= 0 && j < J) A[q] = (j == 0) ? p[q] : A[q] + p[q];
+                if (j >= 0 && j < J) A[q] = (j == 0) ? (l == 0 ? f2{0.f, 0.f} + p[q] : p[q]) : A[q] + p[q];
             }
         }
         // Horizontal sum in lane order 0..W-1 (FIRFilter.cs:176-180).

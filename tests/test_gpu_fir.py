@@ -1,0 +1,403 @@
+"""The RRC matched filter at stage level, bit for bit.
+
+qpsk_demod_last_mf exposes the matched-filter rows of the last synchronous
+call; O.oracle_fir is the reference's streaming ComplexFIRFilter
+(FIRFilter.cs:59-192).  Every GPU case here compares the two with plain
+K.bitwise_equal (tolerance 0, -0 and +0 distinct), over every specialised tap
+count of launch_fir, both staging paths of the tile kernel (float4 and
+scalar), the 2048-output tile edges, histories built from calls shorter than
+the filter, the generic kernel, and windows whose products are all -0 (the
+reference seeds its accumulators with +0, FIRFilter.cs:150,161-162, so a
+finite output of it is never -0).
+
+The unmarked tests run without a GPU: they prove that the signed-zero inputs
+tell the two seedings apart, and that every specialised tap count of
+qpsk_kernels.hip has a case here.
+"""
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import common as K
+import oracle as O
+
+gpu = pytest.mark.gpu
+
+# (sps, span) -> T = sps * span + 1: one pair per tile-kernel instantiation of
+# launch_fir (qpsk_kernels.hip); test_every_specialised_tap_count_has_a_case
+# keeps the two lists equal
+SPECIALISED = [(2, 6), (2, 8), (2, 10), (4, 8), (4, 10), (4, 12), (8, 8), (8, 12), (4, 32)]
+TILE = 2048   # outputs per workgroup of fir_tile_kernel (256 threads x 8)
+
+
+def _ids(pairs):
+    return [f"T{s * p + 1}" for s, p in pairs]
+
+
+@pytest.fixture(scope="module")
+def Q():
+    """The binding and a device (GPU tests only)."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.fail("gpu tests need an MI355X")
+    import qpsk_amd
+    return qpsk_amd
+
+
+@functools.lru_cache(maxsize=None)
+def rrc(sps, span):
+    """The reference's float32 RRC taps for (K.FS, K.FS // sps, K.ALPHA, span)."""
+    h = K.oracle_for(sps, span).rrc_f32()
+    h.setflags(write=False)
+    return h
+
+
+def fir_ref(h, row, lanes=8):
+    """One streaming reference filter over a whole interleaved row."""
+    tiq = np.zeros(2 * h.size, np.float32)
+    tiq[0::2] = h
+    return O.oracle_fir(tiq, row, lanes=lanes)
+
+
+def is_neg_zero(v):
+    return np.signbit(v) & (v == 0)
+
+
+# ---------------------------------------------------------------------------
+# call sequences and inputs
+# ---------------------------------------------------------------------------
+def ragged_calls(T, S=6):
+    """Per-call [S] lengths: stream s takes 1, T-2, T-1, T, 2047, 2048, 2049, 0,
+    4097 samples in that order, started s places in (so stream 0 builds its
+    history from calls shorter than T-1, and every stream reaches and crosses
+    the 2048-output tile edge with both parities of n).  A call in which the
+    rotation leaves no stream empty gets one: stream (call % S) sits that call
+    out and takes its length in the next one."""
+    base = [1, T - 2, T - 1, T, TILE - 1, TILE, TILE + 1, 0, 2 * TILE + 1]
+    todo = [base[s:] + base[:s] for s in range(S)]
+    calls = []
+    while any(todo):
+        lens = [q[0] if q else 0 for q in todo]
+        if 0 not in lens:
+            lens[len(calls) % S] = 0
+        for s in range(S):
+            if todo[s] and lens[s] == todo[s][0]:
+                todo[s].pop(0)
+        calls.append(lens)
+    return calls
+
+
+def normal_rows(S, n, seed):
+    return np.random.default_rng(seed).standard_normal((S, 2 * n)).astype(np.float32)
+
+
+def place_window(row, t, h):
+    """Make every product of output t's window -0: the sample that meets tap
+    h[k] is x[t - k]; -0 where the tap is >= 0, +0 where it is negative (I and Q)."""
+    T = h.size
+    for k in range(T):
+        v = np.float32(-0.0) if h[k] >= 0 else np.float32(0.0)
+        row[2 * (t - k)] = v
+        row[2 * (t - k) + 1] = v
+
+
+SZ_CALLS = (2561, 2304)   # the two uniform calls of the signed-zero case
+
+
+@functools.lru_cache(maxsize=None)
+def signed_zero_case(sps, span):
+    """Rows [6, 2 * sum(SZ_CALLS)] and the target outputs (stream -> positions in
+    the whole row).  Streams 0-2: random rows with crafted windows; 3: all -0;
+    4: all +0; 5: a random row scaled into the subnormal range.
+    Targets, as output indices of their call (n1 = first call's length):
+      stream 0: 2047 (= 7 mod 8, last of tile 0); call 2's (T-1)/2 (half of the
+                window is carried history); call 2's 2048 (first of tile 1)
+      stream 1: 2048 (= 0 mod 8, first of tile 1); call 2's 2047
+      stream 2: 1992 (= 0 mod 8, in the last 64 of tile 0); call 2's 63 (= 7 mod
+                8, in the first 64; straddles the calls when T > 64)."""
+    h = rrc(sps, span)
+    T = h.size
+    n1, n2 = SZ_CALLS
+    iq = normal_rows(6, n1 + n2, seed=4000 + T)
+    targets = {0: [TILE - 1, n1 + (T - 1) // 2, n1 + TILE], 1: [TILE, n1 + TILE - 1],
+               2: [TILE - 56, n1 + 63]}
+    for s, ts in targets.items():
+        for a, b in zip(ts, ts[1:]):
+            assert b - T + 1 > a, "windows overlap"
+        assert ts[0] - T + 1 >= 0
+        for t in ts:
+            place_window(iq[s], t, h)
+    iq[3] = np.float32(-0.0)
+    iq[4] = np.float32(0.0)
+    iq[5] = iq[5] * np.float32(1e-39)
+    iq.setflags(write=False)
+    return iq, targets
+
+
+def fast_path_parent(h, row):
+    """The tile kernel's order before its accumulators were seeded with +0, in
+    float32: W = 8 lane accumulators, each seeded with its first product, block
+    j ascending; the lane sum seeded with lane 0, lanes ascending; then the
+    T mod 8 tail taps (real taps, so I and Q separately)."""
+    T = h.size
+    J = T // 8
+    assert J > 0
+    hrev = h[::-1].astype(np.float32)
+    out = np.zeros_like(row)
+    for c in (0, 1):
+        xp = np.concatenate([np.zeros(T - 1, np.float32), row[c::2]])
+        P = np.lib.stride_tricks.sliding_window_view(xp, T) * hrev     # [n, T] products
+        A = P[:, 0:8].copy()
+        for j in range(1, J):
+            A = A + P[:, 8 * j: 8 * j + 8]
+        acc = A[:, 0].copy()
+        for l in range(1, 8):
+            acc = acc + A[:, l]
+        for k in range(8 * J, T):
+            acc = acc + P[:, k]
+        assert acc.dtype == np.float32
+        out[c::2] = acc
+    return out
+
+
+# ---------------------------------------------------------------------------
+# B. CPU checks
+# ---------------------------------------------------------------------------
+def test_ragged_call_sequence_is_what_the_cases_need():
+    for sps, span in SPECIALISED:
+        T = sps * span + 1
+        calls = ragged_calls(T)
+        assert len(calls) <= 12 and max(map(max, calls)) == 2 * TILE + 1
+        assert all(0 in c for c in calls), "one stream is empty in each call"
+        base = [1, T - 2, T - 1, T, TILE - 1, TILE, TILE + 1, 2 * TILE + 1]
+        for s in range(6):
+            k = min(s, 7)   # the rotation's 0 sits between 2049 and 4097
+            assert [c[s] for c in calls if c[s]] == base[k:] + base[:k]
+
+
+@pytest.mark.parametrize("sps,span", SPECIALISED, ids=_ids(SPECIALISED))
+def test_signed_zero_windows_discriminate(sps, span):
+    """At every placed window the reference gives +0 in both components and
+    the first-product seeding -0; at every other output of the row the two are
+    bit-identical.  So the GPU case below fails on that seeding and only there."""
+    h = rrc(sps, span)
+    assert np.all(h != 0)
+    iq, targets = signed_zero_case(sps, span)
+    for s, ts in targets.items():
+        ref = fir_ref(h, iq[s]).view(np.uint32).reshape(-1, 2)
+        fast = fast_path_parent(h, iq[s]).view(np.uint32).reshape(-1, 2)
+        for t in ts:
+            assert tuple(ref[t]) == (0, 0), f"stream {s} output {t}: reference"
+            assert tuple(fast[t]) == (0x80000000, 0x80000000), f"stream {s} output {t}: fast path"
+        rest = np.ones(ref.shape[0], bool)
+        rest[ts] = False
+        assert np.array_equal(ref[rest], fast[rest]), f"stream {s}: other outputs"
+
+
+def test_every_specialised_tap_count_has_a_case():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "qpsk-modulator-demodulator_amd", "csrc", "qpsk_kernels.hip")) as f:
+        src = f.read()
+    cases = {int(a) for a, b in re.findall(r"case\s+(\d+)\s*:\s*return\s+launch_fir_w8<\s*(\d+)\s*>", src) if a == b}
+    assert len(cases) >= 9
+    assert cases == {sps * span + 1 for sps, span in SPECIALISED}
+
+
+# ---------------------------------------------------------------------------
+# GPU runs
+# ---------------------------------------------------------------------------
+def run_calls(Q, iq, calls, sps, span, n_max, mode=None, **kw):
+    """The host process path with per-stream lengths; per call the decoded rows
+    [(bits, symbols)] and last_mf(max(lens))."""
+    S = iq.shape[0]
+    b = Q.BatchDemodulator(S, Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=n_max, **kw))
+    assert K.bitwise_equal(b.rrc_taps(), rrc(sps, span))
+    pos = np.zeros(S, np.int64)
+    out, mfs = [], []
+    for ci, lens in enumerate(calls):
+        m = mode[ci] if mode else Q.MODE_DEMODULATE
+        n = int(max(lens))
+        x = np.zeros((S, 2 * n), np.float32)
+        for s in range(S):
+            x[s, : 2 * lens[s]] = iq[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
+        bits, nb, syms, ns = b.process(x, mode=m, lengths=np.array(lens, np.int64), want_syms=True)
+        out.append([(Q.unpack_bits(bits[s], int(nb[s])) if m == Q.MODE_DEMODULATE else "",
+                     syms[s, : 2 * int(ns[s])].copy()) for s in range(S)])
+        mf = b.last_mf(n)
+        assert mf.shape == (S, 2 * n)
+        mfs.append(mf.copy())
+        pos += np.array(lens)
+    assert b.status() == 0
+    b.close()
+    return out, mfs
+
+
+def assert_rows(mfs, calls, refs):
+    """refs[s]: the reference filter's output over stream s's whole input."""
+    pos = np.zeros(len(refs), np.int64)
+    for ci, (mf, lens) in enumerate(zip(mfs, calls)):
+        for s, n in enumerate(lens):
+            got, want = mf[s, : 2 * n], refs[s][2 * pos[s]: 2 * (pos[s] + n)]
+            if not K.bitwise_equal(got, want):
+                bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+                pytest.fail(f"call {ci} stream {s} (n = {n}): {bad.size} floats differ, first at output "
+                            f"{bad[0] // 2}: {got[bad[0]]!r} vs {want[bad[0]]!r}")
+            assert not is_neg_zero(got).any(), f"call {ci} stream {s}: -0 in the matched filter"
+            pos[s] += n
+
+
+def stage_case(Q, sps, span, n_max, lanes=8, seed=0):
+    T = sps * span + 1
+    calls = ragged_calls(T)
+    total = sum(c[0] for c in calls)
+    assert all(sum(c[s] for c in calls) == total for s in range(6))
+    iq = normal_rows(6, total, seed=seed + T)
+    _, mfs = run_calls(Q, iq, calls, sps, span, n_max, vector_lanes=lanes)
+    assert_rows(mfs, calls, [fir_ref(rrc(sps, span), iq[s], lanes) for s in range(6)])
+
+
+@gpu
+@pytest.mark.parametrize("n_max", [4098, 4097], ids=["float4", "scalar"])
+@pytest.mark.parametrize("sps,span", SPECIALISED, ids=_ids(SPECIALISED))
+def test_specialised_taps_both_stagings_ragged_calls(Q, sps, span, n_max):
+    """A1.  The host staging rows have a stride of max_samples_per_call samples:
+    even takes the float4 staging loop, odd the scalar one."""
+    stage_case(Q, sps, span, n_max, seed=1000 + n_max)
+
+
+@gpu
+@pytest.mark.parametrize("sps,span", [(8, 8), (4, 32)], ids=_ids([(8, 8), (4, 32)]))
+def test_device_input_layouts(Q, sps, span):
+    """A2.  Device rows: aligned and contiguous (float4 staging), base advanced
+    by one sample (8-byte aligned only) and a row stride of an odd number of
+    samples (both scalar staging), two calls of 2049 samples each."""
+    import torch
+    S, n = 3, TILE + 1
+    h = rrc(sps, span)
+    iq = normal_rows(S, 2 * n, seed=2000 + h.size)
+    refs = [fir_ref(h, iq[s]) for s in range(S)]
+    even = torch.zeros((S, 2 * (n + 3)), dtype=torch.float32, device="cuda")   # 2052 samples per row
+    odd = torch.zeros((S, 2 * (n + 2)), dtype=torch.float32, device="cuda")    # 2051 samples per row
+    views = {"aligned": even[:, : 2 * n], "one sample in": even[:, 2: 2 * n + 2], "odd stride": odd[:, : 2 * n]}
+    assert views["aligned"].data_ptr() % 16 == 0 and views["aligned"].stride(0) % 4 == 0
+    assert views["one sample in"].data_ptr() % 16 == 8
+    assert views["odd stride"].data_ptr() % 16 == 0 and views["odd stride"].stride(0) % 4 == 2
+    for name, v in views.items():
+        b = Q.BatchDemodulator(S, Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=n + 3))
+        ms = b.max_symbols(n)
+        bits = torch.zeros((S, (2 * ms + 7) // 8 + 8), dtype=torch.uint8, device="cuda")
+        nb = torch.zeros(S, dtype=torch.int64, device="cuda")
+        mfs = []
+        for c in range(2):
+            v.copy_(torch.from_numpy(iq[:, 2 * n * c: 2 * n * (c + 1)]))
+            torch.cuda.synchronize()
+            b.process_device(v, n, bits, nb)
+            mfs.append(b.last_mf(n).copy())
+        b.close()
+        try:
+            assert_rows(mfs, [[n] * S] * 2, refs)
+        except BaseException as e:
+            raise AssertionError(f"layout '{name}': {e}") from e
+
+
+@gpu
+@pytest.mark.parametrize("sps,span,lanes", [(3, 6, 8), (3, 5, 8), (8, 8, 1), (8, 8, 4), (8, 8, 16), (30, 6, 8)],
+                         ids=["T19", "T16", "T65-W1", "T65-W4", "T65-W16", "T181"])
+def test_generic_kernel_ragged_calls(Q, sps, span, lanes):
+    """A3.  Tap counts and lane widths without a tile kernel."""
+    stage_case(Q, sps, span, 4098, lanes=lanes, seed=3000 + lanes)
+
+
+@gpu
+@pytest.mark.parametrize("sps,span", SPECIALISED, ids=_ids(SPECIALISED))
+def test_signed_zero_windows_and_subnormals(Q, sps, span):
+    """A4.  Red before the tile kernel seeded its accumulators with +0
+    (test_signed_zero_windows_discriminate shows why, without a GPU)."""
+    h = rrc(sps, span)
+    iq, _ = signed_zero_case(sps, span)
+    assert np.count_nonzero(np.abs(iq[5]) < np.float32(2.0 ** -126)) > iq.shape[1] // 2
+    calls = [[n] * 6 for n in SZ_CALLS]
+    _, mfs = run_calls(Q, iq, calls, sps, span, max(SZ_CALLS) + 1)
+    assert_rows(mfs, calls, [fir_ref(h, iq[s]) for s in range(6)])
+
+
+@gpu
+@pytest.mark.parametrize("sps,span", [(8, 8), (4, 32)], ids=_ids([(8, 8), (4, 32)]))
+def test_signed_zero_tail_through_the_chain(Q, sps, span):
+    """A5.  Ordinary signal, then >= 64 symbols of the all-(-0)-products pattern
+    back to back (stream 1: of -0), split over two calls inside that tail:
+    bits and symbols of DeModulate and of deModulateConstellation."""
+    from test_gpu_parity import assert_same, oracle_run
+    h = rrc(sps, span)
+    T = h.size
+    sig = K.batch_signals(2, seed0=810, sps=sps, span=span, n_bits=800, snr_db=18)
+    pattern = np.where(h[::-1] >= 0, np.float32(-0.0), np.float32(0.0)).astype(np.float32)   # time order
+    reps = -(-64 * sps // T) + 1
+    tail = np.repeat(np.tile(pattern, reps), 2)                                              # I = Q
+    assert tail.size // 2 >= 64 * sps
+    iq = np.stack([np.concatenate([sig[0], tail]), np.concatenate([sig[1], np.full_like(tail, -0.0)])])
+    n = iq.shape[1] // 2
+    n1 = sig.shape[1] // 2 + tail.size // 4 + 3
+    calls = [[n1] * 2, [n - n1] * 2]
+    for modes in ([Q.MODE_DEMODULATE] * 2, [Q.MODE_CONSTELLATION] * 2):
+        got, mfs = run_calls(Q, iq, calls, sps, span, n, mode=modes)
+        assert_same(got, oracle_run(iq, calls, sps, span, mode=modes))
+        assert_rows(mfs, calls, [fir_ref(h, iq[s]) for s in range(2)])
+
+
+@gpu
+def test_fll_then_matched_filter_on_degenerate_streams(Q):
+    """A6.  The FLL in front of the filter on all +0, all -0, a subnormal-scaled
+    signal, a constant 0.25 and a normal signal, in ragged calls (shorter than
+    an 8-sample block and than the 40-tap window, empty ones): bits and symbols
+    against the reference chain, and each call's matched-filter rows against
+    the reference filter over the reference FLL's output."""
+    from test_gpu_parity import assert_same, oracle_run
+    sps, span, S = 8, 8, 5
+    iq = K.batch_signals(S, seed0=830, sps=sps, span=span, n_bits=900, cfo_hz=-3000.0, snr_db=22)
+    iq[0] = np.float32(0.0)
+    iq[1] = np.float32(-0.0)
+    iq[2] = iq[2] * np.float32(1e-39)
+    assert np.count_nonzero(np.abs(iq[2]) < np.float32(2.0 ** -126)) > iq.shape[1] // 2
+    iq[3] = np.float32(0.25)
+    n = iq.shape[1] // 2
+    rng = np.random.default_rng(8)
+    calls, used = [], np.zeros(S, np.int64)
+    for c in range(8):
+        lens = rng.integers(0, 50, S) if c < 6 else np.full(S, 37)
+        lens[c % S] = 0
+        calls.append([int(v) for v in lens])
+        used += lens
+    calls.append([int(n - u) for u in used])
+    got, mfs = run_calls(Q, iq, calls, sps, span, n, enable_fll=True)
+    assert_same(got, oracle_run(iq, calls, sps, span, enable_fll=True))
+    # the FLL as OracleDemod builds it (QPSKDeModulator.cs:35): integer fs / rs,
+    # 40 taps, the default CFO loop bandwidth (float 1e-4), portable trig
+    refs = []
+    for s in range(S):
+        fll = O.OracleFLL(float(K.FS // (K.FS // sps)), K.ALPHA, 40, float(np.float32(0.0001)), lanes=8,
+                          trig=O.TRIG_PORTABLE)
+        pos, parts = 0, []
+        for lens in calls:
+            if lens[s]:
+                parts.append(fll.process(iq[s, 2 * pos: 2 * (pos + lens[s])]))
+            pos += lens[s]
+        refs.append(fir_ref(rrc(sps, span), np.concatenate(parts)))
+    assert_rows(mfs, calls, refs)
+
+
+@gpu
+def test_last_mf_argument_checks(Q):
+    """A7."""
+    b = Q.BatchDemodulator(2, Q.params(K.FS, K.FS // 8, K.ALPHA, 8, max_samples_per_call=100))
+    b.process(normal_rows(2, 100, seed=5))
+    for n in (101, -1):
+        with pytest.raises(ValueError):   # QPSK_ERR_ARGUMENT
+            b.last_mf(n)
+    z = b.last_mf(0)
+    assert z.shape == (2, 0) and z.dtype == np.float32
+    assert b.last_mf(100).shape == (2, 200)
+    b.close()
