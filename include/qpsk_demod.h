@@ -88,8 +88,9 @@ typedef struct qpsk_demod_params {
     int32_t loop_variant;           /* symbol-loop kernel shape: 0 = auto,
                                        1 = 16 streams x 64-sample rounds, 2 = 32 x 64,
                                        3 = 16 x 128 (sps >= 2 only), 4 = 24 x 128 (sps >= 8
-                                       only, else auto), 5 = retired (64 x 32,
-                                       measured slower; runs as auto), 6 = 12 x 256,
+                                       only, else auto), 5 = 64 x 64 on the two-slot
+                                       sample ring (sps >= 4 and costas_trig 0 only,
+                                       else auto), 6 = 12 x 256,
                                        7 = 6 x 512 (both sps >= 8 only, else auto;
                                        32 busy lanes); results are
                                        identical */
@@ -208,6 +209,32 @@ int qpsk_demod_gate_timeouts(qpsk_demod *h, uint64_t *count);
  * which no batch past the 12 x 256 bound meets; it is only picked on request.)
  * A requested variant != 0 is returned unchanged.  Needs no device. */
 int32_t qpsk_demod_pick_loop_variant(int32_t requested, int32_t n_streams, double sps, int32_t cus);
+/* The geometry of the symbol-loop shape a handle of n_streams streams runs for
+ * a requested loop_variant (through qpsk_demod_pick_loop_variant and the
+ * launcher's own rule for what that leaves at 0), on a device of cus CUs
+ * (0 = unknown) with a matched filter of rrc_taps taps (rrc_span * sps + 1),
+ * for costas_trig 0 / 1 and with (1) or without (0) symbol output.  The
+ * launcher's rule: at 4 <= sps < 8 and costas_trig 0, 64 streams x 64-sample
+ * rounds on the two-slot ring where n_streams * rrc_taps >= cus * 16 * 129
+ * (the matched filter of the next pipelined call sets the step: C3), else
+ * 32 x 64.  Needs no device. */
+typedef struct qpsk_loop_shape {
+    int32_t streams;        /* streams (LDS rows) per workgroup                          */
+    int32_t lanes;          /* busy lanes of the stage waves (>= streams: shadow lanes)   */
+    int32_t round;          /* samples per round                                          */
+    int32_t slots;          /* rounds the sample ring holds: 4, or 2 (two-slot ring)      */
+    int32_t prefix;         /* two-slot ring: samples loaded in front of a round, else 0  */
+    int32_t cap;            /* symbol slots per stream and round (row stride cap + 1)     */
+    int32_t lds_bytes;      /* LDS of the workgroup                                       */
+    int32_t fir_beside;     /* matched-filter workgroups of the next pipelined call that  */
+    int32_t fir_taps;       /*   fit the CU beside it, of this many taps, each of         */
+    int32_t fir_lds_bytes;  /*   this much LDS (0: no claim made, e.g. with symbols)      */
+    int32_t lds_granule;    /* LDS allocation granule of a CU, bytes                      */
+    int32_t reserved;
+    double lag_max;         /* largest backlog (samples) a stream carries into a round    */
+} qpsk_loop_shape;
+int qpsk_demod_loop_shape(int32_t requested, int32_t n_streams, double sps, int32_t cus, int32_t rrc_taps,
+                          int32_t costas_trig, int32_t want_syms, qpsk_loop_shape *out);
 /* OR of the QPSK_STATUS_* flags raised since the last qpsk_demod_status call
  * (waits for every queued call), then cleared.  0 = every call so far stayed
  * inside the reference's defined behaviour. */

@@ -19,6 +19,8 @@
 //                     the rotated symbols of round r-2
 //   round r = samples [r*kB, (r+1)*kB) of every stream's queue; one raw
 //   s_barrier per round hands every ring slot one stage forward.
+//   (64 streams x 64-sample rounds, loop_variant 5 and the automatic shape at
+//   C3, run on the two-slot ring below: every lane busy, loader 1 round ahead.)
 //
 // The stages never feed back into an earlier one (Costas does not drive the
 // timing loop) and symbols flow in order, so the outputs are exactly the
@@ -32,6 +34,7 @@
 // -ffp-contract=off: every float/double op rounds as the reference C#.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <type_traits>
 
@@ -61,6 +64,24 @@ template <int KB> struct Ring {
     static constexpr int len = 4 * KB;
     static constexpr int row = kMir + len;   // per-stream LDS row: [mirror 4][ring]
 };
+// The two-slot ring (SLOTS = 2): a row is [kPre | KB][kPre | KB] + 16 B of pad
+// (without the pad every stream's sample k sits on one bank).  Slot r & 1 holds
+// the queue samples [KB r - kPre, KB r + KB): round r and the kPre samples
+// before it, which are contiguous in the MF row, so the loader brings the
+// prefix with the round.  Every tap of a symbol processed in round r, whose
+// b - 1 >= KB r - kPre (backlog <= kPre - 4) and b + 2 < KB (r + 1), lies in
+// its own slot: no mirror, no wrap copy and no index mask on the M&M chain.
+// The row takes 8 (2 KB + 34) B instead of 8 (4 KB + 4), which is what lets 64
+// streams x 64-sample rounds into a CU's LDS; the loader's lead is one round.
+constexpr int kPre = 16;
+template <int KB> struct Ring2 {
+    static constexpr int slot = kPre + KB;
+    static constexpr int row = 2 * slot + 2;
+};
+template <int KB, int SLOTS> struct RingRow {
+    static_assert(SLOTS == 2 || SLOTS == 4, "ring slots");
+    static constexpr int value = SLOTS == 2 ? Ring2<KB>::row : Ring<KB>::row;
+};
 // symbols per round per stream (template CAP): at most floor((KB + 3) / (sps - 0.1)) + 1
 // start in one round: 75 (KB 64, sps >= 1), 36 (KB 64, sps >= 2), 69 (KB 128, sps >= 2)
 constexpr int kCapAny = 80;
@@ -80,6 +101,11 @@ constexpr int kCap256Sps8 = 51;
 // 512-sample rounds at sps >= 8 (variant 7): lag_max = 256 needs CAP >= 99;
 // 100 makes the row stride (CAP + 1) odd
 constexpr int kCap512Sps8 = 100;
+// the two-slot ring: lag_max = kPre - 4 = 12, so (CAP - 1)(sps - 0.1) >= KB + 16
+// -> 64-sample rounds: CAP = 22 (sps >= 4), 12 (sps >= 8); CAP + 1 odd
+constexpr int kCap2Sps4 = 22;
+constexpr int kCap2Sps8 = 12;
+// (32 x 128 on the same ring, CAP 38 / 20, measured and not kept: DESIGN 3.2)
 typedef double d2 __attribute__((ext_vector_type(2)));
 
 // M&M -> Costas symbol slots.  64-sample rounds (the 32 x 64 shapes of C3, C4
@@ -102,8 +128,9 @@ template <> struct SymPut<f2> {
     __device__ static f2 put(float ci, float cq, double, double) { return f2{ci, cq}; }
 };
 // (the glibc-trig Costas step paces its loop at every shape: doubles there)
-template <int KB, int TRIG>
-using SymSlot = typename std::conditional<KB == 64 && TRIG == 0, f2, d2>::type;
+// (the two-slot shapes run TRIG 0 with the M&M pacing: floats)
+template <int KB, int TRIG, int SLOTS>
+using SymSlot = typename std::conditional<(KB == 64 || SLOTS == 2) && TRIG == 0, f2, d2>::type;
 
 __device__ __forceinline__ int wave_max_i32(int v) {
 #pragma unroll
@@ -171,7 +198,7 @@ struct RowStride { static constexpr int value = CAP + 1; };
 // when no symbols are written out: at C3 the workgroup drops from 125 KB to
 // 114 KB of LDS, and two matched-filter workgroups of the next pipelined
 // call fit beside it instead of one
-template <int SPW, int CAP, int KB, int TRIG, bool ROTB>
+template <int SPW, int CAP, int KB, int TRIG, bool ROTB, int SLOTS>
 struct LoopLds {
     static constexpr int RS = RowStride<CAP>::value;
     double tab[TRIG ? 880 : 1024];  // sincos table head, at LDS offset 0 so
@@ -180,25 +207,28 @@ struct LoopLds {
     // immediate offset is 16 bits, so the Costas wave's per-step slot reads and
     // writes then fold their constant part into the instruction instead of one
     // v_add_u32 each (behind the 66 KB ring they did)
-    SymSlot<KB, TRIG> sym[2 * SPW * RS];   // M&M -> Costas [slot][stream][RS] (see SymSlot)
+    SymSlot<KB, TRIG, SLOTS> sym[2 * SPW * RS];   // M&M -> Costas [slot][stream][RS] (see SymSlot)
     typename std::conditional<ROTB, uint16_t, f2>::type rot[2 * SPW * RS];   // Costas -> decode
     int cnt[4 * SPW + 4];          // symbols produced by the M&M in round r: cnt[r & 3];
                                    // cnt[4*SPW + (r & 3)] = their minimum over the batch
-    alignas(16) f2 mf[SPW * Ring<KB>::row];   // sample ring [stream][mirror | 4 rounds x KB]
+    // sample ring [stream][mirror | 4 rounds x KB], or [stream][2 x (prefix | KB) | pad]
+    alignas(16) f2 mf[SPW * RingRow<KB, SLOTS>::value];
 };
 
 // SPW = streams (LDS rows) per workgroup; ACT >= SPW = lanes of the stage
 // waves that run the chains: lanes SPW <= l < ACT shadow the workgroup's first
 // stream on its own LDS rows (same addresses as lane 0, same values written),
 // so a shape with few rows (long rounds) still keeps its waves' lanes busy
-template <int MODE, bool DIFF, bool SYMS, int SPW, int CAP, int KB, int TRIG, int ACT>
+template <int MODE, bool DIFF, bool SYMS, int SPW, int CAP, int KB, int TRIG, int ACT, int SLOTS>
 __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
     static_assert(ACT >= SPW && ACT <= (TRIG ? 32 : 64), "active lanes");
-    constexpr int kRing = Ring<KB>::len, kRowS = Ring<KB>::row;
+    constexpr int kRing = Ring<KB>::len, kRowS = RingRow<KB, SLOTS>::value;
+    constexpr bool TWO = SLOTS == 2;
+    constexpr int kSlot = Ring2<KB>::slot;   // samples per slot of the two-slot ring
     // one LDS object only: a second __shared__ object would make hipcc drain the
     // loader's LDS-DMA before touching it (cdna_hip_programming.md §5)
     constexpr bool ROTB = !SYMS;
-    __shared__ LoopLds<SPW, CAP, KB, TRIG, ROTB> L;
+    __shared__ LoopLds<SPW, CAP, KB, TRIG, ROTB, SLOTS> L;
 
     const int wave = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
@@ -272,6 +302,92 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
         a.probe[blockIdx.x * 16 + 12 + wave] = hw | (static_cast<unsigned long long>(xcc) << 32);
     }
 #endif
+    if constexpr (TWO) if (wave == 0) {
+        // ============================================ loader, two-slot ring
+        // a slot = kSlot samples = NL lanes x 16 B: one instruction at KB = 64
+        // (40 lanes), two at KB = 128 (64 + 8 lanes).  Lane l of instruction h
+        // carries the queue samples KB r - kPre + 2 l + 128 h (+1)
+        constexpr int NL = kSlot / 2, NI = (NL + 63) / 64;
+        const int64_t org = valid ? sc * a.mf_stride + kMfPrefix - R - d : 0;
+        const f2 *mf = reinterpret_cast<const f2 *>(a.mf);
+        // fast path as in the four-slot loader below: per-stream byte offsets
+        // relative to the workgroup's first MF row (>= 0: the prefix's -kPre
+        // rides on the round's base), held in VGPRs
+        const f2 *wg_mf = mf + static_cast<int64_t>(blk_s0) * a.mf_stride;
+        uint32_t voff[SPW];
+#pragma unroll
+        for (int j = 0; j < SPW; ++j) {
+            const int jj = j < nvalid ? j : 0;
+            const int64_t oj = readlane64(org, jj) - static_cast<int64_t>(blk_s0) * a.mf_stride;
+            voff[j] = static_cast<uint32_t>((oj + 2 * lane) * 8);
+        }
+        int cmin = valid ? cnt : 0x7fffffff;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int w = __shfl_xor(cmin, o, 64);
+            cmin = w < cmin ? w : cmin;
+        }
+        cmin = __builtin_amdgcn_readfirstlane(cmin);
+        // the 32-bit offsets reach every row of the workgroup
+        const bool near = static_cast<int64_t>(SPW) * a.mf_stride * 8 < (1ll << 32);
+        auto issue = [&](int r) {
+            f2 *slot = L.mf + (r & 1) * kSlot;
+            // round 0 has no samples before it: its prefix lanes stay off (no
+            // symbol of round 0 reads below physical index 0)
+            const int first = r == 0 ? kPre / 2 : 0;
+            if (near && (r + 1) * KB <= cmin) {
+                const char *rb = reinterpret_cast<const char *>(wg_mf + (static_cast<int64_t>(r) * KB - kPre));
+#pragma unroll
+                for (int j = 0; j < SPW; ++j)
+#pragma unroll
+                    for (int h = 0; h < NI; ++h)
+                        if (lane + 64 * h >= first && lane + 64 * h < NL)
+                            __builtin_amdgcn_global_load_lds((glb_void_t *)(rb + voff[j] + 1024 * h),
+                                                             (lds_void_t *)(slot + j * kRowS + 128 * h), 16, 0, 0);
+                return;
+            }
+#pragma unroll 4
+            for (int j = 0; j < SPW; ++j) {
+                const int c = __builtin_amdgcn_readlane(cnt, j);
+                const int64_t o = readlane64(org, j);
+#pragma unroll
+                for (int h = 0; h < NI; ++h) {
+                    int p = r * KB - kPre + 2 * lane + 128 * h;
+                    // before the queue or past the stream's end: read a harmless
+                    // in-row pair (never used); a pair straddling the end reads
+                    // one sample of row slack
+                    if (p >= c || p < 0) p = 0;
+                    if (lane + 64 * h < NL)
+                        __builtin_amdgcn_global_load_lds((glb_void_t *)(mf + o + p),
+                                                         (lds_void_t *)(slot + j * kRowS + 128 * h), 16, 0, 0);
+                }
+            }
+        };
+#ifdef QPSK_LOOP_STAMPS
+        unsigned long long t_wait = 0, t_bar = 0, t_issue = 0;
+#endif
+        if (NR > 0) issue(0);
+        for (int r = 0; r <= NR + 1; ++r) {
+            STAMP(ta);
+            // round r's loads done; round r + 1 goes into the other slot, which
+            // the M&M wave left at this barrier
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            ACC(t_wait, ta);
+            STAMP(tb);
+            __builtin_amdgcn_s_barrier();
+            ACC(t_bar, tb);
+            STAMP(ti);
+            if (r + 1 < NR) issue(r + 1);
+            ACC(t_issue, ti);
+        }
+#ifdef QPSK_LOOP_STAMPS
+        if (a.probe && lane == 0) {
+            a.probe[blockIdx.x * 16 + 0] = t_wait;
+            a.probe[blockIdx.x * 16 + 1] = t_bar + (t_issue << 32);
+        }
+#endif
+        return;
+    }
     if (wave == 0) {
         // ============================================================ loader
         // one glds instruction = KB/2 lanes x 16 B = one stream's round (8*KB
@@ -377,8 +493,20 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
         int nsym = 0;
         bool stop = !mine;                          // capacity reached (MuellerMuller.cs:101-102)
         f2 *row = L.mf + rowl * kRowS;
-        // taps x[b-1..b+2] of physical index b: contiguous thanks to the mirror
-        auto taps = [&](int b) -> const f2 * { return row + kMir - 3 + ((b + 2) & (kRing - 1)); };
+        // taps x[b-1..b+2] of physical index b: contiguous thanks to the mirror.
+        // Two-slot ring: sample p of round rr sits at slot index p - (KB rr - kPre);
+        // a base outside the slot (a stream not stepping in this round) is
+        // clamped into it, its taps are never used
+        int rr = 0;
+        auto taps = [&](int b) -> const f2 * {
+            if constexpr (TWO) {
+                int i = b - 1 - (rr * KB - kPre);
+                i = i < 0 ? 0 : (i > kSlot - 4 ? kSlot - 4 : i);
+                return row + (rr & 1) * kSlot + i;
+            } else {
+                return row + kMir - 3 + ((b + 2) & (kRing - 1));
+            }
+        };
         // Timing runs in the reference's coordinates: t = baseIndex + mu with
         // baseIndex counted from the start of the whole DeModulate call's queue
         // (MuellerMuller.cs:113-115 rounds newTime at that magnitude).  P = the
@@ -388,18 +516,25 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
         const int dP = d - P;
         // the same address straight from floor(t): fl + (1.5*2^52 + dP + 2) holds
         // b + 2 in its low mantissa bits (no float->int conversion on the chain)
-        const double tap_shift = 6755399441055744.0 + static_cast<double>(dP + 2);
+        // Two-slot ring: the shift also carries the round's slot, dP - 1 -
+        // (KB r - kPre) + (r & 1) kSlot, set once per round, and the low
+        // mantissa bits are the row index as they stand (no mask)
+        double tap_shift = 6755399441055744.0 + static_cast<double>(dP + 2);
         // loop-invariant LDS address of x[-3] relative to the ring, kept opaque so
         // the whole base lives in one VGPR and the tap reads use immediate offsets
         typedef __attribute__((address_space(3))) const f2 lds_f2;
-        uint32_t tap0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_f2 *)(row + kMir - 3)));
+        uint32_t tap0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_f2 *)(TWO ? row : row + kMir - 3)));
         asm volatile("" : "+v"(tap0));
-        auto taps_fl = [&](double fl) -> lds_f2 * {
+        // clampv (two-slot ring, the per-lane steps): the taps fetched for a
+        // symbol that may start past the round stay inside the row
+        auto taps_fl = [&](double fl, auto clampv) -> lds_f2 * {
             union { double v; unsigned long long u; } kb;
             kb.v = fl + tap_shift;
             // and + lshl_add: one op shorter than the shift, and, add the
             // compiler canonicalises 8 * (i & m) + base into
-            const uint32_t idx = static_cast<uint32_t>(kb.u) & (kRing - 1);
+            uint32_t idx = static_cast<uint32_t>(kb.u);
+            if constexpr (!TWO) idx &= kRing - 1;
+            else if constexpr (decltype(clampv)::value) idx = idx < 2 * kSlot - 4 ? idx : 2 * kSlot - 4;
             uint32_t addr;
             asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(addr) : "v"(idx), "v"(tap0));
             return reinterpret_cast<lds_f2 *>(static_cast<uintptr_t>(addr));
@@ -415,7 +550,8 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
         // round: half a round keeps its taps inside the ring slots not being
         // refilled, and a round then holds at most (KB + lag_max + 4)/(sps - 0.1) + 1
         // <= CAP symbols; <= 0 (small sps) means every round is finished
-        const double lag_max = fmin(0.5 * KB, (CAP - 1) * (sps - 0.1) - KB - 4.0);
+        // (two-slot ring: the backlog is read from the slot's prefix, kPre - 4)
+        const double lag_max = fmin(TWO ? kPre - 4.0 : 0.5 * KB, (CAP - 1) * (sps - 0.1) - KB - 4.0);
         // logical time baseIndex + mu.  After baseIndex = floor(t), mu = t - baseIndex
         // (exact, Sterbenz), (double)baseIndex + mu == t exactly, so the reference's
         // next time baseIndex + mu + advance (MuellerMuller.cs:113) is simply t + advance
@@ -428,13 +564,21 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
 #ifdef QPSK_LOOP_STAMPS
         unsigned long long c_bar = 0, c_loop = 0, c_iters = 0, c_uni = 0, c_uit = 0, c_pre = 0, c_post = 0;
 #endif
+        constexpr std::integral_constant<int, 0> kNoLoad{};
+        constexpr std::integral_constant<int, 1> kLoad{};
+        constexpr std::integral_constant<int, 2> kLoadClamped{};
         for (int r = 0; r <= NR + 1; ++r) {
             STAMP(tb);
             __builtin_amdgcn_s_barrier();
             ACC(c_bar, tb);
             if (r >= NR) continue;
             STAMP(tl);
-            if ((r & 3) == 0 && r > 0 && mine && lane < SPW) {
+            if constexpr (TWO) {
+                rr = r;
+                tap_shift = 6755399441055744.0 +
+                            static_cast<double>(dP - 1 + kPre - r * KB + (r & 1) * kSlot);
+            }
+            if (!TWO && (r & 3) == 0 && r > 0 && mine && lane < SPW) {
                 // mirror = last 4 samples of the ring (round r-1, already consumed)
                 row[0] = row[kMir + kRing - 4]; row[1] = row[kMir + kRing - 3];
                 row[2] = row[kMir + kRing - 2]; row[3] = row[kMir + kRing - 1];
@@ -465,7 +609,8 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
                 cq = acc.y;
             };
             // advance timing by adv (MuellerMuller.cs:113-115) and fetch the next taps
-            // LOAD = false: a round's last uniform step fetches no taps; they
+            // (kLoadClamped: of a symbol that may start past the round, taps_fl)
+            // kNoLoad: a round's last uniform step fetches no taps; they
             // would be stale (samples of the next round) and the round-start
             // reload would first have to wait for them
             auto advance = [&](double adv, auto load) {
@@ -473,8 +618,8 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
                 const double fl = floor(nt);
                 mu = nt - fl;
                 base = static_cast<int>(fl) + dP;
-                if constexpr (decltype(load)::value) {
-                    tp = taps_fl(fl);
+                if constexpr (decltype(load)::value != 0) {
+                    tp = taps_fl(fl, std::integral_constant<bool, decltype(load)::value == 2>{});
                     xm1 = tp[0]; x0 = tp[1]; x1 = tp[2]; x2 = tp[3];
                     // the tap loads go out before anything after them in the
                     // source (the step's symbol store, the next interpolation's
@@ -492,11 +637,11 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
                 interp(ci, cq);
                 has_prev = 1;
                 psid = ci; psqd = cq;
-                out[k++] = SymPut<SymSlot<KB, TRIG>>::put(ci, cq, psid, psqd);
+                out[k++] = SymPut<SymSlot<KB, TRIG, SLOTS>>::put(ci, cq, psid, psqd);
                 psi = ci; psq = cq;
                 pdid = ci >= 0.0f ? 1.0 : -1.0;
                 pdqd = cq >= 0.0f ? 1.0 : -1.0;
-                advance(sps, std::true_type{});
+                advance(sps, kLoadClamped);
             }
             auto step = [&](auto load) {
                 float ci, cq;
@@ -521,7 +666,7 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
                 pdid = did; pdqd = dqd;
                 advance(sps + corr, load);
                 // stored after the next taps' loads (LDS serves in issue order)
-                out[k++] = SymPut<SymSlot<KB, TRIG>>::put(ci, cq, cid, cqd);
+                out[k++] = SymPut<SymSlot<KB, TRIG, SLOTS>>::put(ci, cq, cid, cqd);
 #ifdef QPSK_LOOP_STAMPS
                 ++c_iters;
 #endif
@@ -567,15 +712,15 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
                     // 18.4 -> 17.3 ms (326 -> 306 cycles per symbol, A/B x2 on one
                     // MI355X, profiles/r05_loop_unroll4_ab.txt); C3 / C4 unchanged
                     for (; u + 4 < kg; u += 4) {
-                        step(std::true_type{});
-                        step(std::true_type{});
-                        step(std::true_type{});
-                        step(std::true_type{});
+                        step(kLoad);
+                        step(kLoad);
+                        step(kLoad);
+                        step(kLoad);
                     }
-                    if (kg - u >= 4) step(std::true_type{});
-                    if (kg - u >= 3) step(std::true_type{});
-                    if (kg - u >= 2) step(std::true_type{});
-                    if (kg - u >= 1) step(std::false_type{});
+                    if (kg - u >= 4) step(kLoad);
+                    if (kg - u >= 3) step(kLoad);
+                    if (kg - u >= 2) step(kLoad);
+                    if (kg - u >= 1) step(kNoLoad);
                 }
                 ACC(c_uni, tu);
 #ifdef QPSK_LOOP_STAMPS
@@ -595,7 +740,7 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
                 };
                 if (__builtin_amdgcn_ballot_w64(more()) != 0) {   // one vote skips the loop in steady state
                     reload();                   // the uniform loop ended on a tap-less step
-                    while (more()) step(std::true_type{});
+                    while (more()) step(kLoadClamped);
                 }
             }
             nsym += k;
@@ -732,7 +877,7 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
             // fast path for ~10^5 calls (profiles/archive/r02_state_c3.log: a 4096-stream
             // C3 batch has 27 such streams after 6 calls; with the old 1e6 range
             // their 26 workgroups redid every round and the kernel took 2.7x)
-            auto widen = [](SymSlot<KB, TRIG> v) { return from_sym(v); };
+            auto widen = [](SymSlot<KB, TRIG, SLOTS> v) { return from_sym(v); };
             // the previous step's decisions, stored under this step's table loads
             // (row entry CAP, past the round's symbols, takes the first store)
             typename std::remove_reference<decltype(out[0])>::type pend{};
@@ -959,59 +1104,146 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
     if (a.n_bits) a.n_bits[s] = MODE == kModeDemodulate ? nbits : 0;
 }
 
-template <int SPW, int CAP, int KB, int TRIG, int ACT>
+template <int SPW, int CAP, int KB, int TRIG, int ACT, int SLOTS>
 static int launch_loop_spw_t(const LoopArgs &a, const LoopParams &P, int mode, hipStream_t stream) {
     dim3 grid((a.S + SPW - 1) / SPW), block(256);
     const bool syms = a.syms != nullptr;
     const bool diff = P.differential != 0;
     if (mode == kModeConstellation)
-        hipLaunchKernelGGL((loop_kernel<kModeConstellation, false, true, SPW, CAP, KB, TRIG, ACT>), grid, block, 0, stream, a, P);
+        hipLaunchKernelGGL((loop_kernel<kModeConstellation, false, true, SPW, CAP, KB, TRIG, ACT, SLOTS>), grid, block, 0, stream, a, P);
     else if (diff && syms)
-        hipLaunchKernelGGL((loop_kernel<kModeDemodulate, true, true, SPW, CAP, KB, TRIG, ACT>), grid, block, 0, stream, a, P);
+        hipLaunchKernelGGL((loop_kernel<kModeDemodulate, true, true, SPW, CAP, KB, TRIG, ACT, SLOTS>), grid, block, 0, stream, a, P);
     else if (diff)
-        hipLaunchKernelGGL((loop_kernel<kModeDemodulate, true, false, SPW, CAP, KB, TRIG, ACT>), grid, block, 0, stream, a, P);
+        hipLaunchKernelGGL((loop_kernel<kModeDemodulate, true, false, SPW, CAP, KB, TRIG, ACT, SLOTS>), grid, block, 0, stream, a, P);
     else if (syms)
-        hipLaunchKernelGGL((loop_kernel<kModeDemodulate, false, true, SPW, CAP, KB, TRIG, ACT>), grid, block, 0, stream, a, P);
+        hipLaunchKernelGGL((loop_kernel<kModeDemodulate, false, true, SPW, CAP, KB, TRIG, ACT, SLOTS>), grid, block, 0, stream, a, P);
     else
-        hipLaunchKernelGGL((loop_kernel<kModeDemodulate, false, false, SPW, CAP, KB, TRIG, ACT>), grid, block, 0, stream, a, P);
+        hipLaunchKernelGGL((loop_kernel<kModeDemodulate, false, false, SPW, CAP, KB, TRIG, ACT, SLOTS>), grid, block, 0, stream, a, P);
     return static_cast<int>(grid.x);
 }
 
-template <int SPW, int CAP, int KB, int ACT = SPW>
-static int launch_loop_spw(const LoopArgs &a, const LoopParams &P, int mode, hipStream_t stream) {
-    return P.costas_trig ? launch_loop_spw_t<SPW, CAP, KB, 1, ACT>(a, P, mode, stream)
-                         : launch_loop_spw_t<SPW, CAP, KB, 0, ACT>(a, P, mode, stream);
+// A CU's LDS and its allocation granule, and the matched filter's workgroup
+// (fir_tile_kernel: 2048 outputs + T - 1 inputs, 8 pad slots per 64)
+constexpr int kCuLds = 160 * 1024, kLdsGranule = 1280;
+constexpr int lds_alloc(int bytes) { return (bytes + kLdsGranule - 1) / kLdsGranule * kLdsGranule; }
+constexpr int fir_lds(int T) { return 8 * ((2048 + T - 1) + (((2048 + T - 1) >> 6) << 3) + 8); }
+
+// A loop shape: SPW rows x KB-sample rounds, ACT busy lanes, SLOTS ring slots.
+// FIRS workgroups of the next pipelined call's T = FIRT matched filter fit
+// beside the bits-only workgroup (0: no claim)
+template <int SPW_, int CAP_, int KB_, int ACT_ = SPW_, int SLOTS_ = 4, int FIRS_ = 0, int FIRT_ = 0>
+struct Shape {
+    static constexpr int SPW = SPW_, CAP = CAP_, KB = KB_, ACT = ACT_, SLOTS = SLOTS_, FIRS = FIRS_, FIRT = FIRT_;
+    static constexpr int TRIGS = SLOTS_ == 2 ? 1 : 2;   // the two-slot shapes run the portable trig only
+    static constexpr int lds(int trig, bool syms) {
+        return static_cast<int>(
+            trig ? (syms ? sizeof(LoopLds<SPW, CAP, KB, TRIGS - 1, false, SLOTS>)
+                         : sizeof(LoopLds<SPW, CAP, KB, TRIGS - 1, true, SLOTS>))
+                 : (syms ? sizeof(LoopLds<SPW, CAP, KB, 0, false, SLOTS>)
+                         : sizeof(LoopLds<SPW, CAP, KB, 0, true, SLOTS>)));
+    }
+};
+
+enum LoopShapeId {
+    kSh16x64Any, kSh16x64, kSh16x128, kSh24x128, kSh12x256, kSh6x512, kSh32x64Sps8, kSh32x64Sps4, kSh32x64Sps2,
+    kSh2SlotSps4, kSh2SlotSps8
+};
+
+template <typename F>
+static auto with_shape(LoopShapeId id, F &&f) {
+    switch (id) {
+    case kSh16x64Any: return f(Shape<16, kCapAny, 64>{});
+    case kSh16x64: return f(Shape<16, kCapSps2, 64>{});
+    case kSh16x128: return f(Shape<16, kCap128Sps2, 128>{});
+    case kSh24x128: return f(Shape<24, kCap128Sps8, 128>{});
+    // 12 streams x 256-sample rounds, 32 busy lanes (20 shadow lanes on
+    // row 0): a quarter of the rounds of 32 x 64, 135 KB of LDS
+    case kSh12x256: return f(Shape<12, kCap256Sps8, 256, 32>{});
+    // 6 streams x 512-sample rounds, 26 shadow lanes: 137 KB of LDS
+    case kSh6x512: return f(Shape<6, kCap512Sps8, 512, 32>{});
+    case kSh32x64Sps8: return f(Shape<32, kCapSps8, 64>{});
+    // C3: 102 KB bits-only, two T = 129 matched-filter workgroups beside it
+    case kSh32x64Sps4: return f(Shape<32, kCapSps4, 64, 32, 4, 2, 129>{});
+    // 64 streams x 64-sample rounds on the two-slot ring, every lane busy:
+    // 127 KB bits-only at sps >= 4 (one T = 129 matched-filter workgroup fits
+    // beside it), 114 KB at sps >= 8 (two T = 65)
+    case kSh2SlotSps4: return f(Shape<64, kCap2Sps4, 64, 64, 2, 1, 129>{});
+    case kSh2SlotSps8: return f(Shape<64, kCap2Sps8, 64, 64, 2, 2, 65>{});
+    default: return f(Shape<32, kCapSps2, 64>{});
+    }
 }
 
-int launch_loop(const LoopArgs &a, const LoopParams &P, int mode, int variant, hipStream_t stream) {
+// The loop is latency-bound per stream; a wave's lanes are free, so the
+// default (sps >= 2) is 32 streams x 64-sample rounds.  Measured at C2
+// (profiles/archive/r01_loop_probe.txt): 16 x 64 and 16 x 128 (half the barriers)
+// both run slower per symbol.  sps < 2 needs the 80-symbol round capacity,
+// which fits LDS at 16 streams x 64.  variant (qpsk_demod_params.loop_variant)
+// forces 1 = 16 x 64, 2 = 32 x 64, 3 = 16 x 128, 5 = 64 x 64 on the two-slot
+// ring (sps >= 4, portable trig); all compute identical results.  variant 0
+// (what qpsk_demod_pick_loop_variant leaves to the launcher) takes 64 x 64 at
+// 4 <= sps < 8 where the matched filter sets the step.  Every lane of its
+// stage waves is busy, so it holds half the CUs and issues half the
+// wave-instructions per stream, and the matched filter of the next pipelined
+// call gets them: C3 +5.1 % (profiles/r07_two_slot_ab.txt).  Its chains run
+// ~2 % more cycles per symbol (the Costas wave paces at 64 lanes), so a batch
+// whose loop sets the step keeps 32 x 64: at sps 4 and 129 taps 256 / 1024 /
+// 2048 / 3072 streams lose 1.4 / 1.1 / 2.3 / 3.3 %, and at sps >= 8 (C4) its
+// loop, 436 against 380 cycles per symbol, becomes the step (-10 %).  The
+// filter's time goes with streams x taps and the loop's does not, so the rule
+// is S x taps >= that of the measured win: 16 streams x 129 taps per CU.
+static LoopShapeId resolve_shape(int variant, int S, double sps, int cus, int taps, int trig) {
+    if (sps < 2.0) return kSh16x64Any;
+    if (variant == 1) return kSh16x64;
+    if (variant == 3) return kSh16x128;
+    if (sps >= 8.0) {
+        if (variant == 4) return kSh24x128;
+        if (variant == 6) return kSh12x256;
+        if (variant == 7) return kSh6x512;
+    }
+    const bool two_ok = sps >= 4.0 && !trig;
+    const bool two_auto = variant != 2 && sps < 8.0 && cus > 0 &&
+                          static_cast<int64_t>(S) * taps >= static_cast<int64_t>(cus) * 16 * 129;
+    if (two_ok && (variant == 5 || two_auto)) return sps >= 8.0 ? kSh2SlotSps8 : kSh2SlotSps4;
+    return sps >= 8.0 ? kSh32x64Sps8 : sps >= 4.0 ? kSh32x64Sps4 : kSh32x64Sps2;
+}
+
+int launch_loop(const LoopArgs &a, const LoopParams &P, int mode, int variant, hipStream_t stream, int cus,
+                int taps) {
     hipLaunchKernelGGL(carry_prefix_kernel, dim3(a.S), dim3(64), 0, stream, a);
-    // The loop is latency-bound per stream; a wave's lanes are free, so the
-    // default (sps >= 2) is 32 streams x 64-sample rounds.  Measured at C2
-    // (profiles/archive/r01_loop_probe.txt): 16 x 64 and 16 x 128 (half the barriers)
-    // both run slower per symbol.  sps < 2 needs the 80-symbol round capacity,
-    // which fits LDS at 16 streams x 64.  variant (qpsk_demod_params.loop_variant)
-    // forces 1 = 16 x 64, 2 = 32 x 64, 3 = 16 x 128; all compute identical results.
-    if (P.sps < 2.0)
-        return launch_loop_spw<16, kCapAny, 64>(a, P, mode, stream);
-    else if (variant == 1)
-        return launch_loop_spw<16, kCapSps2, 64>(a, P, mode, stream);
-    else if (variant == 3)
-        return launch_loop_spw<16, kCap128Sps2, 128>(a, P, mode, stream);
-    else if (variant == 4 && P.sps >= 8.0)
-        return launch_loop_spw<24, kCap128Sps8, 128>(a, P, mode, stream);
-    else if (variant == 6 && P.sps >= 8.0)
-        // 12 streams x 256-sample rounds, 32 busy lanes (20 shadow lanes on
-        // row 0): a quarter of the rounds of 32 x 64, 135 KB of LDS
-        return launch_loop_spw<12, kCap256Sps8, 256, 32>(a, P, mode, stream);
-    else if (variant == 7 && P.sps >= 8.0)
-        // 6 streams x 512-sample rounds, 26 shadow lanes: 137 KB of LDS
-        return launch_loop_spw<6, kCap512Sps8, 512, 32>(a, P, mode, stream);
-    else if (P.sps >= 8.0)
-        return launch_loop_spw<32, kCapSps8, 64>(a, P, mode, stream);
-    else if (P.sps >= 4.0)
-        return launch_loop_spw<32, kCapSps4, 64>(a, P, mode, stream);
-    else
-        return launch_loop_spw<32, kCapSps2, 64>(a, P, mode, stream);
+    const LoopShapeId id = resolve_shape(variant, a.S, P.sps, cus, taps, P.costas_trig);
+    return with_shape(id, [&](auto sh) {
+        using T = decltype(sh);
+        static_assert(T::SLOTS != 2 || (T::CAP + 1) % 2 == 1, "odd symbol row stride");
+        static_assert(lds_alloc(T::lds(0, true)) <= kCuLds && lds_alloc(T::lds(1, true)) <= kCuLds,
+                      "the workgroup fits a CU");
+        static_assert(T::FIRS == 0 || lds_alloc(T::lds(0, false)) + T::FIRS * lds_alloc(fir_lds(T::FIRT)) <= kCuLds,
+                      "the matched-filter workgroups claimed beside the bits-only workgroup fit the CU");
+        if (T::TRIGS == 2 && P.costas_trig)
+            return launch_loop_spw_t<T::SPW, T::CAP, T::KB, T::TRIGS - 1, T::ACT, T::SLOTS>(a, P, mode, stream);
+        return launch_loop_spw_t<T::SPW, T::CAP, T::KB, 0, T::ACT, T::SLOTS>(a, P, mode, stream);
+    });
+}
+
+void loop_shape_info(int variant, int S, double sps, int cus, int taps, int trig, int syms, LoopShapeInfo *o) {
+    const LoopShapeId id = resolve_shape(variant, S, sps, cus, taps, trig);
+    with_shape(id, [&](auto sh) {
+        using T = decltype(sh);
+        o->streams = T::SPW;
+        o->lanes = T::ACT;
+        o->round = T::KB;
+        o->slots = T::SLOTS;
+        o->prefix = T::SLOTS == 2 ? kPre : 0;
+        o->cap = T::CAP;
+        // as the M&M wave computes it
+        const double lag = std::fmin(T::SLOTS == 2 ? kPre - 4.0 : 0.5 * T::KB, (T::CAP - 1) * (sps - 0.1) - T::KB - 4.0);
+        o->lag_max = lag;
+        o->lds_bytes = T::lds(trig, syms != 0);
+        o->fir_beside = syms ? 0 : T::FIRS;
+        o->fir_taps = syms ? 0 : T::FIRT;
+        o->fir_lds_bytes = syms || !T::FIRS ? 0 : fir_lds(T::FIRT);
+        o->lds_granule = kLdsGranule;
+        return 0;
+    });
 }
 
 }  // namespace qpsk

@@ -422,7 +422,7 @@ int run_loop(qpsk_demod *h, const Call &c, const int64_t *d_len, float *mf, hipS
     la.clk = kt ? kt + 10 : nullptr;
     la.cu_map = h->fir_phases ? h->d_cu_map : nullptr;
     la.resident = h->gate_publish ? resident : nullptr;
-    const int grid = launch_loop(la, h->lp, c.mode, h->loop_variant, st);
+    const int grid = launch_loop(la, h->lp, c.mode, h->loop_variant, st, h->cus, h->T);
     HIP_TRY(hipGetLastError());
     if (resident) {
         // the next FIR may start once min(grid, CUs) workgroups hold their CUs:
@@ -1450,6 +1450,30 @@ int32_t qpsk_demod_pick_loop_variant(int32_t requested, int32_t n_streams, doubl
     if ((S + 5) / 6 <= cus) return 7;
     if ((S + 11) / 12 <= cus) return 6;
     return 0;
+}
+
+int qpsk_demod_loop_shape(int32_t requested, int32_t n_streams, double sps, int32_t cus, int32_t rrc_taps,
+                          int32_t costas_trig, int32_t want_syms, qpsk_loop_shape *out) {
+    if (!out) return fail(QPSK_ERR_ARGUMENT_NULL, "out is NULL");
+    if (requested < 0 || requested > 7 || n_streams <= 0 || !(sps > 0.0) || costas_trig < 0 || costas_trig > 1)
+        return fail(QPSK_ERR_ARGUMENT, "loop shape arguments");
+    LoopShapeInfo i{};
+    loop_shape_info(qpsk_demod_pick_loop_variant(requested, n_streams, sps, cus), n_streams, sps, cus, rrc_taps,
+                    costas_trig, want_syms, &i);
+    out->streams = i.streams;
+    out->lanes = i.lanes;
+    out->round = i.round;
+    out->slots = i.slots;
+    out->prefix = i.prefix;
+    out->cap = i.cap;
+    out->lds_bytes = i.lds_bytes;
+    out->fir_beside = i.fir_beside;
+    out->fir_taps = i.fir_taps;
+    out->fir_lds_bytes = i.fir_lds_bytes;
+    out->lds_granule = i.lds_granule;
+    out->reserved = 0;
+    out->lag_max = i.lag_max;
+    return QPSK_OK;
 }
 
 // Residency gate default (process_async_one).  The wait is bounded

@@ -100,6 +100,21 @@ class ModParams(C.Structure):
     ]
 
 
+class LoopShape(C.Structure):
+    """qpsk_loop_shape (include/qpsk_demod.h)"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "streams", "lanes", "round", "slots", "prefix", "cap", "lds_bytes", "fir_beside", "fir_taps",
+        "fir_lds_bytes", "lds_granule", "reserved")] + [("lag_max", C.c_double)]
+
+
+def loop_shape(requested, n_streams, sps, cus, costas_trig=0, want_syms=False, rrc_taps=129):
+    """The loop shape a handle would run (qpsk_demod_loop_shape), as a dict; needs no device."""
+    o = LoopShape()
+    _check(lib().qpsk_demod_loop_shape(int(requested), int(n_streams), float(sps), int(cus), int(rrc_taps),
+                                       int(costas_trig), 1 if want_syms else 0, C.byref(o)))
+    return {n: getattr(o, n) for n, _ in LoopShape._fields_ if n != "reserved"}
+
+
 class QPSKError(RuntimeError):
     pass
 
@@ -183,6 +198,8 @@ def lib():
     L.qpsk_demod_gate_timeouts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.qpsk_demod_pick_loop_variant.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_int32]
     L.qpsk_demod_pick_loop_variant.restype = C.c_int32
+    L.qpsk_demod_loop_shape.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.POINTER(LoopShape)]
     L.qpsk_demod_enable_fir_phases.argtypes = [C.c_void_p, C.c_int32]
     L.qpsk_demod_fir_phases.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     L.qpsk_framer_create.argtypes = [C.c_int32, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int64,
@@ -238,7 +255,7 @@ EXPORTED_SYMBOLS = [
     "qpsk_demod_rrc_taps",
     "qpsk_demod_gains", "qpsk_demod_fll_taps", "qpsk_demod_state_bytes", "qpsk_demod_get_state",
     "qpsk_demod_set_state", "qpsk_pipeline_gate_enabled", "qpsk_demod_gate_timeouts",
-    "qpsk_demod_pick_loop_variant",
+    "qpsk_demod_pick_loop_variant", "qpsk_demod_loop_shape",
     "qpsk_demod_enable_fir_phases",
     "qpsk_demod_fir_phases", "qpsk_demod_design", "qpsk_framer_create", "qpsk_framer_destroy",
     "qpsk_framer_set_markers", "qpsk_framer_push", "qpsk_framer_dev_create",
