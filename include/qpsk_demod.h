@@ -188,6 +188,40 @@ int qpsk_demod_process_async(qpsk_demod *h, int32_t mode, const float *iq, int64
                              int64_t n_samples, const int64_t *lengths, uint8_t *bits,
                              int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
                              int64_t syms_stride_floats, int64_t *n_syms);
+/*
+ * CS16 input: interleaved int16 I,Q, the format SDR hardware and SoapySDR
+ * streams deliver natively (the reference asks its driver for CF32 only
+ * because its FIR takes floats, ModDemodOverSDR.cs:116-183).  A sample's value
+ * is (float)x * scale: one exact conversion, then one float multiply (no fma),
+ * done inside the first kernel that reads the samples, so the chain computes
+ * bit for bit what it computes from the widened floats and no float copy of
+ * the input is written to device memory (FLL off, no IQ balancer; with either
+ * of them one widening pass fills an internal row ahead of it).  All state
+ * stays float: a handle may alternate float and CS16 calls freely.
+ *
+ * The scale is per handle, 1.0f / 32768 by default (SoapySDR's CS16 -> CF32
+ * convention), and is captured when a call is issued: set waits for nothing
+ * and affects later calls only; pipelined calls already queued keep theirs.
+ * It must be finite and > 0, else QPSK_ERR_OUT_OF_RANGE.
+ */
+int qpsk_demod_set_cs16_scale(qpsk_demod *h, float scale);
+int qpsk_demod_get_cs16_scale(const qpsk_demod *h, float *scale);
+/* qpsk_demod_process / qpsk_demod_process_async with iq as
+ * [n_streams][stride_i16] int16, stream s holding 2*len(s) int16; every other
+ * argument, check, limit and result as there (calls longer than
+ * max_samples_per_call chunk the same way; qpsk_demod_last_mf works after the
+ * synchronous one).  Device rows must be 4-byte aligned with an even
+ * stride_i16, else QPSK_ERR_ARGUMENT; rows that are 16-byte aligned with
+ * stride_i16 % 8 == 0 are read with 16-byte loads (4 samples), others with
+ * 4-byte loads. */
+int qpsk_demod_process_cs16(qpsk_demod *h, int32_t mode, const int16_t *iq, int64_t stride_i16,
+                            int64_t n_samples, const int64_t *lengths, int32_t mem, uint8_t *bits,
+                            int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                            int64_t syms_stride_floats, int64_t *n_syms);
+int qpsk_demod_process_async_cs16(qpsk_demod *h, int32_t mode, const int16_t *iq, int64_t stride_i16,
+                                  int64_t n_samples, const int64_t *lengths, uint8_t *bits,
+                                  int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                                  int64_t syms_stride_floats, int64_t *n_syms);
 /* 1 if handles created now use the residency gate, 0 if the environment turns
  * it off (the list above); needs no device. */
 int qpsk_pipeline_gate_enabled(void);
@@ -403,6 +437,17 @@ int qpsk_rx_submit(qpsk_rx *r, const float *iq, int64_t stride_floats, int64_t n
  * nothing is outstanding. */
 int qpsk_rx_collect(qpsk_rx *r, uint8_t *bits, int64_t bits_stride_bytes, int64_t *n_bits,
                     int64_t *ticket);
+/* The same ring for CS16 buffers (a SoapySDR CS16 stream read straight into a
+ * slot): qpsk_rx_create / qpsk_rx_next_slot / qpsk_rx_submit with pinned slots
+ * of [n_streams][2 * max_samples_per_call] int16, half the pinned memory and
+ * half the upload bytes, queued as qpsk_demod_process_async_cs16 with the
+ * handle's scale at submit.  collect and destroy are the float ring's.  The
+ * float next_slot / submit on a CS16 ring, and these on a float ring, return
+ * QPSK_ERR_STATE. */
+int qpsk_rx_create_cs16(qpsk_demod *h, int32_t depth, qpsk_rx **out);
+int qpsk_rx_next_slot_cs16(qpsk_rx *r, int16_t **iq, int64_t *stride_i16);
+int qpsk_rx_submit_cs16(qpsk_rx *r, const int16_t *iq, int64_t stride_i16, int64_t n_samples,
+                        const int64_t *lengths, int64_t *ticket);
 
 /* ---------------------------------------------------------------------------
  * Byte framer (DeModulateBytes, QPSKDeModulator.cs:169-259), batched: one

@@ -74,6 +74,29 @@ struct FirArgs {
     const unsigned *cu_map;
 };
 constexpr unsigned kFirClockEvery = 64;
+// Input element format of the matched filter's rows: kFmtCf32 = float2 as
+// above; kFmtCs16 = x points at [S][x_stride] int16 pairs (x_stride still in
+// samples) and a sample's value is (float)v * x_scale, widened by the kernel
+// that loads it.  The CS16 kernels take the scale behind the float kernels'
+// arguments, whose layout (and so the float kernels' code) stays as it was.
+constexpr int32_t kFmtCf32 = 0;
+constexpr int32_t kFmtCs16 = 1;
+struct FirArgsCs16 : FirArgs {
+    float x_scale;
+};
+
+// CS16 rows widened into float2 rows, for the serial pre-stages (IQ balancer,
+// FLL) that read one sample per step and already write a float row
+struct WidenArgs {
+    const int16_t *x;      // [S][x_stride] int16 pairs
+    int64_t x_stride;      // in samples
+    float *y;              // [S][y_stride] float2 output at y_offset
+    int64_t y_stride;
+    int64_t y_offset;
+    const int64_t *lengths;
+    int64_t n;
+    float scale;
+};
 
 struct LoopArgs {
     float *mf;             // [S][mf_stride] float2, MF output at kMfPrefix
@@ -153,8 +176,10 @@ struct IqbArgs {
 // Returns true when a specialised tile kernel was used.
 // hrev_dev: the reversed RRC taps (ComplexFIRFilter._tapsIRev) in device memory.
 bool launch_fir(const FirArgs &a, const float *hrev_dev, int T, int W, int S,
-                int64_t n_max, hipStream_t stream);
-void launch_fir_hist(const FirArgs &a, float *hist_new, int H, int S, hipStream_t stream);
+                int64_t n_max, hipStream_t stream, int32_t x_fmt = kFmtCf32, float x_scale = 0.0f);
+void launch_fir_hist(const FirArgs &a, float *hist_new, int H, int S, hipStream_t stream,
+                     int32_t x_fmt = kFmtCf32, float x_scale = 0.0f);
+void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream);
 // carry kernel + loop kernel; returns the loop kernel's workgroup count
 // cus = the device's CU count, taps = the matched filter's (0: unknown), for the automatic shape
 int launch_loop(const LoopArgs &a, const LoopParams &P, int mode, int variant, hipStream_t stream, int cus = 0,

@@ -30,6 +30,29 @@ namespace qpsk {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
+// CS16 input: one sample = an int16 pair, widened where it is loaded
+typedef short s2 __attribute__((ext_vector_type(2)));
+typedef short s8 __attribute__((ext_vector_type(8)));
+
+template <typename A, typename B> struct same_type { static constexpr bool value = false; };
+template <typename A> struct same_type<A, A> { static constexpr bool value = true; };
+
+// (float)x * scale: an exact conversion and one rounding (no fma: -ffp-contract=off)
+__device__ __forceinline__ f2 widen(s2 v, float scale) {
+    return f2{static_cast<float>(v.x) * scale, static_cast<float>(v.y) * scale};
+}
+// The kernel argument block of each element type, and its scale
+template <typename XT> struct fir_args { typedef FirArgs type; };
+template <> struct fir_args<s2> { typedef FirArgsCs16 type; };
+__device__ __forceinline__ float x_scale(const FirArgs &) { return 0.0f; }
+__device__ __forceinline__ float x_scale(const FirArgsCs16 &a) { return a.x_scale; }
+// Input sample g of a row of either element type; the float2 row is read as it
+// always was (scale unused).
+template <typename XT>
+__device__ __forceinline__ f2 load_x(const XT *x, int64_t g, float scale) {
+    if constexpr (same_type<XT, f2>::value) return x[g];
+    else return widen(x[g], scale);
+}
 
 // ---------------------------------------------------------------------------
 // Matched-filter FIR
@@ -200,8 +223,43 @@ __device__ __forceinline__ void fir_stage(f2 *lds, const f2 *x, const f2 *hist, 
     }
 }
 
-template <int T, int W, int Q, bool VEC, int NT>
-__global__ __launch_bounds__(NT) void fir_tile_kernel(FirArgs a, const float *hrev) {
+// The same LDS image from CS16 rows: the int16 pairs are widened on their way
+// into LDS, so fir_core reads what it reads from a float row.
+template <int T, int NIN, bool VEC, int NT>
+__device__ __forceinline__ void fir_stage_cs16(f2 *lds, const s2 *x, const f2 *hist, int64_t tile0, int64_t n,
+                                               float scale) {
+    const int tid = threadIdx.x;
+    const int64_t g0 = tile0 - (T - 1);
+    auto one = [&](int64_t g) -> f2 {
+        return g < 0 ? hist[T - 1 + g] : (g < n ? widen(x[g], scale) : f2{0.f, 0.f});
+    };
+    if constexpr (VEC) {
+        // g0 is a multiple of 4 (T - 1 is) and rows are 16-B aligned: one
+        // 16-B load = 4 samples, which share a 64-sample LDS row (two 16-B
+        // LDS writes; slot 4p + 8 floor(4p / 64) is 32-B aligned)
+        static_assert((T - 1) % 4 == 0, "CS16 vector staging expects T = 1 mod 4");
+        for (int p = tid; p < (NIN + 3) / 4; p += NT) {
+            const int64_t g = g0 + 4 * p;
+            f2 u[4];
+            if (g >= 0 && g + 3 < n) {
+                const s8 v = *reinterpret_cast<const s8 *>(x + g);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) u[k] = widen(s2{v[2 * k], v[2 * k + 1]}, scale);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) u[k] = one(g + k);
+            }
+            f2 *dst = &lds[lds_slot(4 * p)];
+            *reinterpret_cast<f4 *>(dst) = f4{u[0].x, u[0].y, u[1].x, u[1].y};
+            *reinterpret_cast<f4 *>(dst + 2) = f4{u[2].x, u[2].y, u[3].x, u[3].y};
+        }
+    } else {
+        for (int i = tid; i < NIN; i += NT) lds[lds_slot(i)] = one(g0 + i);
+    }
+}
+
+template <int T, int W, int Q, bool VEC, int NT, typename XT = f2>
+__global__ __launch_bounds__(NT) void fir_tile_kernel(typename fir_args<XT>::type a, const float *hrev) {
     constexpr int TILE = NT * Q;
     constexpr int NIN = TILE + T - 1;
     __shared__ f2 lds[lds_slots(NIN)];
@@ -227,7 +285,7 @@ __global__ __launch_bounds__(NT) void fir_tile_kernel(FirArgs a, const float *hr
         c0 = __builtin_amdgcn_s_memtime();
         r0 = wall_clock64();
     }
-    const f2 *x = reinterpret_cast<const f2 *>(a.x) + s * a.x_stride;
+    const XT *x = reinterpret_cast<const XT *>(a.x) + s * a.x_stride;
     const f2 *hist = reinterpret_cast<const f2 *>(a.hist) + static_cast<int64_t>(s) * (T - 1);
     // phase sample: shader-clock stamps at the phase boundaries (the barriers)
     // and whether a loop workgroup holds this CU (glc read: the map entry was
@@ -240,7 +298,8 @@ __global__ __launch_bounds__(NT) void fir_tile_kernel(FirArgs a, const float *hr
         p0 = __builtin_amdgcn_s_memtime();
     }
 
-    fir_stage<T, NIN, VEC, NT>(lds, x, hist, tile0, n);
+    if constexpr (same_type<XT, f2>::value) fir_stage<T, NIN, VEC, NT>(lds, x, hist, tile0, n);
+    else fir_stage_cs16<T, NIN, VEC, NT>(lds, x, hist, tile0, n, x_scale(a));
     __syncthreads();
     if (ph_wg) p1 = __builtin_amdgcn_s_memtime();
 
@@ -297,11 +356,21 @@ __global__ __launch_bounds__(NT) void fir_tile_kernel(FirArgs a, const float *hr
                 const int64_t go = tile0 + o0 + W * q;   // output sample
                 if (!((bad >> q) & 1u) || go >= n) continue;
                 const int64_t w0 = go - (T - 1);         // its oldest window sample
-                auto xs = [&](int k) -> f2 {
-                    const int64_t g = w0 + k;
-                    return g < 0 ? hist[T - 1 + g] : x[g];
-                };
-                y[go] = fir_exact_one(xs, hrev, T, W);
+                if constexpr (same_type<XT, f2>::value) {
+                    auto xs = [&](int k) -> f2 {
+                        const int64_t g = w0 + k;
+                        return g < 0 ? hist[T - 1 + g] : x[g];
+                    };
+                    y[go] = fir_exact_one(xs, hrev, T, W);
+                } else {
+                    // CS16 rows: the history may hold a NaN or Inf of an earlier float call
+                    const float scale = x_scale(a);
+                    auto xs = [&](int k) -> f2 {
+                        const int64_t g = w0 + k;
+                        return g < 0 ? hist[T - 1 + g] : widen(x[g], scale);
+                    };
+                    y[go] = fir_exact_one(xs, hrev, T, W);
+                }
             }
         }
     }
@@ -315,7 +384,8 @@ __global__ __launch_bounds__(NT) void fir_tile_kernel(FirArgs a, const float *hr
 
 // Any (T, W) without a specialised tile kernel: the reference's formula
 // itself, full complex products included (not on the benchmarked path).
-__global__ __launch_bounds__(256) void fir_generic_kernel(FirArgs a, const float *hrev, int T,
+template <typename XT>
+__global__ __launch_bounds__(256) void fir_generic_kernel(typename fir_args<XT>::type a, const float *hrev, int T,
                                                           int W) {
     const int s = blockIdx.y;
     const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -324,29 +394,31 @@ __global__ __launch_bounds__(256) void fir_generic_kernel(FirArgs a, const float
     if (a.kt && threadIdx.x == 0 && lin < 64) kt_start(a.kt);
     KtEnd kte{lin + kKtLastWgs >= gridDim.x * gridDim.y ? a.kt : nullptr};
     if (t >= n) return;
-    const f2 *x = reinterpret_cast<const f2 *>(a.x) + s * a.x_stride;
+    const XT *x = reinterpret_cast<const XT *>(a.x) + s * a.x_stride;
     const f2 *hist = reinterpret_cast<const f2 *>(a.hist) + static_cast<int64_t>(s) * (T - 1);
     const int64_t w0 = t - T + 1;
     auto xs = [&](int k) -> f2 {
         const int64_t g = w0 + k;
-        return g < 0 ? hist[T - 1 + g] : x[g];
+        return g < 0 ? hist[T - 1 + g] : load_x(x, g, x_scale(a));
     };
     f2 *y = reinterpret_cast<f2 *>(a.y) + s * a.y_stride + a.y_offset;
     y[t] = fir_exact_one(xs, hrev, T, W);
 }
 
-// new_hist = last (T-1) samples of concat(old_hist, x[0..n))
-__global__ void fir_hist_kernel(FirArgs a, float *hist_new, int H, int S) {
+// new_hist = last (T-1) samples of concat(old_hist, x[0..n)); the history is
+// float whatever the input format (CS16 samples enter it widened)
+template <typename XT>
+__global__ void fir_hist_kernel(typename fir_args<XT>::type a, float *hist_new, int H, int S) {
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (idx >= static_cast<int64_t>(S) * H) return;
     const int s = static_cast<int>(idx / H);
     const int k = static_cast<int>(idx % H);
     const int64_t n = a.lengths ? a.lengths[s] : a.n;
-    const f2 *x = reinterpret_cast<const f2 *>(a.x) + s * a.x_stride;
+    const XT *x = reinterpret_cast<const XT *>(a.x) + s * a.x_stride;
     const f2 *ho = reinterpret_cast<const f2 *>(a.hist) + static_cast<int64_t>(s) * H;
     f2 *hn = reinterpret_cast<f2 *>(hist_new) + static_cast<int64_t>(s) * H;
     const int64_t m = n + k;
-    hn[k] = m < H ? ho[m] : x[m - H];
+    hn[k] = m < H ? ho[m] : load_x(x, m - H, x_scale(a));
 }
 
 // ---------------------------------------------------------------------------
@@ -520,64 +592,125 @@ void launch_append(const AppendArgs &a, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------
+// CS16 -> float2 rows ahead of the serial pre-stages (IQ balancer, FLL)
+// ---------------------------------------------------------------------------
+// 16-B loads (4 samples) and two 16-B stores per thread where the rows allow,
+// 4-B loads and 8-B stores otherwise.
+template <bool VEC>
+__global__ __launch_bounds__(256) void widen_kernel(WidenArgs a) {
+    const int s = blockIdx.y;
+    const int64_t n = a.lengths ? a.lengths[s] : a.n;
+    const s2 *x = reinterpret_cast<const s2 *>(a.x) + s * a.x_stride;
+    f2 *y = reinterpret_cast<f2 *>(a.y) + s * a.y_stride + a.y_offset;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if constexpr (VEC) {
+        const int64_t g = 4 * i;
+        if (g + 3 < n) {
+            const s8 v = *reinterpret_cast<const s8 *>(x + g);
+            const f2 u0 = widen(s2{v[0], v[1]}, a.scale), u1 = widen(s2{v[2], v[3]}, a.scale);
+            const f2 u2 = widen(s2{v[4], v[5]}, a.scale), u3 = widen(s2{v[6], v[7]}, a.scale);
+            *reinterpret_cast<f4 *>(y + g) = f4{u0.x, u0.y, u1.x, u1.y};
+            *reinterpret_cast<f4 *>(y + g + 2) = f4{u2.x, u2.y, u3.x, u3.y};
+        } else {
+            for (int64_t k = g; k < n; ++k) y[k] = widen(x[k], a.scale);
+        }
+    } else {
+        if (i < n) y[i] = widen(x[i], a.scale);
+    }
+}
+
+void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream) {
+    if (n_max <= 0 || S <= 0) return;
+    const bool vec = ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.x_stride % 4 == 0) &&
+                     ((reinterpret_cast<uintptr_t>(a.y) & 15) == 0) && (a.y_stride % 2 == 0) &&
+                     (a.y_offset % 2 == 0);
+    const int threads = 256;
+    const int64_t items = vec ? (n_max + 3) / 4 : n_max;
+    dim3 grid(static_cast<unsigned>((items + threads - 1) / threads), static_cast<unsigned>(S));
+    if (vec) hipLaunchKernelGGL(widen_kernel<true>, grid, dim3(threads), 0, stream, a);
+    else hipLaunchKernelGGL(widen_kernel<false>, grid, dim3(threads), 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------
-template <int T, int NT>
-static void launch_fir_w8_nt(const FirArgs &a, const float *hrev, int S,
+// vec: float rows 16-B aligned, even stride (2 samples a load).  CS16 rows take
+// their own rule (launch_fir): 16-B aligned, stride a multiple of 4 samples and
+// T = 1 mod 4 (4 samples a load), which every specialised tap count meets.
+template <int T, int NT, typename XT>
+static void launch_fir_w8_nt(const typename fir_args<XT>::type &a, const float *hrev, int S,
                              int64_t n_max, bool vec, hipStream_t stream) {
     constexpr int Q = 8;
     const int64_t tiles = (n_max + NT * Q - 1) / (NT * Q);
     dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(S));
-    if (vec)
-        hipLaunchKernelGGL((fir_tile_kernel<T, 8, Q, true, NT>), grid, dim3(NT), 0, stream, a, hrev);
-    else
-        hipLaunchKernelGGL((fir_tile_kernel<T, 8, Q, false, NT>), grid, dim3(NT), 0, stream, a, hrev);
+    constexpr bool kVecOk = same_type<XT, f2>::value || (T - 1) % 4 == 0;
+    if constexpr (kVecOk) {
+        if (vec) {
+            hipLaunchKernelGGL((fir_tile_kernel<T, 8, Q, true, NT, XT>), grid, dim3(NT), 0, stream, a, hrev);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((fir_tile_kernel<T, 8, Q, false, NT, XT>), grid, dim3(NT), 0, stream, a, hrev);
 }
 
 template <int T>
-static bool launch_fir_w8(const FirArgs &a, const float *hrev, int S,
+static bool launch_fir_w8(const FirArgsCs16 &a, int32_t x_fmt, const float *hrev, int S,
                           int64_t n_max, bool vec, hipStream_t stream) {
     // 2048-output tiles; 1024- and 512-output tiles (128 / 64 threads, more
     // workgroups beside the loop kernel's) measured the same at C3 and C2
     // (pipelined bench, A/B x2 on one MI355X), and so did a
     // work-sharing tile whose waves take 512-output units from an LDS counter
     // (profiles/archive/r02_fir_share_ab.txt)
-    launch_fir_w8_nt<T, kFirThreads>(a, hrev, S, n_max, vec, stream);
+    if (x_fmt == kFmtCs16) launch_fir_w8_nt<T, kFirThreads, s2>(a, hrev, S, n_max, vec, stream);
+    else launch_fir_w8_nt<T, kFirThreads, f2>(static_cast<const FirArgs &>(a), hrev, S, n_max, vec, stream);
     return true;
 }
 
-bool launch_fir(const FirArgs &a, const float *hrev_dev, int T, int W, int S,
-                int64_t n_max, hipStream_t stream) {
+bool launch_fir(const FirArgs &a0, const float *hrev_dev, int T, int W, int S,
+                int64_t n_max, hipStream_t stream, int32_t x_fmt, float x_scale) {
     if (n_max <= 0 || S <= 0) return true;
-    const bool vec = (T % 2 == 1) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) &&
-                     (a.x_stride % 2 == 0) && ((reinterpret_cast<uintptr_t>(a.y) & 15) == 0) &&
-                     (a.y_stride % 2 == 0) && (a.y_offset % 2 == 0);
+    const bool cs16 = x_fmt == kFmtCs16;
+    FirArgsCs16 a{};
+    static_cast<FirArgs &>(a) = a0;
+    a.x_scale = x_scale;
+    const bool vec = cs16 ? (T % 4 == 1) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.x_stride % 4 == 0)
+                          : (T % 2 == 1) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) &&
+                                (a.x_stride % 2 == 0) && ((reinterpret_cast<uintptr_t>(a.y) & 15) == 0) &&
+                                (a.y_stride % 2 == 0) && (a.y_offset % 2 == 0);
     if (W == 8) {
         switch (T) {
-        case 13: return launch_fir_w8<13>(a, hrev_dev, S, n_max, vec, stream);
-        case 17: return launch_fir_w8<17>(a, hrev_dev, S, n_max, vec, stream);
-        case 21: return launch_fir_w8<21>(a, hrev_dev, S, n_max, vec, stream);
-        case 33: return launch_fir_w8<33>(a, hrev_dev, S, n_max, vec, stream);
-        case 41: return launch_fir_w8<41>(a, hrev_dev, S, n_max, vec, stream);
-        case 49: return launch_fir_w8<49>(a, hrev_dev, S, n_max, vec, stream);
-        case 65: return launch_fir_w8<65>(a, hrev_dev, S, n_max, vec, stream);
-        case 97: return launch_fir_w8<97>(a, hrev_dev, S, n_max, vec, stream);
-        case 129: return launch_fir_w8<129>(a, hrev_dev, S, n_max, vec, stream);
+        case 13: return launch_fir_w8<13>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
+        case 17: return launch_fir_w8<17>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
+        case 21: return launch_fir_w8<21>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
+        case 33: return launch_fir_w8<33>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
+        case 41: return launch_fir_w8<41>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
+        case 49: return launch_fir_w8<49>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
+        case 65: return launch_fir_w8<65>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
+        case 97: return launch_fir_w8<97>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
+        case 129: return launch_fir_w8<129>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
         default: break;
         }
     }
     const int threads = 256;
     dim3 grid(static_cast<unsigned>((n_max + threads - 1) / threads), static_cast<unsigned>(S));
-    hipLaunchKernelGGL(fir_generic_kernel, grid, dim3(threads), 0, stream, a, hrev_dev, T, W);
+    if (cs16) hipLaunchKernelGGL(fir_generic_kernel<s2>, grid, dim3(threads), 0, stream, a, hrev_dev, T, W);
+    else hipLaunchKernelGGL(fir_generic_kernel<f2>, grid, dim3(threads), 0, stream, a0, hrev_dev, T, W);
     return false;
 }
 
-void launch_fir_hist(const FirArgs &a, float *hist_new, int H, int S, hipStream_t stream) {
+void launch_fir_hist(const FirArgs &a, float *hist_new, int H, int S, hipStream_t stream, int32_t x_fmt,
+                     float x_scale) {
     if (H <= 0 || S <= 0) return;
     const int64_t total = static_cast<int64_t>(S) * H;
     const int threads = 256;
-    hipLaunchKernelGGL(fir_hist_kernel, dim3(static_cast<unsigned>((total + threads - 1) / threads)),
-                       dim3(threads), 0, stream, a, hist_new, H, S);
+    const dim3 grid(static_cast<unsigned>((total + threads - 1) / threads));
+    if (x_fmt == kFmtCs16) {
+        FirArgsCs16 c{};
+        static_cast<FirArgs &>(c) = a;
+        c.x_scale = x_scale;
+        hipLaunchKernelGGL(fir_hist_kernel<s2>, grid, dim3(threads), 0, stream, c, hist_new, H, S);
+    } else
+        hipLaunchKernelGGL(fir_hist_kernel<f2>, grid, dim3(threads), 0, stream, a, hist_new, H, S);
 }
 
 

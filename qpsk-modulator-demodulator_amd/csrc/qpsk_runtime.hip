@@ -19,7 +19,9 @@
 //
 // Device layout (HBM, stream-major so every stage reads/writes each stream's
 // time axis contiguously):
-//   in      [S][n_max]              float2  staging for host input
+//   in      [S][n_max]              float2  staging for host input (CS16 calls:
+//                                           int16 pairs, rows of n_max rounded up to
+//                                           4 samples so they take 16-B loads)
 //   fll_out [S][n_max]              float2  (FLL mode)
 //   hist    2 x [S][T-1]            float2  FIR delay line (ping-pong)
 //   mf      [2][S][256 + n_max]     float2  matched-filter output; the 256-slot
@@ -90,8 +92,8 @@ int set_last_error(int code, const std::string &msg) { return fail(code, msg); }
 namespace {
 struct Call {
     int32_t mode;
-    const float *iq;
-    int64_t stride_floats;
+    const void *iq;          // float rows, or int16 rows (fmt = kFmtCs16)
+    int64_t stride_floats;   // row stride in elements of iq: two per sample in either format
     int64_t n_samples;
     const int64_t *lengths;
     int32_t mem;
@@ -112,6 +114,20 @@ struct Call {
     int64_t dst_syms_stride = 0;
     int64_t *dst_n_bits = nullptr;   // device; written after the last chunk
     int64_t *dst_n_syms = nullptr;
+    // input format and, for CS16, the handle's scale when the call was issued
+    int32_t fmt = kFmtCf32;
+    float scale = 0.0f;
+};
+
+size_t elem_bytes(int32_t fmt) { return fmt == kFmtCs16 ? sizeof(int16_t) : sizeof(float); }
+
+// The first stage's input rows: the caller's (or the staged) rows in the
+// call's own format, until a pre-stage has rewritten them as float rows.
+struct InRows {
+    const void *x;
+    int64_t stride;   // samples
+    int32_t fmt;
+    float scale;
 };
 }  // namespace
 
@@ -131,7 +147,9 @@ struct qpsk_demod {
     int64_t bits_words = 0;      // per stream
     int64_t syms_cap = 0;        // per stream
     float *d_hrev = nullptr;
-    float *d_in = nullptr;
+    void *d_in = nullptr;            // host-input staging, in the call's format
+    size_t in_bytes = 0;
+    float cs16_scale = 1.0f / 32768; // (float)int16 * scale; SoapySDR's CS16 -> CF32 convention
     float *d_fll_out[2] = {nullptr, nullptr};
     float *d_iqb = nullptr;          // [S][n_max] float2, IQ_Balancer output (iq_balance only)
     float *d_hist[2] = {nullptr, nullptr};
@@ -266,7 +284,10 @@ int validate(qpsk_demod *h, Call &c) {
     if (c.syms && c.syms_stride_floats < 2 * max_sym)
         return fail(QPSK_ERR_ARGUMENT, "syms_stride_floats smaller than 2*max_symbols");
     if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && (c.stride_floats & 1))
-        return fail(QPSK_ERR_ARGUMENT, "device stride_floats must be even");
+        return fail(QPSK_ERR_ARGUMENT, c.fmt == kFmtCs16 ? "device stride_i16 must be even"
+                                                         : "device stride_floats must be even");
+    if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && c.fmt == kFmtCs16 && (reinterpret_cast<uintptr_t>(c.iq) & 3))
+        return fail(QPSK_ERR_ARGUMENT, "device CS16 rows must be 4-byte aligned");
     int rc;
     if (c.syms && !h->d_syms) {
         // on the handle's device whatever the calling thread's current one is
@@ -314,11 +335,29 @@ void run_fll(qpsk_demod *h, const float *x, int64_t x_stride, const int64_t *d_l
     launch_fll(fa, h->fp, st);
 }
 
+// CS16 rows ahead of a serial pre-stage (IQ balancer, FLL): widened into the
+// call's own MF rows, which nothing reads until the matched filter, the last
+// stage in front of the loop, has rewritten them (DESIGN.md, CS16 input).
+// Float rows pass through.
+const float *float_rows(qpsk_demod *h, InRows *in, const int64_t *d_len, int64_t n_call, float *mf,
+                        hipStream_t st) {
+    if (in->fmt == kFmtCs16) {
+        WidenArgs wa{};
+        wa.x = static_cast<const int16_t *>(in->x); wa.x_stride = in->stride;
+        wa.y = mf; wa.y_stride = h->mf_stride; wa.y_offset = kMfPrefix;
+        wa.lengths = d_len; wa.n = n_call;
+        wa.scale = in->scale;
+        launch_widen(wa, h->S, n_call, st);
+        *in = InRows{mf + 2 * kMfPrefix, h->mf_stride, kFmtCf32, 0.0f};
+    }
+    return static_cast<const float *>(in->x);
+}
+
 // matched filter (QPSKDeModulator.cs:360) + FIR delay-line carry
-int run_fir(qpsk_demod *h, const float *x, int64_t x_stride, const int64_t *d_len, int64_t n_call,
+int run_fir(qpsk_demod *h, const InRows &in, const int64_t *d_len, int64_t n_call,
             float *mf, hipStream_t st, unsigned long long *kt) {
     FirArgs fa{};
-    fa.x = x; fa.x_stride = x_stride;
+    fa.x = static_cast<const float *>(in.x); fa.x_stride = in.stride;
     fa.hist = h->d_hist[h->hist_cur];
     fa.lengths = d_len; fa.n = n_call;
     fa.y = mf; fa.y_stride = h->mf_stride; fa.y_offset = kMfPrefix;
@@ -329,11 +368,11 @@ int run_fir(qpsk_demod *h, const float *x, int64_t x_stride, const int64_t *d_le
         fa.cu_map = h->d_cu_map;
     }
     if (n_call > 0) {
-        launch_fir(fa, h->d_hrev, h->T, h->W, h->S, n_call, st);
+        launch_fir(fa, h->d_hrev, h->T, h->W, h->S, n_call, st, in.fmt, in.scale);
         fa.kt = nullptr;
         fa.clk = nullptr;
         fa.phases = nullptr;
-        launch_fir_hist(fa, h->d_hist[h->hist_cur ^ 1], h->T - 1, h->S, st);
+        launch_fir_hist(fa, h->d_hist[h->hist_cur ^ 1], h->T - 1, h->S, st, in.fmt, in.scale);
         h->hist_cur ^= 1;
     }
     return QPSK_OK;
@@ -931,7 +970,6 @@ namespace {
 int process_one(qpsk_demod *h, const Call &c) {
     int rc;
     const int32_t mem = c.mem;
-    const float *iq = c.iq;
     const int64_t stride_floats = c.stride_floats;
     const int64_t *lengths = c.lengths;
     const int S = h->S;
@@ -945,14 +983,26 @@ int process_one(qpsk_demod *h, const Call &c) {
     if (mem == QPSK_MEM_HOST && !c.append) HIP_TRY(hipMemsetAsync(h->d_flags + 1, 0, sizeof(uint32_t), st));
 
     // ---- input -----------------------------------------------------------
-    const float *x = iq;
-    int64_t x_stride = stride_floats / 2;   // float2 units
+    InRows in{c.iq, stride_floats / 2, c.fmt, c.scale};   // stride in samples
     if (n_call > 0 && mem == QPSK_MEM_HOST) {
-        if (!h->d_in && (rc = dev_alloc(&h->d_in, static_cast<size_t>(2 * S * h->n_max)))) return rc;
-        HIP_TRY(hipMemcpy2DAsync(h->d_in, 2 * h->n_max * sizeof(float), iq, stride_floats * sizeof(float),
-                                 2 * n_call * sizeof(float), S, hipMemcpyHostToDevice, st));
-        x = h->d_in;
-        x_stride = h->n_max;
+        // staged in the call's own format: a CS16 call uploads 4 bytes a sample
+        const size_t eb = elem_bytes(c.fmt);
+        const int64_t pitch = c.fmt == kFmtCs16 ? (h->n_max + 3) / 4 * 4 : h->n_max;   // samples
+        const size_t need = static_cast<size_t>(S) * pitch * 2 * eb;
+        if (need > h->in_bytes) {
+            // the last host-memory call has returned, so nothing reads d_in
+            hipFree(h->d_in);
+            h->d_in = nullptr;
+            h->in_bytes = 0;
+            char *p = nullptr;
+            if ((rc = dev_alloc(&p, need))) return rc;
+            h->d_in = p;
+            h->in_bytes = need;
+        }
+        HIP_TRY(hipMemcpy2DAsync(h->d_in, 2 * pitch * eb, c.iq, stride_floats * eb, 2 * n_call * eb, S,
+                                 hipMemcpyHostToDevice, st));
+        in.x = h->d_in;
+        in.stride = pitch;
     }
     const int64_t *d_len = nullptr;
     if (lengths) {
@@ -961,22 +1011,21 @@ int process_one(qpsk_demod *h, const Call &c) {
     }
 
     if (h->p.iq_balance && n_call > 0) {
-        run_iqb(h, x, x_stride, d_len, n_call, st);
-        x = h->d_iqb;
-        x_stride = h->n_max;
+        const float *x = float_rows(h, &in, d_len, n_call, h->d_mf[0], st);   // may rewrite in
+        run_iqb(h, x, in.stride, d_len, n_call, st);
+        in = InRows{h->d_iqb, h->n_max, kFmtCf32, 0.0f};
     }
     if (h->p.enable_fll && n_call > 0) {
-        run_fll(h, x, x_stride, d_len, n_call, h->d_fll_out[0], st, kt);
-        x = h->d_fll_out[0];
-        x_stride = h->n_max;
+        const float *x = float_rows(h, &in, d_len, n_call, h->d_mf[0], st);
+        run_fll(h, x, in.stride, d_len, n_call, h->d_fll_out[0], st, kt);
+        in = InRows{h->d_fll_out[0], h->n_max, kFmtCf32, 0.0f};
     }
-    if ((rc = run_fir(h, x, x_stride, d_len, n_call, h->d_mf[0], st, kt))) return rc;
+    if ((rc = run_fir(h, in, d_len, n_call, h->d_mf[0], st, kt))) return rc;
     return run_loop(h, c, d_len, h->d_mf[0], st, kt);
 }
 
 int process_async_one(qpsk_demod *h, const Call &c) {
     int rc;
-    const float *iq = c.iq;
     const int64_t stride_floats = c.stride_floats;
     const int64_t *lengths = c.lengths;
     HIP_TRY(hipSetDevice(h->p.device));
@@ -1003,15 +1052,16 @@ int process_async_one(qpsk_demod *h, const Call &c) {
         HIP_TRY(hipMemcpyAsync(h->d_lengths[b], h->h_len[b], S * sizeof(int64_t), hipMemcpyHostToDevice, F));
         d_len = h->d_lengths[b];
     }
-    const float *x = iq;
-    int64_t x_stride = stride_floats / 2;
+    InRows in{c.iq, stride_floats / 2, c.fmt, c.scale};
+    // MF rows b: the front stage waited above for the back stage that last read
+    // them, so a CS16 call's pre-stages may widen into them (float_rows)
+    float *mf = h->d_mf[b];
     if (h->p.iq_balance && n_call > 0) {
         // read only by this call's own front stage (FLL or FIR on F)
-        run_iqb(h, x, x_stride, d_len, n_call, F);
-        x = h->d_iqb;
-        x_stride = h->n_max;
+        const float *x = float_rows(h, &in, d_len, n_call, mf, F);   // may rewrite in
+        run_iqb(h, x, in.stride, d_len, n_call, F);
+        in = InRows{h->d_iqb, h->n_max, kFmtCf32, 0.0f};
     }
-    float *mf;
     if (h->p.enable_fll) {
         // FLL on (C5): the FLL keeps every SIMD's VALU busy with one wave each
         // (DESIGN.md 3.3), so a kernel beside it gains what it takes from it,
@@ -1023,7 +1073,11 @@ int process_async_one(qpsk_demod *h, const Call &c) {
         // a flush (pipeline_wait, a synchronous call, state access, destroy).
         // FLL(k) waited above for loop(k-2), the last reader of MF rows b, and
         // follows FIR(k-1) on F, so it runs alone.
-        if (n_call > 0) run_fll(h, x, x_stride, d_len, n_call, h->d_fll_out[0], F, kt);
+        if (n_call > 0) {
+            const float *x = float_rows(h, &in, d_len, n_call, mf, F);
+            run_fll(h, x, in.stride, d_len, n_call, h->d_fll_out[0], F, kt);
+            in = InRows{h->d_fll_out[0], h->n_max, kFmtCf32, 0.0f};
+        }
         HIP_TRY(hipEventRecord(h->e_fll, F));
         if (h->deferred) {
             Call dc = h->dcall;
@@ -1037,10 +1091,7 @@ int process_async_one(qpsk_demod *h, const Call &c) {
             h->last_back = db;
         }
         if ((rc = gate_wait(h, F))) return rc;
-        mf = h->d_mf[b];
-        if ((rc = run_fir(h, n_call > 0 ? h->d_fll_out[0] : x, n_call > 0 ? h->n_max : x_stride, d_len, n_call,
-                          mf, F, kt)))
-            return rc;
+        if ((rc = run_fir(h, in, d_len, n_call, mf, F, kt))) return rc;
         HIP_TRY(hipEventRecord(h->e_front[b], F));
         h->front_rec[b] = true;
         h->dcall = c;
@@ -1066,8 +1117,7 @@ int process_async_one(qpsk_demod *h, const Call &c) {
         // dispatch timing: the FIR cannot be dispatched before min(grid, CUs)
         // loop workgroups run, and every one of those was dispatched before it.
         if ((rc = gate_wait(h, F))) return rc;
-        mf = h->d_mf[b];
-        if ((rc = run_fir(h, x, x_stride, d_len, n_call, mf, F, kt))) return rc;
+        if ((rc = run_fir(h, in, d_len, n_call, mf, F, kt))) return rc;
         HIP_TRY(hipEventRecord(h->e_front[b], F));
         HIP_TRY(hipStreamWaitEvent(B, h->e_front[b], 0));
     }
@@ -1158,7 +1208,7 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
     for (int64_t k = 0; k < K; ++k) {
         const int64_t off = k * N;
         Call sub = c;
-        sub.iq = c.iq + 2 * off;
+        sub.iq = static_cast<const char *>(c.iq) + 2 * off * static_cast<int64_t>(elem_bytes(c.fmt));
         if (c.lengths) {
             int64_t m = 0;
             for (int s = 0; s < S; ++s) {
@@ -1252,6 +1302,51 @@ int qpsk_demod_process_async(qpsk_demod *h, int32_t mode, const float *iq, int64
                              int64_t syms_stride_floats, int64_t *n_syms) {
     Call c{mode, iq, stride_floats, n_samples, lengths, QPSK_MEM_DEVICE, bits, bits_stride_bytes,
            n_bits, syms, syms_stride_floats, n_syms};
+    int rc;
+    if ((rc = validate(h, c))) return rc;
+    if (c.n_call > h->n_max) return process_chunked(h, c, true);
+    return process_async_one(h, c);
+}
+
+int qpsk_demod_set_cs16_scale(qpsk_demod *h, float scale) {
+    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    if (!std::isfinite(scale) || !(scale > 0.0f))
+        return fail(QPSK_ERR_OUT_OF_RANGE, "the CS16 scale must be finite and > 0");
+    h->cs16_scale = scale;   // calls issued from now on; queued ones carry their own
+    return QPSK_OK;
+}
+
+int qpsk_demod_get_cs16_scale(const qpsk_demod *h, float *scale) {
+    if (!h || !scale) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    *scale = h->cs16_scale;
+    return QPSK_OK;
+}
+
+int qpsk_demod_process_cs16(qpsk_demod *h, int32_t mode, const int16_t *iq, int64_t stride_i16,
+                            int64_t n_samples, const int64_t *lengths, int32_t mem, uint8_t *bits,
+                            int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                            int64_t syms_stride_floats, int64_t *n_syms) {
+    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    Call c{mode, iq, stride_i16, n_samples, lengths, mem, bits, bits_stride_bytes, n_bits,
+           syms, syms_stride_floats, n_syms};
+    c.fmt = kFmtCs16;
+    c.scale = h->cs16_scale;
+    int rc;
+    if ((rc = validate(h, c))) return rc;
+    if (c.n_call > h->n_max) return process_chunked(h, c, false);
+    if ((rc = process_one(h, c))) return rc;
+    return c.mem == QPSK_MEM_HOST ? host_call_status(h) : QPSK_OK;
+}
+
+int qpsk_demod_process_async_cs16(qpsk_demod *h, int32_t mode, const int16_t *iq, int64_t stride_i16,
+                                  int64_t n_samples, const int64_t *lengths, uint8_t *bits,
+                                  int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                                  int64_t syms_stride_floats, int64_t *n_syms) {
+    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    Call c{mode, iq, stride_i16, n_samples, lengths, QPSK_MEM_DEVICE, bits, bits_stride_bytes,
+           n_bits, syms, syms_stride_floats, n_syms};
+    c.fmt = kFmtCs16;
+    c.scale = h->cs16_scale;
     int rc;
     if ((rc = validate(h, c))) return rc;
     if (c.n_call > h->n_max) return process_chunked(h, c, true);

@@ -17,6 +17,10 @@
 // last read ITS slot, so it runs on the copy engine while chunk k computes.
 // Everything the chain computes is done by the same kernels in the same call
 // order as synchronous qpsk_demod_process calls, hence identical bits.
+//
+// A CS16 ring (qpsk_rx_create_cs16) is the same ring with int16 slots: an SDR
+// driver's native CS16 buffers go up as they are, 4 bytes a sample, and the
+// matched filter widens them (qpsk_demod_process_async_cs16).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,8 +49,8 @@ int fail(int code, const std::string &msg) { return qpsk::set_last_error(code, m
     } while (0)
 
 struct Slot {
-    float *h_in = nullptr;      // pinned [S][in_stride]
-    float *d_in = nullptr;      // device, same layout
+    void *h_in = nullptr;       // pinned [S][in_stride] floats, or int16 (CS16 ring)
+    void *d_in = nullptr;       // device, same layout
     uint8_t *d_bits = nullptr;  // device [S][bits_stride]
     int64_t *d_nb = nullptr;    // device [S]
     uint8_t *h_bits = nullptr;  // pinned
@@ -62,7 +66,9 @@ struct qpsk_rx {
     int depth = 0;
     int S = 0;
     int64_t n_max = 0;
-    int64_t in_stride = 0;      // floats
+    int64_t in_stride = 0;      // elements (floats, or int16): 2 * n_max
+    bool cs16 = false;
+    size_t elem = sizeof(float);   // bytes per element of a slot
     int64_t bits_stride = 0;    // bytes
     int device = 0;
     hipStream_t up = nullptr, down = nullptr;
@@ -92,14 +98,14 @@ int setup(qpsk_rx *r) {
     RX_TRY(hipStreamCreateWithFlags(&r->up, hipStreamNonBlocking));
     RX_TRY(hipStreamCreateWithFlags(&r->down, hipStreamNonBlocking));
     const size_t S = static_cast<size_t>(r->S);
-    const size_t in_bytes = S * static_cast<size_t>(r->in_stride) * sizeof(float);
+    const size_t in_bytes = S * static_cast<size_t>(r->in_stride) * r->elem;
     const size_t bit_bytes = S * static_cast<size_t>(r->bits_stride);
     r->slots.resize(r->depth);
     for (auto &s : r->slots) {
-        RX_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_in), in_bytes));
+        RX_TRY(hipHostMalloc(&s.h_in, in_bytes));
         RX_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_bits), bit_bytes));
         RX_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_nb), S * sizeof(int64_t)));
-        RX_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_in), in_bytes));
+        RX_TRY(hipMalloc(&s.d_in, in_bytes));
         RX_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_bits), bit_bytes));
         RX_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_nb), S * sizeof(int64_t)));
         RX_TRY(hipEventCreateWithFlags(&s.in_free, hipEventDisableTiming));
@@ -107,11 +113,8 @@ int setup(qpsk_rx *r) {
     }
     return QPSK_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int qpsk_rx_create(qpsk_demod *h, int32_t depth, qpsk_rx **out) {
+int create(qpsk_demod *h, int32_t depth, bool cs16, qpsk_rx **out) {
     if (!h || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     *out = nullptr;
     if (depth < 2 || depth > 8) return fail(QPSK_ERR_ARGUMENT, "depth must be 2..8");
@@ -122,6 +125,8 @@ int qpsk_rx_create(qpsk_demod *h, int32_t depth, qpsk_rx **out) {
     r->n_max = qpsk::handle_max_samples(h);
     r->device = qpsk::handle_device(h);
     r->in_stride = 2 * r->n_max;
+    r->cs16 = cs16;
+    r->elem = cs16 ? sizeof(int16_t) : sizeof(float);
     r->bits_stride = ((2 * qpsk_demod_max_symbols(h, r->n_max) + 7) / 8 + 15) / 16 * 16;
     int rc = setup(r);
     if (rc == QPSK_OK) rc = qpsk_demod_set_stream(h, r->up);
@@ -133,19 +138,11 @@ int qpsk_rx_create(qpsk_demod *h, int32_t depth, qpsk_rx **out) {
     return QPSK_OK;
 }
 
-int qpsk_rx_destroy(qpsk_rx *r) {
-    if (!r) return fail(QPSK_ERR_ARGUMENT_NULL, "null ring");
-    hipSetDevice(r->device);
-    qpsk_demod_pipeline_wait(r->h, nullptr);
-    hipStreamSynchronize(r->up);
-    hipStreamSynchronize(r->down);
-    const int rc = qpsk_demod_set_stream(r->h, nullptr);
-    release(r);
-    return rc;
-}
+const char *kWrongFormat = "the ring was created for the other sample format (CF32 / CS16)";
 
-int qpsk_rx_next_slot(qpsk_rx *r, float **iq, int64_t *stride_floats) {
+int next_slot(qpsk_rx *r, bool cs16, void **iq, int64_t *stride_floats) {
     if (!r || !iq) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    if (r->cs16 != cs16) return fail(QPSK_ERR_STATE, kWrongFormat);
     if (r->submitted - r->collected >= r->depth)
         return fail(QPSK_ERR_STATE, "every ring slot holds an uncollected chunk");
     Slot &sl = r->slots[r->submitted % r->depth];
@@ -156,9 +153,10 @@ int qpsk_rx_next_slot(qpsk_rx *r, float **iq, int64_t *stride_floats) {
     return QPSK_OK;
 }
 
-int qpsk_rx_submit(qpsk_rx *r, const float *iq, int64_t stride_floats, int64_t n_samples,
-                   const int64_t *lengths, int64_t *ticket) {
+int submit(qpsk_rx *r, bool cs16, const void *iq, int64_t stride_floats, int64_t n_samples,
+           const int64_t *lengths, int64_t *ticket) {
     if (!r) return fail(QPSK_ERR_ARGUMENT_NULL, "null ring");
+    if (r->cs16 != cs16) return fail(QPSK_ERR_STATE, kWrongFormat);
     if (r->submitted - r->collected >= r->depth)
         return fail(QPSK_ERR_STATE, "every ring slot holds an uncollected chunk");
     const int S = r->S;
@@ -184,18 +182,23 @@ int qpsk_rx_submit(qpsk_rx *r, const float *iq, int64_t stride_floats, int64_t n
     if (n_call > 0 && iq != sl.h_in) {
         for (int s = 0; s < S; ++s) {
             const int64_t len = lengths ? lengths[s] : n_call;
-            std::memcpy(sl.h_in + static_cast<int64_t>(s) * r->in_stride, iq + static_cast<int64_t>(s) * stride_floats,
-                        static_cast<size_t>(2 * len) * sizeof(float));
+            std::memcpy(static_cast<char *>(sl.h_in) + static_cast<int64_t>(s) * r->in_stride * r->elem,
+                        static_cast<const char *>(iq) + static_cast<int64_t>(s) * stride_floats * r->elem,
+                        static_cast<size_t>(2 * len) * r->elem);
         }
     } else if (n_call > 0 && stride_floats != r->in_stride) {
-        return fail(QPSK_ERR_ARGUMENT, "a ring slot has stride_floats = 2 * max_samples_per_call");
+        return fail(QPSK_ERR_ARGUMENT, "a ring slot has a stride of 2 * max_samples_per_call elements");
     }
     if (sl.out_rec) RX_TRY(hipStreamWaitEvent(r->up, sl.out_done, 0));
     if (n_call > 0)
-        RX_TRY(hipMemcpy2DAsync(sl.d_in, r->in_stride * sizeof(float), sl.h_in, r->in_stride * sizeof(float),
-                                2 * n_call * sizeof(float), S, hipMemcpyHostToDevice, r->up));
-    int rc = qpsk_demod_process_async(r->h, QPSK_MODE_DEMODULATE, sl.d_in, r->in_stride, n_samples, lengths,
-                                      sl.d_bits, r->bits_stride, sl.d_nb, nullptr, 0, nullptr);
+        RX_TRY(hipMemcpy2DAsync(sl.d_in, r->in_stride * r->elem, sl.h_in, r->in_stride * r->elem,
+                                2 * n_call * r->elem, S, hipMemcpyHostToDevice, r->up));
+    int rc = cs16 ? qpsk_demod_process_async_cs16(r->h, QPSK_MODE_DEMODULATE, static_cast<const int16_t *>(sl.d_in),
+                                                  r->in_stride, n_samples, lengths, sl.d_bits, r->bits_stride,
+                                                  sl.d_nb, nullptr, 0, nullptr)
+                  : qpsk_demod_process_async(r->h, QPSK_MODE_DEMODULATE, static_cast<const float *>(sl.d_in),
+                                             r->in_stride, n_samples, lengths, sl.d_bits, r->bits_stride, sl.d_nb,
+                                             nullptr, 0, nullptr);
     if (rc != QPSK_OK) return rc;
     RX_TRY(hipEventRecord(sl.in_free, qpsk::pipe_front_stream(r->h)));
     sl.in_rec = true;
@@ -210,6 +213,40 @@ int qpsk_rx_submit(qpsk_rx *r, const float *iq, int64_t stride_floats, int64_t n
     if (ticket) *ticket = r->submitted;
     ++r->submitted;
     return QPSK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qpsk_rx_create(qpsk_demod *h, int32_t depth, qpsk_rx **out) { return create(h, depth, false, out); }
+int qpsk_rx_create_cs16(qpsk_demod *h, int32_t depth, qpsk_rx **out) { return create(h, depth, true, out); }
+
+int qpsk_rx_next_slot(qpsk_rx *r, float **iq, int64_t *stride_floats) {
+    return next_slot(r, false, reinterpret_cast<void **>(iq), stride_floats);
+}
+int qpsk_rx_next_slot_cs16(qpsk_rx *r, int16_t **iq, int64_t *stride_i16) {
+    return next_slot(r, true, reinterpret_cast<void **>(iq), stride_i16);
+}
+
+int qpsk_rx_submit(qpsk_rx *r, const float *iq, int64_t stride_floats, int64_t n_samples,
+                   const int64_t *lengths, int64_t *ticket) {
+    return submit(r, false, iq, stride_floats, n_samples, lengths, ticket);
+}
+int qpsk_rx_submit_cs16(qpsk_rx *r, const int16_t *iq, int64_t stride_i16, int64_t n_samples,
+                        const int64_t *lengths, int64_t *ticket) {
+    return submit(r, true, iq, stride_i16, n_samples, lengths, ticket);
+}
+
+int qpsk_rx_destroy(qpsk_rx *r) {
+    if (!r) return fail(QPSK_ERR_ARGUMENT_NULL, "null ring");
+    hipSetDevice(r->device);
+    qpsk_demod_pipeline_wait(r->h, nullptr);
+    hipStreamSynchronize(r->up);
+    hipStreamSynchronize(r->down);
+    const int rc = qpsk_demod_set_stream(r->h, nullptr);
+    release(r);
+    return rc;
 }
 
 int qpsk_rx_collect(qpsk_rx *r, uint8_t *bits, int64_t bits_stride_bytes, int64_t *n_bits,

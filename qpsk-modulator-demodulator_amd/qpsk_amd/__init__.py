@@ -164,6 +164,11 @@ def lib():
     L.qpsk_demod_process_async.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                            _i64p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.c_void_p]
+    # CS16 (int16 I,Q) input: the float entry points' arguments, int16 rows
+    L.qpsk_demod_process_cs16.argtypes = L.qpsk_demod_process.argtypes
+    L.qpsk_demod_process_async_cs16.argtypes = L.qpsk_demod_process_async.argtypes
+    L.qpsk_demod_set_cs16_scale.argtypes = [C.c_void_p, C.c_float]
+    L.qpsk_demod_get_cs16_scale.argtypes = [C.c_void_p, _f32p]
     L.qpsk_demod_pipeline_wait.argtypes = [C.c_void_p, C.c_void_p]
     L.qpsk_demod_status.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.qpsk_demod_last_mf.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]
@@ -228,6 +233,9 @@ def lib():
     L.qpsk_rx_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _i64p,
                                  C.POINTER(C.c_int64)]
     L.qpsk_rx_collect.argtypes = [C.c_void_p, _u8p, C.c_int64, _i64p, C.POINTER(C.c_int64)]
+    L.qpsk_rx_create_cs16.argtypes = L.qpsk_rx_create.argtypes
+    L.qpsk_rx_next_slot_cs16.argtypes = L.qpsk_rx_next_slot.argtypes
+    L.qpsk_rx_submit_cs16.argtypes = L.qpsk_rx_submit.argtypes
     L.qpsk_shard_streams.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32)]
     L.qpsk_demod_group_create.argtypes = [C.POINTER(DemodParams), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
@@ -269,6 +277,8 @@ EXPORTED_SYMBOLS = [
     "qpsk_shard_streams", "qpsk_demod_group_create", "qpsk_demod_group_destroy", "qpsk_demod_group_size",
     "qpsk_demod_group_shard", "qpsk_demod_group_process", "qpsk_demod_group_state_bytes",
     "qpsk_demod_group_get_state", "qpsk_demod_group_set_state",
+    "qpsk_demod_set_cs16_scale", "qpsk_demod_get_cs16_scale", "qpsk_demod_process_cs16",
+    "qpsk_demod_process_async_cs16", "qpsk_rx_create_cs16", "qpsk_rx_next_slot_cs16", "qpsk_rx_submit_cs16",
 ]
 
 _EXC = {
@@ -468,11 +478,62 @@ class BatchDemodulator:
         buf = C.create_string_buffer(bytes(blob), len(blob))
         _check(lib().qpsk_demod_set_state(self._h, buf, len(blob)))
 
+    # ---- CS16 (interleaved int16 I,Q) input -------------------------------
+    def set_cs16_scale(self, scale: float):
+        """A CS16 sample's value is float32(x) * scale (default 1 / 32768); applies
+        to calls issued from now on.  Finite and > 0, else ValueError."""
+        _check(lib().qpsk_demod_set_cs16_scale(self._h, C.c_float(float(np.float32(scale)))))
+
+    def cs16_scale(self) -> float:
+        v = C.c_float()
+        _check(lib().qpsk_demod_get_cs16_scale(self._h, C.byref(v)))
+        return float(v.value)
+
+    def process_cs16(self, iq: np.ndarray, mode=MODE_DEMODULATE, lengths=None, want_syms=False):
+        """process() on an [S, 2n] int16 host array (qpsk_demod_process_cs16); any
+        other dtype raises: nothing is converted on the way."""
+        if np.asarray(iq).dtype != np.int16:
+            raise ValueError("process_cs16 takes int16 samples")
+        return self._process_host(lib().qpsk_demod_process_cs16, np.ascontiguousarray(iq), mode, lengths,
+                                  want_syms)
+
+    def process_device_cs16(self, iq_dev, n, bits_dev, n_bits_dev, mode=MODE_DEMODULATE,
+                            syms_dev=None, n_syms_dev=None, lengths=None):
+        """process_device() on an int16 [S, >= 2n] torch CUDA tensor; lengths:
+        optional host int64 array of per-stream sample counts."""
+        self._device_call(lib().qpsk_demod_process_cs16, True, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev,
+                          n_syms_dev, lengths, False)
+
+    def process_device_async_cs16(self, iq_dev, n, bits_dev, n_bits_dev, mode=MODE_DEMODULATE,
+                                  syms_dev=None, n_syms_dev=None, lengths=None):
+        """process_device_async() on an int16 [S, >= 2n] torch CUDA tensor."""
+        self._device_call(lib().qpsk_demod_process_async_cs16, True, iq_dev, n, bits_dev, n_bits_dev, mode,
+                          syms_dev, n_syms_dev, lengths, True)
+
+    def _device_call(self, fn, cs16, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev, n_syms_dev, lengths,
+                     is_async):
+        self._check_device_args(iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev, cs16=cs16)
+        self._after_torch(iq_dev)
+        bstride = bits_dev.stride(0) * bits_dev.element_size() if bits_dev is not None else 0
+        sstride = syms_dev.stride(0) if syms_dev is not None else 0
+        if lengths is not None:
+            lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+        head = (self._h, int(mode), iq_dev.data_ptr(), iq_dev.stride(0), int(n),
+                lengths.ctypes.data_as(_i64p) if lengths is not None else None)
+        tail = (bits_dev.data_ptr() if bits_dev is not None else None, bstride,
+                n_bits_dev.data_ptr() if n_bits_dev is not None else None,
+                syms_dev.data_ptr() if syms_dev is not None else None, sstride,
+                n_syms_dev.data_ptr() if n_syms_dev is not None else None)
+        _check(fn(*head, *tail) if is_async else fn(*head, MEM_DEVICE, *tail))
+
     # ---- host path --------------------------------------------------------
     def process(self, iq: np.ndarray, mode=MODE_DEMODULATE, lengths=None, want_syms=False):
         """iq: [S, 2n] float32 host array.  Returns (bits [S, B] uint8, n_bits [S],
         syms [S, 2M] float32 or None, n_syms [S])."""
         iq = np.ascontiguousarray(iq, dtype=np.float32)
+        return self._process_host(lib().qpsk_demod_process, iq, mode, lengths, want_syms)
+
+    def _process_host(self, fn, iq, mode, lengths, want_syms):
         if iq.ndim != 2 or iq.shape[0] != self.S:
             raise ValueError("iq must be [n_streams, 2*n]")
         if iq.shape[1] & 1:
@@ -493,7 +554,7 @@ class BatchDemodulator:
         n_bits = np.zeros(self.S, dtype=np.int64)
         n_syms = np.zeros(self.S, dtype=np.int64)
         syms = np.zeros((self.S, 2 * ms), dtype=np.float32) if (want_syms or mode == MODE_CONSTELLATION) else None
-        _check(lib().qpsk_demod_process(
+        _check(fn(
             self._h, int(mode), iq.ctypes.data if iq.size else None, iq.shape[1], n,
             lengths.ctypes.data_as(_i64p) if lengths is not None else None, MEM_HOST,
             bits.ctypes.data if mode == MODE_DEMODULATE else None, bstride,
@@ -503,12 +564,13 @@ class BatchDemodulator:
         return bits, n_bits, syms, n_syms
 
     # ---- device path (torch tensors resident in HBM) ---------------------
-    def _check_device_args(self, iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev):
+    def _check_device_args(self, iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev, cs16=False):
         import torch
-        if iq_dev.dtype != torch.float32 or iq_dev.dim() != 2 or iq_dev.shape[0] != self.S:
-            raise ValueError("iq_dev must be a float32 [n_streams, >= 2n] tensor")
+        want = torch.int16 if cs16 else torch.float32
+        if iq_dev.dtype != want or iq_dev.dim() != 2 or iq_dev.shape[0] != self.S:
+            raise ValueError(f"iq_dev must be a {want} [n_streams, >= 2n] tensor")
         if iq_dev.stride(1) != 1 or iq_dev.shape[1] < 2 * int(n):
-            raise ValueError("iq_dev rows must be contiguous and hold 2n floats")
+            raise ValueError("iq_dev rows must be contiguous and hold 2n elements")
         for t, dt, what in ((bits_dev, torch.uint8, "bits_dev"), (syms_dev, torch.float32, "syms_dev")):
             if t is not None and (t.dtype != dt or t.dim() != 2 or t.shape[0] != self.S or t.stride(1) != 1):
                 raise ValueError(f"{what} must be a contiguous-row {dt} [n_streams, k] tensor")
@@ -671,37 +733,50 @@ class HostRing:
     on host samples, collect() returns the oldest outstanding call's bits.  The
     handle must not be used directly while the ring lives."""
 
-    def __init__(self, demod: "BatchDemodulator", depth: int = 2):
+    def __init__(self, demod: "BatchDemodulator", depth: int = 2, fmt: str = "cf32"):
+        """fmt "cf32": float32 slots; "cs16": int16 slots (qpsk_rx_*_cs16), half
+        the pinned memory and upload bytes, widened by the matched filter."""
+        if fmt not in ("cf32", "cs16"):
+            raise ValueError("fmt must be 'cf32' or 'cs16'")
         self._demod = demod
         self.S = demod.S
+        self.fmt = fmt
+        cs16 = fmt == "cs16"
+        self._dtype, self._ctype = (np.int16, C.c_int16) if cs16 else (np.float32, C.c_float)
+        L = lib()
+        self._next_slot = L.qpsk_rx_next_slot_cs16 if cs16 else L.qpsk_rx_next_slot
+        self._submit = L.qpsk_rx_submit_cs16 if cs16 else L.qpsk_rx_submit
         self._r = C.c_void_p()
-        _check(lib().qpsk_rx_create(demod._h, int(depth), C.byref(self._r)))
+        _check((L.qpsk_rx_create_cs16 if cs16 else L.qpsk_rx_create)(demod._h, int(depth), C.byref(self._r)))
         ms = demod.max_symbols(int(demod.p.max_samples_per_call))
         self.bits_stride = (2 * ms + 7) // 8
 
     def next_slot(self) -> np.ndarray:
-        """The pinned slot the next submit reads, as a writable (S, stride) float32 view."""
+        """The pinned slot the next submit reads, as a writable (S, stride) view
+        of the ring's sample type (float32, or int16 for a CS16 ring)."""
         ptr, stride = C.c_void_p(), C.c_int64()
-        _check(lib().qpsk_rx_next_slot(self._r, C.byref(ptr), C.byref(stride)))
-        buf = (C.c_float * (self.S * stride.value)).from_address(ptr.value)
+        _check(self._next_slot(self._r, C.byref(ptr), C.byref(stride)))
+        buf = (self._ctype * (self.S * stride.value)).from_address(ptr.value)
         return np.ctypeslib.as_array(buf).reshape(self.S, stride.value)
 
     def submit(self, iq: np.ndarray | None = None, n: int | None = None, lengths=None) -> int:
-        """iq None: the slot from next_slot() (filled in place); else (S, >= 2n) float32 rows."""
+        """iq None: the slot from next_slot() (filled in place); else (S, >= 2n)
+        rows of the ring's sample type (a CS16 ring takes int16 only)."""
         if iq is None:
             slot = self.next_slot()
             ptr, stride = slot.ctypes.data, slot.shape[1]
         else:
-            iq = np.ascontiguousarray(iq, dtype=np.float32)
+            if self.fmt == "cs16" and np.asarray(iq).dtype != np.int16:
+                raise ValueError("a CS16 ring takes int16 samples")
+            iq = np.ascontiguousarray(iq, dtype=self._dtype)
             assert iq.shape[0] == self.S
             ptr, stride = iq.ctypes.data, iq.shape[1]
         if n is None:
             n = stride // 2
         lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
         t = C.c_int64()
-        _check(lib().qpsk_rx_submit(self._r, C.c_void_p(ptr), int(stride), int(n),
-                                    lens.ctypes.data_as(_i64p) if lens is not None else None,
-                                    C.byref(t)))
+        _check(self._submit(self._r, C.c_void_p(ptr), int(stride), int(n),
+                            lens.ctypes.data_as(_i64p) if lens is not None else None, C.byref(t)))
         return t.value
 
     def collect(self):
