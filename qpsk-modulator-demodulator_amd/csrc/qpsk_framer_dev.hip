@@ -30,10 +30,7 @@
 #include <vector>
 
 #include "qpsk_demod.h"
-
-namespace qpsk {
-int set_last_error(int code, const std::string &msg);
-}
+#include "qpsk_internal.h"
 
 namespace {
 
@@ -433,14 +430,7 @@ tsc_find_kernel(const uint8_t *bits, int64_t stride, const int64_t *n_bits, TscP
     if (threadIdx.x == 0) offsets[s] = best == ULLONG_MAX ? -1 : static_cast<int64_t>(best) + m;
 }
 
-int fail(int code, const std::string &msg) { return qpsk::set_last_error(code, msg); }
-
-#define FR_TRY(expr)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return fail(QPSK_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+using qpsk::fail;
 
 }  // namespace
 
@@ -478,25 +468,25 @@ int load_markers(qpsk_framer_dev *f, const uint8_t *start, int32_t ns, const uin
     if (!start || !end) return fail(QPSK_ERR_ARGUMENT_NULL, "marker is null");
     if (ns <= 0) return fail(QPSK_ERR_ARGUMENT, "startMarker cannot be empty.");   // :174
     if (ne <= 0) return fail(QPSK_ERR_ARGUMENT, "endMarker cannot be empty.");     // :175
-    FR_TRY(hipSetDevice(f->device));
-    if (f->stream) FR_TRY(hipStreamSynchronize(f->stream));
+    QPSK_HIP_TRY(hipSetDevice(f->device));
+    if (f->stream) QPSK_HIP_TRY(hipStreamSynchronize(f->stream));
     if (static_cast<int64_t>(ns) + ne > f->markers_cap) {
         hipFree(f->markers);
         f->markers = nullptr;
         f->markers_cap = static_cast<int64_t>(ns) + ne;
-        FR_TRY(hipMalloc(reinterpret_cast<void **>(&f->markers), f->markers_cap));
+        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&f->markers), f->markers_cap));
     }
     std::vector<uint8_t> m(start, start + ns);
     m.insert(m.end(), end, end + ne);
-    FR_TRY(hipMemcpy(f->markers, m.data(), m.size(), hipMemcpyHostToDevice));
+    QPSK_HIP_TRY(hipMemcpy(f->markers, m.data(), m.size(), hipMemcpyHostToDevice));
     const int64_t need = ((static_cast<int64_t>(ns) + 1 + 15) / 16) * 16;
     if (need > f->carry_stride) {
         uint8_t *c = nullptr;
-        FR_TRY(hipMalloc(reinterpret_cast<void **>(&c), need * f->n_streams));
-        FR_TRY(hipMemset(c, 0, need * f->n_streams));
+        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c), need * f->n_streams));
+        QPSK_HIP_TRY(hipMemset(c, 0, need * f->n_streams));
         if (f->carry)
-            FR_TRY(hipMemcpy2D(c, need, f->carry, f->carry_stride, f->carry_stride, f->n_streams,
-                               hipMemcpyDeviceToDevice));
+            QPSK_HIP_TRY(hipMemcpy2D(c, need, f->carry, f->carry_stride, f->carry_stride, f->n_streams,
+                                     hipMemcpyDeviceToDevice));
         hipFree(f->carry);
         f->carry = c;
         f->carry_stride = need;
@@ -549,14 +539,14 @@ int qpsk_framer_dev_destroy(qpsk_framer_dev *f) {
 
 int qpsk_framer_dev_set_stream(qpsk_framer_dev *f, void *hip_stream) {
     if (!f) return fail(QPSK_ERR_ARGUMENT_NULL, "null framer");
-    FR_TRY(hipSetDevice(f->device));
-    FR_TRY(hipStreamSynchronize(f->stream));
+    QPSK_HIP_TRY(hipSetDevice(f->device));
+    QPSK_HIP_TRY(hipStreamSynchronize(f->stream));
     if (hip_stream) {
         if (f->own_stream) hipStreamDestroy(f->stream);
         f->stream = static_cast<hipStream_t>(hip_stream);
         f->own_stream = false;
     } else if (!f->own_stream) {
-        FR_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+        QPSK_HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
         f->own_stream = true;
     }
     return QPSK_OK;
@@ -573,15 +563,15 @@ int qpsk_framer_dev_push(qpsk_framer_dev *f, const uint8_t *bits, int64_t bits_s
                          int64_t payload_stride, int64_t *n_payload) {
     if (!f || !bits || !n_bits || !n_payload) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     if (bits_stride_bytes <= 0 || payload_stride < 0) return fail(QPSK_ERR_ARGUMENT, "bad stride");
-    FR_TRY(hipSetDevice(f->device));
+    QPSK_HIP_TRY(hipSetDevice(f->device));
     // candidate row: carry (<= carry_stride bytes) + one row of bits, 8 B slack
     const int64_t need = ((f->carry_stride + bits_stride_bytes + 8 + 15) / 16) * 16;
     if (need > f->scr_stride) {
-        FR_TRY(hipStreamSynchronize(f->stream));
+        QPSK_HIP_TRY(hipStreamSynchronize(f->stream));
         hipFree(f->scratch);
         f->scratch = nullptr;
         f->scr_stride = 0;
-        FR_TRY(hipMalloc(reinterpret_cast<void **>(&f->scratch), need * f->n_streams));
+        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&f->scratch), need * f->n_streams));
         f->scr_stride = need;
     }
     FrArgs a;
@@ -604,17 +594,17 @@ int qpsk_framer_dev_push(qpsk_framer_dev *f, const uint8_t *bits, int64_t bits_s
     a.end = f->markers + f->ns;
     a.ne = f->ne;
     hipLaunchKernelGGL(framer_push_kernel, dim3(f->n_streams), dim3(kFrThreads), 0, f->stream, a);
-    FR_TRY(hipGetLastError());
+    QPSK_HIP_TRY(hipGetLastError());
     return QPSK_OK;
 }
 
 int qpsk_framer_dev_status(const qpsk_framer_dev *f, int32_t *in_frame, int64_t *ring_count,
                            int64_t *carry_bits) {
     if (!f) return fail(QPSK_ERR_ARGUMENT_NULL, "null framer");
-    FR_TRY(hipSetDevice(f->device));
-    FR_TRY(hipStreamSynchronize(f->stream));
+    QPSK_HIP_TRY(hipSetDevice(f->device));
+    QPSK_HIP_TRY(hipStreamSynchronize(f->stream));
     std::vector<FrState> h(f->n_streams);
-    FR_TRY(hipMemcpy(h.data(), f->st, sizeof(FrState) * f->n_streams, hipMemcpyDeviceToHost));
+    QPSK_HIP_TRY(hipMemcpy(h.data(), f->st, sizeof(FrState) * f->n_streams, hipMemcpyDeviceToHost));
     for (int32_t s = 0; s < f->n_streams; ++s) {
         if (in_frame) in_frame[s] = h[s].in_frame;
         if (ring_count) ring_count[s] = h[s].count;
@@ -636,11 +626,11 @@ int qpsk_tsc_find_device(const uint8_t *bits, int64_t bits_stride_bytes, const i
         if (tsc[i] != '0' && tsc[i] != '1') binary = false;
     }
     if (blank) {                                             // no TSC: payload = every bit
-        FR_TRY(hipMemsetAsync(offsets, 0, sizeof(int64_t) * n_streams, stream));
+        QPSK_HIP_TRY(hipMemsetAsync(offsets, 0, sizeof(int64_t) * n_streams, stream));
         return QPSK_OK;
     }
     if (!binary || m > INT32_MAX) {                          // '0'/'1' rows never match other chars
-        FR_TRY(hipMemsetAsync(offsets, 0xff, sizeof(int64_t) * n_streams, stream));
+        QPSK_HIP_TRY(hipMemsetAsync(offsets, 0xff, sizeof(int64_t) * n_streams, stream));
         return QPSK_OK;
     }
     if (!bits) return fail(QPSK_ERR_ARGUMENT_NULL, "bits is null");
@@ -653,16 +643,16 @@ int qpsk_tsc_find_device(const uint8_t *bits, int64_t bits_stride_bytes, const i
     if (packed.size() <= sizeof(small.b)) {
         std::memcpy(small.b, packed.data(), packed.size());
     } else {                                                 // rare: stream-ordered buffer
-        FR_TRY(hipMallocAsync(reinterpret_cast<void **>(&big), packed.size(), stream));
-        FR_TRY(hipMemcpyAsync(big, packed.data(), packed.size(), hipMemcpyHostToDevice, stream));
+        QPSK_HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&big), packed.size(), stream));
+        QPSK_HIP_TRY(hipMemcpyAsync(big, packed.data(), packed.size(), hipMemcpyHostToDevice, stream));
     }
     hipLaunchKernelGGL(tsc_find_kernel, dim3(n_streams), dim3(kFrThreads), 0, stream, bits,
                        bits_stride_bytes, n_bits, small, static_cast<const uint8_t *>(big),
                        static_cast<int32_t>(m), offsets);
-    FR_TRY(hipGetLastError());
+    QPSK_HIP_TRY(hipGetLastError());
     if (big) {
-        FR_TRY(hipFreeAsync(big, stream));
-        FR_TRY(hipStreamSynchronize(stream));               // pageable source outlives the copy
+        QPSK_HIP_TRY(hipFreeAsync(big, stream));
+        QPSK_HIP_TRY(hipStreamSynchronize(stream));               // pageable source outlives the copy
     }
     return QPSK_OK;
 }

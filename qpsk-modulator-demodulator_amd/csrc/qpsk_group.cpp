@@ -26,15 +26,10 @@
 #include <vector>
 
 #include "qpsk_demod.h"
-
-namespace qpsk {
-int set_last_error(int code, const std::string &msg);
-int handle_sync(qpsk_demod *h);
-int handle_device(const qpsk_demod *h);
-}  // namespace qpsk
+#include "qpsk_internal.h"
 
 namespace {
-int fail(int code, const std::string &msg) { return qpsk::set_last_error(code, msg); }
+using qpsk::fail;
 
 struct Shard {
     int32_t first = 0, count = 0, device = 0;
@@ -206,30 +201,12 @@ int qpsk_demod_group_process(qpsk_demod_group *g, int32_t mode, const float *iq,
                              int64_t bits_stride_bytes, int64_t *n_bits, float *syms, int64_t syms_stride_floats,
                              int64_t *n_syms) {
     if (!g) return fail(QPSK_ERR_ARGUMENT_NULL, "null group");
-    if (mode != QPSK_MODE_DEMODULATE && mode != QPSK_MODE_CONSTELLATION) return fail(QPSK_ERR_ARGUMENT, "unknown mode");
-    if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
-    // the checks every shard would make, made once on the whole batch first, so
+    // the check every shard would make, made once on the whole batch first, so
     // a bad argument fails the call before any shard's state moves
-    int64_t n_call = 0;
-    if (lengths) {   // host memory in every call, as for qpsk_demod_process
-        for (int s = 0; s < g->S; ++s) {
-            if (lengths[s] < 0) return fail(QPSK_ERR_ARGUMENT, "negative length");
-            n_call = lengths[s] > n_call ? lengths[s] : n_call;
-        }
-    } else {
-        if (n_samples < 0) return fail(QPSK_ERR_ARGUMENT, "negative n_samples");
-        n_call = n_samples;
-    }
-    if (n_call > 0 && !iq) return fail(QPSK_ERR_ARGUMENT_NULL, "SamplesIQ is null");
-    if (n_call > 0 && stride_floats < 2 * n_call) return fail(QPSK_ERR_ARGUMENT, "stride too small");
-    if (mode == QPSK_MODE_DEMODULATE && (!bits || !n_bits)) return fail(QPSK_ERR_ARGUMENT_NULL, "bits / n_bits required");
-    if (mode == QPSK_MODE_CONSTELLATION && (!syms || !n_syms))
-        return fail(QPSK_ERR_ARGUMENT_NULL, "syms / n_syms required");
-    const int64_t max_sym = qpsk_demod_max_symbols(g->shards[0].h, n_call);
-    if (bits && bits_stride_bytes < (2 * max_sym + 7) / 8)
-        return fail(QPSK_ERR_ARGUMENT, "bits_stride_bytes smaller than 2*max_symbols/8");
-    if (syms && syms_stride_floats < 2 * max_sym)
-        return fail(QPSK_ERR_ARGUMENT, "syms_stride_floats smaller than 2*max_symbols");
+    qpsk::CallArgs c{mode, iq, stride_floats, n_samples, lengths, mem, bits, bits_stride_bytes, n_bits,
+                     syms, syms_stride_floats, n_syms};
+    int rc;
+    if ((rc = qpsk::check_call(g->shards[0].h, g->S, c))) return rc;
     if (mem == QPSK_MEM_DEVICE) {
         // one device pointer cannot address several GPUs' rows: device-memory
         // batches go to the shard handles (qpsk_demod_group_shard) directly

@@ -6,6 +6,8 @@
 
 #include "qpsk_state.h"
 
+struct qpsk_loop_shape;   // include/qpsk_demod.h
+
 namespace qpsk {
 
 constexpr int kModeDemodulate = 0;
@@ -181,17 +183,13 @@ void launch_fir_hist(const FirArgs &a, float *hist_new, int H, int S, hipStream_
                      int32_t x_fmt = kFmtCf32, float x_scale = 0.0f);
 void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream);
 // carry kernel + loop kernel; returns the loop kernel's workgroup count
-// cus = the device's CU count, taps = the matched filter's (0: unknown), for the automatic shape
+// variant = the requested qpsk_demod_params.loop_variant; cus = the device's CU
+// count, taps = the matched filter's (0: unknown), for the automatic shape
 int launch_loop(const LoopArgs &a, const LoopParams &P, int mode, int variant, hipStream_t stream, int cus = 0,
                 int taps = 0);
 // the geometry of the loop shape launch_loop runs for these arguments
 // (qpsk_demod_loop_shape)
-struct LoopShapeInfo {
-    int32_t streams, lanes, round, slots, prefix, cap, lds_bytes, fir_beside, fir_taps, fir_lds_bytes, lds_granule,
-        reserved;
-    double lag_max;
-};
-void loop_shape_info(int variant, int S, double sps, int cus, int taps, int trig, int syms, LoopShapeInfo *out);
+void loop_shape_info(int variant, int S, double sps, int cus, int taps, int trig, int syms, qpsk_loop_shape *out);
 void launch_append(const AppendArgs &a, hipStream_t stream);
 void launch_iq_balance(const IqbArgs &a, hipStream_t stream);
 void launch_fll(const FllArgs &a, const FllParams &P, hipStream_t stream);

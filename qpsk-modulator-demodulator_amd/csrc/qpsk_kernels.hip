@@ -8,10 +8,7 @@
 //   fir_generic_kernel same contract for tap counts / lane widths without a
 //                      specialised instantiation.
 //   fir_hist_kernel    carries the last T-1 input samples to the next call.
-//   loop_kernel        MuellerMuller.Process (MuellerMuller.cs:52-190) fused with
-//                      CostasLoopQpsk.Process (CostasLoopQpsk.cs:63-92), hard
-//                      decision, differential decode and MSB-first bit packing
-//                      (QPSKDeModulator.cs:372-408); one lane per stream.
+//   (the symbol loop, loop_kernel, is in qpsk_loop.hip)
 //   fll_kernel         FLLBandEdgeFilter.Process (Band-Edge Filter.cs:64-129),
 //                      one lane per stream (any Vector width); the 8-lane
 //                      systolic kernel is in qpsk_fll.hip.

@@ -38,6 +38,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "qpsk_demod.h"
 #include "qpsk_glibc_trig.h"
 #include "qpsk_kernels.h"
 #include "qpsk_sincos.h"
@@ -1173,6 +1174,37 @@ static auto with_shape(LoopShapeId id, F &&f) {
     }
 }
 
+}  // namespace qpsk
+
+// The automatic shape at sps >= 8, where the loop sets the step.  24 streams x
+// 128-sample rounds halve the per-round bookkeeping per symbol (C2 loop 23.9
+// -> 22.2-22.95 ms, A/B x3 on one MI355X) but take 147 KB of LDS, one
+// workgroup per CU; above one workgroup per CU (C5: 8192 streams = 342
+// workgroups) the 32 x 64 shape (256 workgroups) is the faster one (C5 serial
+// loop 24.0 vs 39.2 ms).  Above half the CUs, too: no FIR workgroup fits
+// beside a 147 KB one, and pipelined calls then wait for the FIR (4096
+// streams: 37.7 vs 33.4 ms a call; 2048: 24.6 vs 29.1 ms,
+// profiles/archive/r02_loop_shapes_c4_ab.txt).
+// Long rounds with shadow lanes (6 x 512, 12 x 256: 32 busy lanes, a quarter
+// / half of the per-round bookkeeping per symbol of 24 x 128) beat it wherever
+// they fit the chip in one pass, A/B on one MI355X
+// (profiles/r04_loop_long_rounds_ab.txt): 256 streams 13.6 -> 14.4 GSa/s (C2),
+// 1024: 48.5 / 51.2 / 54.5 (24 x 128 / 12 x 256 / 6 x 512), 2048: 88.4 / 99.3
+// (32 x 64: 74.6).  Above 12 x 256's one pass (4096 streams, C4) the 32 x 64
+// default stays: more workgroups than CUs, and half-empty waves cost the FIR
+// beside them issue slots.  So 24 x 128 (variant 4) is run on request only.
+extern "C" int32_t qpsk_demod_pick_loop_variant(int32_t requested, int32_t n_streams, double sps, int32_t cus) {
+    if (requested != 0 || !(sps >= 8.0) || cus <= 0 || n_streams <= 0) return requested;
+    const int64_t S = n_streams;
+    if ((S + 5) / 6 <= cus) return 7;
+    if ((S + 11) / 12 <= cus) return 6;
+    return 0;
+}
+
+namespace qpsk {
+
+// The one rule from a requested loop_variant to the shape that runs; the
+// launcher, qpsk_demod_loop_shape and the header's description all mean this.
 // The loop is latency-bound per stream; a wave's lanes are free, so the
 // default (sps >= 2) is 32 streams x 64-sample rounds.  Measured at C2
 // (profiles/archive/r01_loop_probe.txt): 16 x 64 and 16 x 128 (half the barriers)
@@ -1180,7 +1212,7 @@ static auto with_shape(LoopShapeId id, F &&f) {
 // which fits LDS at 16 streams x 64.  variant (qpsk_demod_params.loop_variant)
 // forces 1 = 16 x 64, 2 = 32 x 64, 3 = 16 x 128, 5 = 64 x 64 on the two-slot
 // ring (sps >= 4, portable trig); all compute identical results.  variant 0
-// (what qpsk_demod_pick_loop_variant leaves to the launcher) takes 64 x 64 at
+// (what qpsk_demod_pick_loop_variant leaves at 0) takes 64 x 64 at
 // 4 <= sps < 8 where the matched filter sets the step.  Every lane of its
 // stage waves is busy, so it holds half the CUs and issues half the
 // wave-instructions per stream, and the matched filter of the next pipelined
@@ -1192,6 +1224,7 @@ static auto with_shape(LoopShapeId id, F &&f) {
 // filter's time goes with streams x taps and the loop's does not, so the rule
 // is S x taps >= that of the measured win: 16 streams x 129 taps per CU.
 static LoopShapeId resolve_shape(int variant, int S, double sps, int cus, int taps, int trig) {
+    variant = qpsk_demod_pick_loop_variant(variant, S, sps, cus);
     if (sps < 2.0) return kSh16x64Any;
     if (variant == 1) return kSh16x64;
     if (variant == 3) return kSh16x128;
@@ -1224,7 +1257,7 @@ int launch_loop(const LoopArgs &a, const LoopParams &P, int mode, int variant, h
     });
 }
 
-void loop_shape_info(int variant, int S, double sps, int cus, int taps, int trig, int syms, LoopShapeInfo *o) {
+void loop_shape_info(int variant, int S, double sps, int cus, int taps, int trig, int syms, qpsk_loop_shape *o) {
     const LoopShapeId id = resolve_shape(variant, S, sps, cus, taps, trig);
     with_shape(id, [&](auto sh) {
         using T = decltype(sh);
@@ -1242,6 +1275,7 @@ void loop_shape_info(int variant, int S, double sps, int cus, int taps, int trig
         o->fir_taps = syms ? 0 : T::FIRT;
         o->fir_lds_bytes = syms || !T::FIRS ? 0 : fir_lds(T::FIRT);
         o->lds_granule = kLdsGranule;
+        o->reserved = 0;
         return 0;
     });
 }

@@ -26,10 +26,7 @@
 
 #include "qpsk_demod.h"
 #include "qpsk_design.h"
-
-namespace qpsk {
-int set_last_error(int code, const std::string &msg);
-}
+#include "qpsk_internal.h"
 
 struct qpsk_mod {
     qpsk_mod_params p{};
@@ -54,14 +51,7 @@ struct qpsk_mod {
 
 namespace {
 
-using qpsk::set_last_error;
-
-#define MOD_HIP_TRY(expr)                                                                      \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return set_last_error(QPSK_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+using qpsk::fail;
 
 constexpr float kInvSqrt2 = 0.7071067811865475f;   // QPSKModulator.cs:36
 
@@ -162,7 +152,7 @@ int grow(T **p, size_t *have, size_t need_bytes) {
     *p = nullptr;
     *have = 0;
     if (hipMalloc(reinterpret_cast<void **>(p), need_bytes) != hipSuccess)
-        return set_last_error(QPSK_ERR_DEVICE, "hipMalloc (modulator staging)");
+        return fail(QPSK_ERR_DEVICE, "hipMalloc (modulator staging)");
     *have = need_bytes;
     return QPSK_OK;
 }
@@ -196,15 +186,15 @@ void qpsk_mod_params_init(qpsk_mod_params *p, int32_t sample_rate, int32_t symbo
 }
 
 int qpsk_mod_create(const qpsk_mod_params *p, const char *tsc, qpsk_mod **out) {
-    if (!p || !out) return set_last_error(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    if (!p || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     *out = nullptr;
-    if (p->symbol_rate <= 0) return set_last_error(QPSK_ERR_OUT_OF_RANGE, "SymbolRate must be positive");
+    if (p->symbol_rate <= 0) return fail(QPSK_ERR_OUT_OF_RANGE, "SymbolRate must be positive");
     if (tsc && !blank(tsc))
         for (const char *c = tsc; *c; ++c)
-            if (*c != '0' && *c != '1') return set_last_error(QPSK_ERR_ARGUMENT, "tsc must be a '0'/'1' string");
+            if (*c != '0' && *c != '1') return fail(QPSK_ERR_ARGUMENT, "tsc must be a '0'/'1' string");
     std::vector<double> h = qpsk::rrc_coefficients(static_cast<double>(p->rrc_span), p->rrc_alpha,
                                                    p->sample_rate, p->symbol_rate);
-    if (h.empty()) return set_last_error(QPSK_ERR_ARGUMENT, "RRC design failed");
+    if (h.empty()) return fail(QPSK_ERR_ARGUMENT, "RRC design failed");
     auto *m = new qpsk_mod();
     m->p = *p;
     m->T = static_cast<int>(h.size());
@@ -222,7 +212,7 @@ int qpsk_mod_create(const qpsk_mod_params *p, const char *tsc, qpsk_mod **out) {
         hipMemcpy(m->d_taps, tf.data(), m->T * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(m->d_tsc, tb.data(), tb.size(), hipMemcpyHostToDevice) != hipSuccess) {
         qpsk_mod_destroy(m);
-        return set_last_error(QPSK_ERR_DEVICE, "modulator device set-up failed (no GPU?)");
+        return fail(QPSK_ERR_DEVICE, "modulator device set-up failed (no GPU?)");
     }
     m->own_stream = true;
     *out = m;
@@ -244,14 +234,14 @@ int qpsk_mod_destroy(qpsk_mod *m) {
 }
 
 int qpsk_mod_set_stream(qpsk_mod *m, void *hip_stream) {
-    if (!m) return set_last_error(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    MOD_HIP_TRY(hipStreamSynchronize(m->stream));
+    if (!m) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    QPSK_HIP_TRY(hipStreamSynchronize(m->stream));
     if (hip_stream) {
         if (m->own_stream) hipStreamDestroy(m->stream);
         m->stream = static_cast<hipStream_t>(hip_stream);
         m->own_stream = false;
     } else if (!m->own_stream) {
-        MOD_HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+        QPSK_HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
         m->own_stream = true;
     }
     return QPSK_OK;
@@ -265,25 +255,25 @@ int64_t qpsk_mod_output_floats(const qpsk_mod *m, int64_t n_bits, int32_t pulse_
 int qpsk_mod_modulate(qpsk_mod *m, int32_t n_streams, const uint8_t *bits, int64_t bits_stride_bytes,
                       const int64_t *n_bits, int32_t pulse_shaping, int32_t mem, float *out,
                       int64_t out_stride_floats, int64_t *n_out_floats) {
-    if (!m) return set_last_error(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    if (n_streams <= 0) return set_last_error(QPSK_ERR_ARGUMENT, "n_streams must be positive");
-    if (!n_bits || !out || !n_out_floats) return set_last_error(QPSK_ERR_ARGUMENT_NULL, "data is null");
-    if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return set_last_error(QPSK_ERR_ARGUMENT, "unknown mem");
+    if (!m) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    if (n_streams <= 0) return fail(QPSK_ERR_ARGUMENT, "n_streams must be positive");
+    if (!n_bits || !out || !n_out_floats) return fail(QPSK_ERR_ARGUMENT_NULL, "data is null");
+    if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
     const int S = n_streams;
     const bool host = mem == QPSK_MEM_HOST;
     std::vector<int64_t> nb(S);
     if (host) std::memcpy(nb.data(), n_bits, S * sizeof(int64_t));
-    else MOD_HIP_TRY(hipMemcpy(nb.data(), n_bits, S * sizeof(int64_t), hipMemcpyDeviceToHost));
+    else QPSK_HIP_TRY(hipMemcpy(nb.data(), n_bits, S * sizeof(int64_t), hipMemcpyDeviceToHost));
     int64_t nb_max = 0, tot_max = 0;
     for (int s = 0; s < S; ++s) {
-        if (nb[s] < 0) return set_last_error(QPSK_ERR_ARGUMENT, "negative bit count");
+        if (nb[s] < 0) return fail(QPSK_ERR_ARGUMENT, "negative bit count");
         nb_max = std::max(nb_max, nb[s]);
         tot_max = std::max(tot_max, out_complex(m, nb[s], pulse_shaping != 0));
     }
     if (nb_max > 0 && (!bits || bits_stride_bytes < (nb_max + 7) / 8))
-        return set_last_error(bits ? QPSK_ERR_ARGUMENT : QPSK_ERR_ARGUMENT_NULL, "bit rows too short");
-    if (out_stride_floats < 2 * tot_max) return set_last_error(QPSK_ERR_ARGUMENT, "out_stride_floats too small");
-    MOD_HIP_TRY(hipSetDevice(m->p.device));
+        return fail(bits ? QPSK_ERR_ARGUMENT : QPSK_ERR_ARGUMENT_NULL, "bit rows too short");
+    if (out_stride_floats < 2 * tot_max) return fail(QPSK_ERR_ARGUMENT, "out_stride_floats too small");
+    QPSK_HIP_TRY(hipSetDevice(m->p.device));
     hipStream_t st = m->stream;
     const int64_t nd_max = (static_cast<int64_t>(m->tsc.size()) + nb_max) / 2;
     int rc;
@@ -298,17 +288,17 @@ int qpsk_mod_modulate(qpsk_mod *m, int32_t n_streams, const uint8_t *bits, int64
         const size_t brow = static_cast<size_t>((nb_max + 7) / 8 + 1);
         if ((rc = grow(&m->d_bits, &m->bits_bytes, S * brow))) return rc;
         if (nb_max > 0)
-            MOD_HIP_TRY(hipMemcpy2DAsync(m->d_bits, brow, bits, bits_stride_bytes, (nb_max + 7) / 8, S,
-                                         hipMemcpyHostToDevice, st));
+            QPSK_HIP_TRY(hipMemcpy2DAsync(m->d_bits, brow, bits, bits_stride_bytes, (nb_max + 7) / 8, S,
+                                          hipMemcpyHostToDevice, st));
         if (S > m->nbits_cap) {
             hipFree(m->d_nbits);
             m->d_nbits = nullptr;
             m->nbits_cap = 0;
             if (hipMalloc(reinterpret_cast<void **>(&m->d_nbits), S * sizeof(int64_t)) != hipSuccess)
-                return set_last_error(QPSK_ERR_DEVICE, "hipMalloc");
+                return fail(QPSK_ERR_DEVICE, "hipMalloc");
             m->nbits_cap = S;
         }
-        MOD_HIP_TRY(hipMemcpyAsync(m->d_nbits, nb.data(), S * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        QPSK_HIP_TRY(hipMemcpyAsync(m->d_nbits, nb.data(), S * sizeof(int64_t), hipMemcpyHostToDevice, st));
         const size_t orow = static_cast<size_t>(2 * std::max<int64_t>(tot_max, 1));
         if ((rc = grow(&m->d_out, &m->out_bytes, S * orow * sizeof(float)))) return rc;
         a.bits = m->d_bits;
@@ -333,19 +323,19 @@ int qpsk_mod_modulate(qpsk_mod *m, int32_t n_streams, const uint8_t *bits, int64
         hipLaunchKernelGGL(mod_symbols_kernel, dim3((S + 63) / 64), dim3(64), 0, st, a);
         dim3 grid(static_cast<unsigned>((tot_max + 255) / 256), static_cast<unsigned>(S));
         hipLaunchKernelGGL(mod_samples_kernel, grid, dim3(256), 0, st, a);
-        MOD_HIP_TRY(hipGetLastError());
+        QPSK_HIP_TRY(hipGetLastError());
     }
     std::vector<int64_t> nout(S);
     for (int s = 0; s < S; ++s) nout[s] = 2 * out_complex(m, nb[s], pulse_shaping != 0);
     if (host) {
         if (tot_max > 0)
-            MOD_HIP_TRY(hipMemcpy2DAsync(out, out_stride_floats * sizeof(float), a.out, a.out_stride * sizeof(float),
-                                         2 * tot_max * sizeof(float), S, hipMemcpyDeviceToHost, st));
-        MOD_HIP_TRY(hipStreamSynchronize(st));
+            QPSK_HIP_TRY(hipMemcpy2DAsync(out, out_stride_floats * sizeof(float), a.out, a.out_stride * sizeof(float),
+                                          2 * tot_max * sizeof(float), S, hipMemcpyDeviceToHost, st));
+        QPSK_HIP_TRY(hipStreamSynchronize(st));
         std::memcpy(n_out_floats, nout.data(), S * sizeof(int64_t));
     } else {
-        MOD_HIP_TRY(hipMemcpyAsync(n_out_floats, nout.data(), S * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        MOD_HIP_TRY(hipStreamSynchronize(st));   // nout is a host temporary
+        QPSK_HIP_TRY(hipMemcpyAsync(n_out_floats, nout.data(), S * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        QPSK_HIP_TRY(hipStreamSynchronize(st));   // nout is a host temporary
     }
     return QPSK_OK;
 }
@@ -354,19 +344,19 @@ int qpsk_mod_modulate_bytes(qpsk_mod *m, int32_t n_streams, const uint8_t *paylo
                             const int64_t *n_payload, const uint8_t *start_marker, int32_t n_start,
                             const uint8_t *end_marker, int32_t n_end, int32_t pulse_shaping, float *out,
                             int64_t out_stride_floats, int64_t *n_out_floats) {
-    if (!m) return set_last_error(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    if (n_start <= 0 || !start_marker) return set_last_error(QPSK_ERR_ARGUMENT, "startMarker cannot be empty.");
-    if (n_end <= 0 || !end_marker) return set_last_error(QPSK_ERR_ARGUMENT, "endMarker cannot be empty.");
-    if (n_streams <= 0 || !n_payload) return set_last_error(QPSK_ERR_ARGUMENT_NULL, "payload is null");
+    if (!m) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    if (n_start <= 0 || !start_marker) return fail(QPSK_ERR_ARGUMENT, "startMarker cannot be empty.");
+    if (n_end <= 0 || !end_marker) return fail(QPSK_ERR_ARGUMENT, "endMarker cannot be empty.");
+    if (n_streams <= 0 || !n_payload) return fail(QPSK_ERR_ARGUMENT_NULL, "payload is null");
     // frame START + payload + END (QPSKModulator.cs:54-72), bits MSB-first
     // (BitPacker.BytesToBitString, HelperFunctions.cs:14-29)
     const int S = n_streams;
     int64_t pmax = 0;
     for (int s = 0; s < S; ++s) {
-        if (n_payload[s] < 0) return set_last_error(QPSK_ERR_ARGUMENT, "negative payload length");
+        if (n_payload[s] < 0) return fail(QPSK_ERR_ARGUMENT, "negative payload length");
         pmax = std::max(pmax, n_payload[s]);
     }
-    if (pmax > 0 && (!payload || payload_stride < pmax)) return set_last_error(QPSK_ERR_ARGUMENT, "payload rows too short");
+    if (pmax > 0 && (!payload || payload_stride < pmax)) return fail(QPSK_ERR_ARGUMENT, "payload rows too short");
     const int64_t row = n_start + pmax + n_end;
     std::vector<uint8_t> framed(static_cast<size_t>(S) * row);
     std::vector<int64_t> nb(S);

@@ -42,29 +42,26 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "qpsk_demod.h"
 #include "qpsk_design.h"
+#include "qpsk_internal.h"
 #include "qpsk_kernels.h"
 
 using namespace qpsk;
 
 namespace {
 thread_local std::string g_last_error;
+}  // namespace
 
-int fail(int code, const std::string &msg) {
+int qpsk::fail(int code, const std::string &msg) {
     g_last_error = msg;
     return code;
 }
 
-#define HIP_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return fail(QPSK_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
+namespace {
 template <typename T>
 int dev_alloc(T **p, size_t count) {
     *p = nullptr;
@@ -75,36 +72,22 @@ int dev_alloc(T **p, size_t count) {
     return QPSK_OK;
 }
 
-// launch-timestamp slots per timed call: FLL, FIR, loop kernel (start, end)
-// and one spare pair; qpsk_demod_enable_timing records the first kKtCalls calls
-constexpr int kKtPerCall = 12;   // spans: FLL 0-1, FIR 2-3, loop 4-5; clock sums: FIR 6-7, FLL 8-9, loop 10-11
+// launch-timestamp slots of one timed call, a pair per kernel: its (start, end)
+// span, then its clock sample (shader ticks, wall ticks); each list in the
+// order FLL, FIR, loop kernel.  qpsk_demod_enable_timing records the first
+// kKtCalls calls
+constexpr int kKtSpan[3] = {0, 2, 4};
+constexpr int kKtClk[3] = {8, 6, 10};
+constexpr int kKtFll = 0, kKtFir = 1, kKtLoop = 2;
+constexpr int kKtSpanSlots = 6;   // the slots below this hold spans
+constexpr int kKtPerCall = 12;
 constexpr int kKtCalls = 4096;
 constexpr int64_t kMaxSamplesPerCall = int64_t(1) << 30;
 // the symbol loop keeps sample indices of one call in 32-bit integers
 constexpr int64_t kMaxCallSamples = (int64_t(1) << 31) - 129;
-}  // namespace
+static_assert(kFmtCf32 == 0, "CallArgs.fmt defaults to CF32");
 
-namespace qpsk {
-// shared error channel for the other C-ABI translation units (framer, synth)
-int set_last_error(int code, const std::string &msg) { return fail(code, msg); }
-}  // namespace qpsk
-
-namespace {
-struct Call {
-    int32_t mode;
-    const void *iq;          // float rows, or int16 rows (fmt = kFmtCs16)
-    int64_t stride_floats;   // row stride in elements of iq: two per sample in either format
-    int64_t n_samples;
-    const int64_t *lengths;
-    int32_t mem;
-    uint8_t *bits;
-    int64_t bits_stride_bytes;
-    int64_t *n_bits;
-    float *syms;
-    int64_t syms_stride_floats;
-    int64_t *n_syms;
-    int64_t n_call = 0;    // derived by validate()
-    int64_t max_sym = 0;
+struct Call : CallArgs {
     // internal chunk of a longer call: outputs appended to dst_* at the running
     // offsets d_acc (first chunk: from 0), totals to n_bits / n_syms after the last
     bool append = false, first = false, last = false;
@@ -114,8 +97,7 @@ struct Call {
     int64_t dst_syms_stride = 0;
     int64_t *dst_n_bits = nullptr;   // device; written after the last chunk
     int64_t *dst_n_syms = nullptr;
-    // input format and, for CS16, the handle's scale when the call was issued
-    int32_t fmt = kFmtCf32;
+    // a CS16 call: the handle's scale when the call was issued
     float scale = 0.0f;
 };
 
@@ -234,7 +216,6 @@ hipStream_t pipe_front_stream(const qpsk_demod *h) { return h->s_front; }
 int handle_streams(const qpsk_demod *h) { return h->S; }
 int64_t handle_max_samples(const qpsk_demod *h) { return h->n_max; }
 int handle_device(const qpsk_demod *h) { return h->p.device; }
-int handle_sync(qpsk_demod *h);   // below: every queued call of the handle done
 }  // namespace qpsk
 
 namespace {
@@ -249,27 +230,66 @@ int flush_deferred(qpsk_demod *h);   // issues a deferred back stage (with the s
 int drain_async(qpsk_demod *h) {
     int rc;
     if ((rc = flush_deferred(h))) return rc;
-    if (hipEvent_t e = last_async(h)) HIP_TRY(hipEventSynchronize(e));
+    if (hipEvent_t e = last_async(h)) QPSK_HIP_TRY(hipEventSynchronize(e));
     return QPSK_OK;
 }
 
+// lazily, for the first call that asks for symbols
+int ensure_syms(qpsk_demod *h) {
+    if (h->d_syms) return QPSK_OK;
+    // on the handle's device whatever the calling thread's current one is
+    // (a group's worker threads, qpsk_group.cpp)
+    QPSK_HIP_TRY(hipSetDevice(h->p.device));
+    return dev_alloc(&h->d_syms, static_cast<size_t>(2 * h->S * h->syms_cap));
+}
 
-int validate(qpsk_demod *h, Call &c) {
-    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+// grow-on-demand scratch: *p holds at least need bytes afterwards (what it
+// held is dropped; nothing queued may still use it)
+template <typename T>
+int ensure_bytes(T **p, size_t *have, size_t need) {
+    if (need <= *have) return QPSK_OK;
+    hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    char *q = nullptr;
+    int rc;
+    if ((rc = dev_alloc(&q, need))) return rc;
+    *p = static_cast<T *>(static_cast<void *>(q));
+    *have = need;
+    return QPSK_OK;
+}
+
+}  // namespace
+
+int qpsk::handle_sync(qpsk_demod *h) {
+    int rc;
+    if ((rc = drain_async(h))) return rc;
+    QPSK_HIP_TRY(hipSetDevice(h->p.device));
+    QPSK_HIP_TRY(hipStreamSynchronize(h->stream));
+    return QPSK_OK;
+}
+
+int qpsk::call_length(int S, int64_t n_samples, const int64_t *lengths, int64_t *n_call) {
+    *n_call = 0;
+    if (lengths) {   // host memory in every call
+        for (int s = 0; s < S; ++s) {
+            if (lengths[s] < 0) return fail(QPSK_ERR_ARGUMENT, "negative length");
+            *n_call = std::max(*n_call, lengths[s]);
+        }
+    } else {
+        if (n_samples < 0) return fail(QPSK_ERR_ARGUMENT, "negative n_samples");
+        *n_call = n_samples;
+    }
+    return QPSK_OK;
+}
+
+int qpsk::check_call(const qpsk_demod *h, int S, CallArgs &c) {
     if (c.mode != QPSK_MODE_DEMODULATE && c.mode != QPSK_MODE_CONSTELLATION)
         return fail(QPSK_ERR_ARGUMENT, "unknown mode");
     if (c.mem != QPSK_MEM_HOST && c.mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
-    const int S = h->S;
+    int rc;
     int64_t n_call = 0;
-    if (c.lengths) {
-        for (int s = 0; s < S; ++s) {
-            if (c.lengths[s] < 0) return fail(QPSK_ERR_ARGUMENT, "negative length");
-            n_call = std::max(n_call, c.lengths[s]);
-        }
-    } else {
-        if (c.n_samples < 0) return fail(QPSK_ERR_ARGUMENT, "negative n_samples");
-        n_call = c.n_samples;
-    }
+    if ((rc = call_length(S, c.n_samples, c.lengths, &n_call))) return rc;
     if (n_call > kMaxCallSamples)
         return fail(QPSK_ERR_OUT_OF_RANGE, "calls above 2^31 - 129 samples per stream (a C# span holds 2^30)");
     if (n_call > 0 && !c.iq) return fail(QPSK_ERR_ARGUMENT_NULL, "SamplesIQ is null");
@@ -288,27 +308,18 @@ int validate(qpsk_demod *h, Call &c) {
                                                          : "device stride_floats must be even");
     if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && c.fmt == kFmtCs16 && (reinterpret_cast<uintptr_t>(c.iq) & 3))
         return fail(QPSK_ERR_ARGUMENT, "device CS16 rows must be 4-byte aligned");
-    int rc;
-    if (c.syms && !h->d_syms) {
-        // on the handle's device whatever the calling thread's current one is
-        // (a group's worker threads, qpsk_group.cpp)
-        HIP_TRY(hipSetDevice(h->p.device));
-        if ((rc = dev_alloc(&h->d_syms, static_cast<size_t>(2 * S * h->syms_cap)))) return rc;
-    }
     c.n_call = n_call;
     c.max_sym = max_sym;
     return QPSK_OK;
 }
+
+namespace {
 
 // the launch-timestamp slots of the next timed call, or nullptr
 unsigned long long *next_kt(qpsk_demod *h) {
     if (!h->timing || !h->d_kt || h->kt_used >= kKtCalls) return nullptr;
     return h->d_kt + static_cast<size_t>(kKtPerCall) * h->kt_used++;
 }
-
-}  // namespace (validation)
-
-namespace {
 
 // optional IQ_Balancer pre-stage (IQ Balancer.cs:15-25) into d_iqb
 void run_iqb(qpsk_demod *h, const float *x, int64_t x_stride, const int64_t *d_len, int64_t n_call,
@@ -330,8 +341,8 @@ void run_fll(qpsk_demod *h, const float *x, int64_t x_stride, const int64_t *d_l
     fa.delay = h->d_fll_delay;
     fa.lengths = d_len; fa.n = n_call;
     fa.state = h->d_state; fa.S = h->S;
-    fa.kt = kt ? kt + 0 : nullptr;
-    fa.clk = kt ? kt + 8 : nullptr;
+    fa.kt = kt ? kt + kKtSpan[kKtFll] : nullptr;
+    fa.clk = kt ? kt + kKtClk[kKtFll] : nullptr;
     launch_fll(fa, h->fp, st);
 }
 
@@ -353,6 +364,24 @@ const float *float_rows(qpsk_demod *h, InRows *in, const int64_t *d_len, int64_t
     return static_cast<const float *>(in->x);
 }
 
+// The serial stages in front of the matched filter, each on the rows the one
+// before it wrote: [CS16 widen ->] IQ balancer, [CS16 widen ->] FLL.  *in
+// becomes the rows the matched filter reads; mf = the call's own MF rows.
+void pre_stages(qpsk_demod *h, InRows *in, const int64_t *d_len, int64_t n_call, float *mf, hipStream_t st,
+                unsigned long long *kt) {
+    if (n_call <= 0) return;
+    if (h->p.iq_balance) {
+        const float *x = float_rows(h, in, d_len, n_call, mf, st);
+        run_iqb(h, x, in->stride, d_len, n_call, st);
+        *in = InRows{h->d_iqb, h->n_max, kFmtCf32, 0.0f};
+    }
+    if (h->p.enable_fll) {
+        const float *x = float_rows(h, in, d_len, n_call, mf, st);
+        run_fll(h, x, in->stride, d_len, n_call, h->d_fll_out[0], st, kt);
+        *in = InRows{h->d_fll_out[0], h->n_max, kFmtCf32, 0.0f};
+    }
+}
+
 // matched filter (QPSKDeModulator.cs:360) + FIR delay-line carry
 int run_fir(qpsk_demod *h, const InRows &in, const int64_t *d_len, int64_t n_call,
             float *mf, hipStream_t st, unsigned long long *kt) {
@@ -361,8 +390,8 @@ int run_fir(qpsk_demod *h, const InRows &in, const int64_t *d_len, int64_t n_cal
     fa.hist = h->d_hist[h->hist_cur];
     fa.lengths = d_len; fa.n = n_call;
     fa.y = mf; fa.y_stride = h->mf_stride; fa.y_offset = kMfPrefix;
-    fa.kt = kt ? kt + 2 : nullptr;
-    fa.clk = kt ? kt + 6 : nullptr;
+    fa.kt = kt ? kt + kKtSpan[kKtFir] : nullptr;
+    fa.clk = kt ? kt + kKtClk[kKtFir] : nullptr;
     if (h->fir_phases) {
         fa.phases = h->d_phases;
         fa.cu_map = h->d_cu_map;
@@ -382,10 +411,9 @@ int run_fir(qpsk_demod *h, const InRows &in, const int64_t *d_len, int64_t n_cal
 // the front stream, ahead of the FIR, polls the counter the loop kernel's
 // workgroups bump as they start (s_sleep between reads) and ends when it
 // reaches target -- or when cap wall-clock ticks have passed, counted in
-// *timeouts.  The FIR behind it in stream order is dispatched only then, as
-// with hipStreamWaitValue64, but a counter that never arrives (a dispatch
-// serialised by a tool the environment predicate does not know) costs one cap
-// per call instead of a hang.  The gate orders dispatch only; no result
+// *timeouts.  The FIR behind it in stream order is dispatched only then, and
+// a counter that never arrives (a dispatch serialised by a tool the
+// environment predicate does not know) costs one cap per call, not a hang.  The gate orders dispatch only; no result
 // depends on it.
 __global__ void gate_wait_kernel(const unsigned long long *resident, unsigned long long target,
                                  unsigned long long cap, unsigned *timeouts) {
@@ -405,7 +433,21 @@ int gate_wait(qpsk_demod *h, hipStream_t st) {
     h->gate_pending = false;
     hipLaunchKernelGGL(gate_wait_kernel, dim3(1), dim3(64), 0, st, h->d_resident,
                        static_cast<unsigned long long>(h->resident_gate), h->gate_cap_ticks, h->d_gate);
-    HIP_TRY(hipGetLastError());
+    QPSK_HIP_TRY(hipGetLastError());
+    return QPSK_OK;
+}
+
+// The end of a host-memory call: its counts (counts: device [2][S]) and the
+// flags it raised come back, the host waits for the stream, and the caller
+// gets the counts.
+int host_epilogue(qpsk_demod *h, const Call &c, const int64_t *counts, hipStream_t st) {
+    const int S = h->S;
+    QPSK_HIP_TRY(hipMemcpyAsync(h->h_counts, counts, 2 * S * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    QPSK_HIP_TRY(hipMemcpyAsync(h->h_flags, h->d_flags + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    QPSK_HIP_TRY(hipStreamSynchronize(st));
+    if (c.n_bits) std::memcpy(c.n_bits, h->h_counts, S * sizeof(int64_t));
+    if (c.n_syms) std::memcpy(c.n_syms, h->h_counts + S, S * sizeof(int64_t));
+    h->status_host |= *h->h_flags;
     return QPSK_OK;
 }
 
@@ -457,12 +499,12 @@ int run_loop(qpsk_demod *h, const Call &c, const int64_t *d_len, float *mf, hipS
     // slot 0, read by qpsk_demod_status
     la.flags = h->d_flags + (c.mem == QPSK_MEM_HOST ? 1 : 0);
     la.chunked = c.append ? 1 : 0;
-    la.kt = kt ? kt + 4 : nullptr;
-    la.clk = kt ? kt + 10 : nullptr;
+    la.kt = kt ? kt + kKtSpan[kKtLoop] : nullptr;
+    la.clk = kt ? kt + kKtClk[kKtLoop] : nullptr;
     la.cu_map = h->fir_phases ? h->d_cu_map : nullptr;
     la.resident = h->gate_publish ? resident : nullptr;
     const int grid = launch_loop(la, h->lp, c.mode, h->loop_variant, st, h->cus, h->T);
-    HIP_TRY(hipGetLastError());
+    QPSK_HIP_TRY(hipGetLastError());
     if (resident) {
         // the next FIR may start once min(grid, CUs) workgroups hold their CUs:
         // at most one 104-147 KB loop workgroup fits a CU, and those are the
@@ -488,34 +530,40 @@ int run_loop(qpsk_demod *h, const Call &c, const int64_t *d_len, float *mf, hipS
         aa.state = h->d_state;
         aa.S = S;
         launch_append(aa, st);
-        HIP_TRY(hipGetLastError());
+        QPSK_HIP_TRY(hipGetLastError());
         if (c.last) {
             if (c.dst_n_bits)
-                HIP_TRY(hipMemcpyAsync(c.dst_n_bits, h->d_acc, S * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+                QPSK_HIP_TRY(hipMemcpyAsync(c.dst_n_bits, h->d_acc, S * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
             if (c.dst_n_syms)
-                HIP_TRY(hipMemcpyAsync(c.dst_n_syms, h->d_acc + S, S * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+                QPSK_HIP_TRY(hipMemcpyAsync(c.dst_n_syms, h->d_acc + S, S * sizeof(int64_t), hipMemcpyDeviceToDevice,
+                                            st));
         }
         return QPSK_OK;
     }
     const hipMemcpyKind kind = c.mem == QPSK_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     const int64_t bytes_row = (2 * c.max_sym + 7) / 8;
     if (c.bits && bytes_row > 0 && !direct_bits)
-        HIP_TRY(hipMemcpy2DAsync(c.bits, c.bits_stride_bytes, h->d_bits, h->bits_words * 4, bytes_row, S, kind, st));
+        QPSK_HIP_TRY(hipMemcpy2DAsync(c.bits, c.bits_stride_bytes, h->d_bits, h->bits_words * 4, bytes_row, S, kind,
+                                      st));
     if (c.syms && c.max_sym > 0 && !direct_syms)
-        HIP_TRY(hipMemcpy2DAsync(c.syms, c.syms_stride_floats * sizeof(float), h->d_syms,
-                                 2 * h->syms_cap * sizeof(float), 2 * c.max_sym * sizeof(float), S, kind, st));
-    if (c.mem == QPSK_MEM_HOST) {
-        HIP_TRY(hipMemcpyAsync(h->h_counts, h->d_counts, 2 * S * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h->h_flags, h->d_flags + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c.n_bits) std::memcpy(c.n_bits, h->h_counts, S * sizeof(int64_t));
-        if (c.n_syms) std::memcpy(c.n_syms, h->h_counts + S, S * sizeof(int64_t));
-        h->status_host |= *h->h_flags;
-    } else {
-        if (c.n_bits && !direct_bits) HIP_TRY(hipMemcpyAsync(c.n_bits, h->d_counts, S * sizeof(int64_t), kind, st));
-        if (c.n_syms && !(direct_syms && la.n_syms == c.n_syms))
-            HIP_TRY(hipMemcpyAsync(c.n_syms, h->d_counts + S, S * sizeof(int64_t), kind, st));
-    }
+        QPSK_HIP_TRY(hipMemcpy2DAsync(c.syms, c.syms_stride_floats * sizeof(float), h->d_syms,
+                                      2 * h->syms_cap * sizeof(float), 2 * c.max_sym * sizeof(float), S, kind, st));
+    if (c.mem == QPSK_MEM_HOST) return host_epilogue(h, c, h->d_counts, st);
+    if (c.n_bits && !direct_bits) QPSK_HIP_TRY(hipMemcpyAsync(c.n_bits, h->d_counts, S * sizeof(int64_t), kind, st));
+    if (c.n_syms && !(direct_syms && la.n_syms == c.n_syms))
+        QPSK_HIP_TRY(hipMemcpyAsync(c.n_syms, h->d_counts + S, S * sizeof(int64_t), kind, st));
+    return QPSK_OK;
+}
+
+// A back stage on the back stream: the loop kernel on MF rows buf with its
+// output copies, then the event the next user of those rows waits for.
+int issue_back(qpsk_demod *h, const Call &c, const int64_t *d_len, int buf, unsigned long long *kt,
+               unsigned long long *resident) {
+    int rc;
+    if ((rc = run_loop(h, c, d_len, h->d_mf[buf], h->s_back, kt, resident))) return rc;
+    QPSK_HIP_TRY(hipEventRecord(h->e_back[buf], h->s_back));
+    h->back_rec[buf] = true;
+    h->last_back = buf;
     return QPSK_OK;
 }
 
@@ -532,25 +580,25 @@ int pipe_setup(qpsk_demod *h) {
     // next pipelined call and completes what is missing, leaking nothing and
     // keeping (not re-zeroing) the counters it already made
     int least = 0, greatest = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    if (!h->s_front) HIP_TRY(hipStreamCreateWithPriority(&h->s_front, hipStreamNonBlocking, least));
-    if (!h->s_back) HIP_TRY(hipStreamCreateWithPriority(&h->s_back, hipStreamNonBlocking, greatest));
-    if (!h->e_in) HIP_TRY(hipEventCreateWithFlags(&h->e_in, hipEventDisableTiming));
+    QPSK_HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    if (!h->s_front) QPSK_HIP_TRY(hipStreamCreateWithPriority(&h->s_front, hipStreamNonBlocking, least));
+    if (!h->s_back) QPSK_HIP_TRY(hipStreamCreateWithPriority(&h->s_back, hipStreamNonBlocking, greatest));
+    if (!h->e_in) QPSK_HIP_TRY(hipEventCreateWithFlags(&h->e_in, hipEventDisableTiming));
     for (int b = 0; b < 2; ++b) {
-        if (!h->e_front[b]) HIP_TRY(hipEventCreateWithFlags(&h->e_front[b], hipEventDisableTiming));
-        if (!h->e_back[b]) HIP_TRY(hipEventCreateWithFlags(&h->e_back[b], hipEventDisableTiming));
-        if (!h->h_len[b]) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_len[b]), h->S * sizeof(int64_t)));
+        if (!h->e_front[b]) QPSK_HIP_TRY(hipEventCreateWithFlags(&h->e_front[b], hipEventDisableTiming));
+        if (!h->e_back[b]) QPSK_HIP_TRY(hipEventCreateWithFlags(&h->e_back[b], hipEventDisableTiming));
+        if (!h->h_len[b]) QPSK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_len[b]), h->S * sizeof(int64_t)));
     }
-    if (!h->e_fll) HIP_TRY(hipEventCreateWithFlags(&h->e_fll, hipEventDisableTiming));
+    if (!h->e_fll) QPSK_HIP_TRY(hipEventCreateWithFlags(&h->e_fll, hipEventDisableTiming));
     if (!h->d_resident) {
-        HIP_TRY(hipExtMallocWithFlags(reinterpret_cast<void **>(&h->d_resident), sizeof(unsigned long long),
-                                      hipMallocSignalMemory));
-        HIP_TRY(hipMemset(h->d_resident, 0, sizeof(unsigned long long)));
+        QPSK_HIP_TRY(hipExtMallocWithFlags(reinterpret_cast<void **>(&h->d_resident), sizeof(unsigned long long),
+                                           hipMallocSignalMemory));
+        QPSK_HIP_TRY(hipMemset(h->d_resident, 0, sizeof(unsigned long long)));
     }
     int rc;
     if (!h->d_gate) {
         if ((rc = dev_alloc(&h->d_gate, 1))) return rc;
-        HIP_TRY(hipMemset(h->d_gate, 0, sizeof(unsigned)));
+        QPSK_HIP_TRY(hipMemset(h->d_gate, 0, sizeof(unsigned)));
     }
     if (!h->d_lengths[1] && (rc = dev_alloc(&h->d_lengths[1], h->S))) return rc;
     // the second boundary buffer: MF rows (the FIR of one call writes one while
@@ -564,7 +612,7 @@ int pipe_setup(qpsk_demod *h) {
             (void)hipGetLastError();
             h->d_mf[1] = nullptr;
         } else {
-            HIP_TRY(hipMemset(h->d_mf[1], 0, 2 * S * h->mf_stride * sizeof(float)));
+            QPSK_HIP_TRY(hipMemset(h->d_mf[1], 0, 2 * S * h->mf_stride * sizeof(float)));
         }
     }
     h->pipe_bufs = h->d_mf[1] ? 2 : 1;
@@ -618,26 +666,25 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
     // most 2^31 - 1 floats anyway)
     if (p->max_samples_per_call > kMaxSamplesPerCall)
         return fail(QPSK_ERR_OUT_OF_RANGE, "max_samples_per_call above 2^30");
-    auto *h = new qpsk_demod();
-    h->p = *p;
-    h->S = n_streams;
-    h->W = p->vector_lanes <= 1 ? 1 : p->vector_lanes;
-    if (h->W != 1 && h->W != 4 && h->W != 8 && h->W != 16) {
-        delete h;
-        return fail(QPSK_ERR_ARGUMENT, "vector_lanes must be 1, 4, 8 or 16");
-    }
-    if (p->loop_variant < 0 || p->loop_variant > 7) {
-        delete h;
-        return fail(QPSK_ERR_ARGUMENT, "loop_variant must be 0..7");
-    }
+    const int W = p->vector_lanes <= 1 ? 1 : p->vector_lanes;
+    if (W != 1 && W != 4 && W != 8 && W != 16) return fail(QPSK_ERR_ARGUMENT, "vector_lanes must be 1, 4, 8 or 16");
+    if (p->loop_variant < 0 || p->loop_variant > 7) return fail(QPSK_ERR_ARGUMENT, "loop_variant must be 0..7");
+    LoopDesign d;
     std::string err;
     int rc = design_loops(p->sample_rate, p->symbol_rate, p->rrc_alpha, p->rrc_span,
                           p->symbol_sync_bandwidth, p->costas_loop_bandwidth, p->cfo_loop_bandwidth,
-                          &h->d, &err);
-    if (rc != QPSK_OK) {
-        delete h;
-        return fail(rc, err);
-    }
+                          &d, &err);
+    if (rc != QPSK_OK) return fail(rc, err);
+    if (p->costas_trig != 0 && p->costas_trig != 1)
+        return fail(QPSK_ERR_ARGUMENT, "costas_trig must be 0 (portable) or 1 (glibc)");
+
+    // every knob is good: from here on a failure is the device's, and the one
+    // way out is cleanup_fail
+    auto *h = new qpsk_demod();
+    h->p = *p;
+    h->S = n_streams;
+    h->W = W;
+    h->d = std::move(d);
     h->T = static_cast<int>(h->d.rrc_f32.size());
     h->lp.sps = h->d.mm_sps;
     h->lp.kp = h->d.kp;
@@ -645,12 +692,8 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
     h->lp.c_alpha = h->d.costas_alpha;
     h->lp.c_beta = h->d.costas_beta;
     h->lp.differential = p->differential ? 1 : 0;
-    if (p->costas_trig != 0 && p->costas_trig != 1) {
-        delete h;
-        return fail(QPSK_ERR_ARGUMENT, "costas_trig must be 0 (portable) or 1 (glibc)");
-    }
     h->lp.costas_trig = p->costas_trig;
-    h->loop_variant = p->loop_variant;
+    h->loop_variant = p->loop_variant;   // as requested: the launcher resolves it (resolve_shape, qpsk_loop.hip)
     h->fp.beta = h->d.fll_beta;
     h->fp.alpha = h->d.fll_alpha;
     h->fp.max_freq = h->d.fll_max_freq;
@@ -679,28 +722,11 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
     };
     if (hipSetDevice(p->device) != hipSuccess)
         return cleanup_fail(fail(QPSK_ERR_DEVICE, "hipSetDevice failed (no GPU?)"));
-    // auto loop shape at sps >= 8: 24 streams x 128-sample rounds halve the
-    // per-round bookkeeping per symbol (C2 loop 23.9 -> 22.2-22.95 ms, A/B x3 on
-    // one MI355X) but take 147 KB of LDS, one workgroup per CU; above one
-    // workgroup per CU (C5: 8192 streams = 342 workgroups) the 32 x 64 shape
-    // (256 workgroups) is the faster one (C5 serial loop 24.0 vs 39.2 ms).
-    // Above half the CUs, too: no FIR workgroup fits beside a 147 KB one, and
-    // pipelined calls then wait for the FIR (4096 streams: 37.7 vs 33.4 ms a
-    // call; 2048: 24.6 vs 29.1 ms, profiles/archive/r02_loop_shapes_c4_ab.txt)
     if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess)
         h->cus = 0;
     if (hipDeviceGetAttribute(&h->wall_khz, hipDeviceAttributeWallClockRate, p->device) != hipSuccess ||
         h->wall_khz <= 0)
         h->wall_khz = 100000;
-    // Round 4: long rounds with shadow lanes (6 x 512, 12 x 256: 32 busy lanes,
-    // a quarter / half of the per-round bookkeeping per symbol of 24 x 128)
-    // beat it wherever they fit the chip in one pass, at sps >= 8, A/B on one
-    // MI355X (profiles/r04_loop_long_rounds_ab.txt): 256 streams 13.6 -> 14.4
-    // GSa/s (C2), 1024: 48.5 / 51.2 / 54.5 (24 x 128 / 12 x 256 / 6 x 512),
-    // 2048: 88.4 / 99.3 (32 x 64: 74.6).  Above 12 x 256's one pass (4096
-    // streams, C4) the 32 x 64 default stays: more workgroups than CUs, and
-    // half-empty waves cost the FIR beside them issue slots
-    h->loop_variant = qpsk_demod_pick_loop_variant(h->loop_variant, h->S, h->lp.sps, h->cus);
     h->use_gate = qpsk_pipeline_gate_enabled() == 1;
     {
         const char *v = std::getenv("QPSK_GATE_TIMEOUT_MS");
@@ -805,16 +831,14 @@ int qpsk_demod_destroy(qpsk_demod *h) {
 
 int qpsk_demod_set_stream(qpsk_demod *h, void *hip_stream) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    HIP_TRY(hipSetDevice(h->p.device));
     int rc;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = handle_sync(h))) return rc;
     if (hip_stream) {
         if (h->own_stream) hipStreamDestroy(h->stream);
         h->stream = static_cast<hipStream_t>(hip_stream);
         h->own_stream = false;
     } else if (!h->own_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        QPSK_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         h->own_stream = true;
     }
     return QPSK_OK;
@@ -825,27 +849,24 @@ int qpsk_demod_enable_timing(qpsk_demod *h, int32_t on) {
     h->kt_used = 0;
     h->timing = on != 0;
     if (!h->timing) return QPSK_OK;
-    HIP_TRY(hipSetDevice(h->p.device));
+    QPSK_HIP_TRY(hipSetDevice(h->p.device));
     int rc;
     const size_t n = static_cast<size_t>(kKtCalls) * kKtPerCall;
     if (!h->d_kt && (rc = dev_alloc(&h->d_kt, n))) return rc;
-    // (start, end) pairs of slots 0-5: start = +inf for the atomic minimum, end
-    // = 0 for the maximum; slots 6-11 (clock sums) = 0
+    // spans: start = +inf for the atomic minimum, end = 0 for the maximum;
+    // clock sums = 0
     std::vector<unsigned long long> init(n, 0ull);
     for (size_t i = 0; i < n; i += 2)
-        if (i % kKtPerCall < 6) init[i] = ~0ull;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(h->d_kt, init.data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        if (i % kKtPerCall < kKtSpanSlots) init[i] = ~0ull;
+    if ((rc = handle_sync(h))) return rc;
+    QPSK_HIP_TRY(hipMemcpy(h->d_kt, init.data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice));
     return QPSK_OK;
 }
 
 int qpsk_demod_enable_fir_phases(qpsk_demod *h, int32_t on) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     int rc;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipSetDevice(h->p.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = handle_sync(h))) return rc;
     if (on && (!h->d_phases || !h->d_cu_map)) {
         // both or neither: a half-allocated pair would let the sampled FIR
         // workgroups read a null cu_map
@@ -857,9 +878,9 @@ int qpsk_demod_enable_fir_phases(qpsk_demod *h, int32_t on) {
             h->d_cu_map = nullptr;
             return rc;
         }
-        HIP_TRY(hipMemset(h->d_cu_map, 0, kCuKeys * sizeof(unsigned)));
+        QPSK_HIP_TRY(hipMemset(h->d_cu_map, 0, kCuKeys * sizeof(unsigned)));
     }
-    if (on) HIP_TRY(hipMemset(h->d_phases, 0, kFirPhaseWords * sizeof(unsigned long long)));
+    if (on) QPSK_HIP_TRY(hipMemset(h->d_phases, 0, kFirPhaseWords * sizeof(unsigned long long)));
     h->fir_phases = on != 0;
     return QPSK_OK;
 }
@@ -872,12 +893,21 @@ int qpsk_demod_fir_phases(qpsk_demod *h, uint64_t *out, int32_t n) {
         return kFirPhaseWords;
     }
     int rc;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipSetDevice(h->p.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(out, h->d_phases, kFirPhaseWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(h->d_phases, 0, kFirPhaseWords * sizeof(unsigned long long)));
+    if ((rc = handle_sync(h))) return rc;
+    QPSK_HIP_TRY(hipMemcpy(out, h->d_phases, kFirPhaseWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    QPSK_HIP_TRY(hipMemset(h->d_phases, 0, kFirPhaseWords * sizeof(unsigned long long)));
     return kFirPhaseWords;
+}
+
+// the timestamp slots of the timed calls so far, once every one of them has run
+static int read_kt(qpsk_demod *h, std::vector<unsigned long long> *t) {
+    int rc;
+    if ((rc = handle_sync(h))) return rc;
+    if (h->s_front) QPSK_HIP_TRY(hipStreamSynchronize(h->s_front));
+    if (h->s_back) QPSK_HIP_TRY(hipStreamSynchronize(h->s_back));
+    t->resize(static_cast<size_t>(h->kt_used) * kKtPerCall);
+    QPSK_HIP_TRY(hipMemcpy(t->data(), h->d_kt, t->size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return QPSK_OK;
 }
 
 // per timed call: FLL, FIR and loop kernel durations and the call's kernel
@@ -886,19 +916,14 @@ static int read_launch_times(qpsk_demod *h, std::vector<float> *out) {
     out->assign(static_cast<size_t>(h->kt_used) * 4, 0.f);
     if (!h->kt_used) return QPSK_OK;
     int rc;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipSetDevice(h->p.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->s_front) HIP_TRY(hipStreamSynchronize(h->s_front));
-    if (h->s_back) HIP_TRY(hipStreamSynchronize(h->s_back));
-    std::vector<unsigned long long> t(static_cast<size_t>(h->kt_used) * kKtPerCall);
-    HIP_TRY(hipMemcpy(t.data(), h->d_kt, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> t;
+    if ((rc = read_kt(h, &t))) return rc;
     const double ms_per_tick = 1.0 / h->wall_khz;
     for (int c = 0; c < h->kt_used; ++c) {
         const unsigned long long *k = t.data() + static_cast<size_t>(kKtPerCall) * c;
         unsigned long long lo = ~0ull, hi = 0;
         for (int j = 0; j < 3; ++j) {
-            const unsigned long long s0 = k[2 * j], e0 = k[2 * j + 1];
+            const unsigned long long s0 = k[kKtSpan[j]], e0 = k[kKtSpan[j] + 1];
             if (s0 == ~0ull || e0 < s0) continue;   // did not run
             (*out)[4 * c + j] = static_cast<float>((e0 - s0) * ms_per_tick);
             lo = std::min(lo, s0);
@@ -932,20 +957,13 @@ int qpsk_demod_kernel_clocks(qpsk_demod *h, float *ghz, int32_t max_calls) {
     if (!h || !ghz) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     if (!h->kt_used) return 0;
     int rc;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipSetDevice(h->p.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->s_front) HIP_TRY(hipStreamSynchronize(h->s_front));
-    if (h->s_back) HIP_TRY(hipStreamSynchronize(h->s_back));
-    std::vector<unsigned long long> t(static_cast<size_t>(h->kt_used) * kKtPerCall);
-    HIP_TRY(hipMemcpy(t.data(), h->d_kt, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> t;
+    if ((rc = read_kt(h, &t))) return rc;
     const int k = std::min<int32_t>(max_calls, h->kt_used);
     for (int c = 0; c < k; ++c) {
         const unsigned long long *s = t.data() + static_cast<size_t>(kKtPerCall) * c;
-        // FLL (slots 8, 9), FIR (6, 7), loop kernel (10, 11)
-        const int slot[3] = {8, 6, 10};
         for (int j = 0; j < 3; ++j) {
-            const unsigned long long cy = s[slot[j]], wt = s[slot[j] + 1];
+            const unsigned long long cy = s[kKtClk[j]], wt = s[kKtClk[j] + 1];
             ghz[3 * c + j] = wt ? static_cast<float>(static_cast<double>(cy) / wt * h->wall_khz * 1e-6) : 0.f;
         }
     }
@@ -975,12 +993,12 @@ int process_one(qpsk_demod *h, const Call &c) {
     const int S = h->S;
     const int64_t n_call = c.n_call;
     hipStream_t st = h->stream;
-    HIP_TRY(hipSetDevice(h->p.device));
+    QPSK_HIP_TRY(hipSetDevice(h->p.device));
     // pipelined calls issued before this one finish first (they share the state)
     if ((rc = flush_deferred(h))) return rc;
-    if (hipEvent_t e = last_async(h)) HIP_TRY(hipStreamWaitEvent(st, e, 0));
+    if (hipEvent_t e = last_async(h)) QPSK_HIP_TRY(hipStreamWaitEvent(st, e, 0));
     unsigned long long *kt = next_kt(h);
-    if (mem == QPSK_MEM_HOST && !c.append) HIP_TRY(hipMemsetAsync(h->d_flags + 1, 0, sizeof(uint32_t), st));
+    if (mem == QPSK_MEM_HOST && !c.append) QPSK_HIP_TRY(hipMemsetAsync(h->d_flags + 1, 0, sizeof(uint32_t), st));
 
     // ---- input -----------------------------------------------------------
     InRows in{c.iq, stride_floats / 2, c.fmt, c.scale};   // stride in samples
@@ -988,38 +1006,20 @@ int process_one(qpsk_demod *h, const Call &c) {
         // staged in the call's own format: a CS16 call uploads 4 bytes a sample
         const size_t eb = elem_bytes(c.fmt);
         const int64_t pitch = c.fmt == kFmtCs16 ? (h->n_max + 3) / 4 * 4 : h->n_max;   // samples
-        const size_t need = static_cast<size_t>(S) * pitch * 2 * eb;
-        if (need > h->in_bytes) {
-            // the last host-memory call has returned, so nothing reads d_in
-            hipFree(h->d_in);
-            h->d_in = nullptr;
-            h->in_bytes = 0;
-            char *p = nullptr;
-            if ((rc = dev_alloc(&p, need))) return rc;
-            h->d_in = p;
-            h->in_bytes = need;
-        }
-        HIP_TRY(hipMemcpy2DAsync(h->d_in, 2 * pitch * eb, c.iq, stride_floats * eb, 2 * n_call * eb, S,
-                                 hipMemcpyHostToDevice, st));
+        // the last host-memory call has returned, so nothing reads d_in
+        if ((rc = ensure_bytes(&h->d_in, &h->in_bytes, static_cast<size_t>(S) * pitch * 2 * eb))) return rc;
+        QPSK_HIP_TRY(hipMemcpy2DAsync(h->d_in, 2 * pitch * eb, c.iq, stride_floats * eb, 2 * n_call * eb, S,
+                                      hipMemcpyHostToDevice, st));
         in.x = h->d_in;
         in.stride = pitch;
     }
     const int64_t *d_len = nullptr;
     if (lengths) {
-        HIP_TRY(hipMemcpyAsync(h->d_lengths[0], lengths, S * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        QPSK_HIP_TRY(hipMemcpyAsync(h->d_lengths[0], lengths, S * sizeof(int64_t), hipMemcpyHostToDevice, st));
         d_len = h->d_lengths[0];
     }
 
-    if (h->p.iq_balance && n_call > 0) {
-        const float *x = float_rows(h, &in, d_len, n_call, h->d_mf[0], st);   // may rewrite in
-        run_iqb(h, x, in.stride, d_len, n_call, st);
-        in = InRows{h->d_iqb, h->n_max, kFmtCf32, 0.0f};
-    }
-    if (h->p.enable_fll && n_call > 0) {
-        const float *x = float_rows(h, &in, d_len, n_call, h->d_mf[0], st);
-        run_fll(h, x, in.stride, d_len, n_call, h->d_fll_out[0], st, kt);
-        in = InRows{h->d_fll_out[0], h->n_max, kFmtCf32, 0.0f};
-    }
+    pre_stages(h, &in, d_len, n_call, h->d_mf[0], st, kt);
     if ((rc = run_fir(h, in, d_len, n_call, h->d_mf[0], st, kt))) return rc;
     return run_loop(h, c, d_len, h->d_mf[0], st, kt);
 }
@@ -1028,7 +1028,7 @@ int process_async_one(qpsk_demod *h, const Call &c) {
     int rc;
     const int64_t stride_floats = c.stride_floats;
     const int64_t *lengths = c.lengths;
-    HIP_TRY(hipSetDevice(h->p.device));
+    QPSK_HIP_TRY(hipSetDevice(h->p.device));
     if ((rc = pipe_setup(h))) return rc;
     const int S = h->S;
     const int64_t n_call = c.n_call;
@@ -1039,29 +1039,27 @@ int process_async_one(qpsk_demod *h, const Call &c) {
     // the front stage starts after the work already on the handle's stream
     // (the producer of iq, earlier synchronous calls) and after the back stage
     // that last used boundary buffer b
-    HIP_TRY(hipEventRecord(h->e_in, h->stream));
-    HIP_TRY(hipStreamWaitEvent(F, h->e_in, 0));
+    QPSK_HIP_TRY(hipEventRecord(h->e_in, h->stream));
+    QPSK_HIP_TRY(hipStreamWaitEvent(F, h->e_in, 0));
     const int prev = h->pipe_bufs == 2 ? b : h->last_back;
-    if (prev >= 0 && h->back_rec[prev]) HIP_TRY(hipStreamWaitEvent(F, h->e_back[prev], 0));
+    if (prev >= 0 && h->back_rec[prev]) QPSK_HIP_TRY(hipStreamWaitEvent(F, h->e_back[prev], 0));
     unsigned long long *kt = next_kt(h);
     const int64_t *d_len = nullptr;
     if (lengths) {
         // pinned staging row b is free once the front stage that last read it ran
-        if (h->front_rec[b]) HIP_TRY(hipEventSynchronize(h->e_front[b]));
+        if (h->front_rec[b]) QPSK_HIP_TRY(hipEventSynchronize(h->e_front[b]));
         std::memcpy(h->h_len[b], lengths, S * sizeof(int64_t));
-        HIP_TRY(hipMemcpyAsync(h->d_lengths[b], h->h_len[b], S * sizeof(int64_t), hipMemcpyHostToDevice, F));
+        QPSK_HIP_TRY(hipMemcpyAsync(h->d_lengths[b], h->h_len[b], S * sizeof(int64_t), hipMemcpyHostToDevice, F));
         d_len = h->d_lengths[b];
     }
     InRows in{c.iq, stride_floats / 2, c.fmt, c.scale};
     // MF rows b: the front stage waited above for the back stage that last read
-    // them, so a CS16 call's pre-stages may widen into them (float_rows)
+    // them, so a CS16 call's pre-stages may widen into them (float_rows).  The
+    // IQ balancer's rows are read only by this call's own front stage (FLL or
+    // FIR on F).
     float *mf = h->d_mf[b];
-    if (h->p.iq_balance && n_call > 0) {
-        // read only by this call's own front stage (FLL or FIR on F)
-        const float *x = float_rows(h, &in, d_len, n_call, mf, F);   // may rewrite in
-        run_iqb(h, x, in.stride, d_len, n_call, F);
-        in = InRows{h->d_iqb, h->n_max, kFmtCf32, 0.0f};
-    }
+    unsigned long long *resident = h->use_gate ? h->d_resident : nullptr;
+    pre_stages(h, &in, d_len, n_call, mf, F, kt);
     if (h->p.enable_fll) {
         // FLL on (C5): the FLL keeps every SIMD's VALU busy with one wave each
         // (DESIGN.md 3.3), so a kernel beside it gains what it takes from it,
@@ -1073,26 +1071,15 @@ int process_async_one(qpsk_demod *h, const Call &c) {
         // a flush (pipeline_wait, a synchronous call, state access, destroy).
         // FLL(k) waited above for loop(k-2), the last reader of MF rows b, and
         // follows FIR(k-1) on F, so it runs alone.
-        if (n_call > 0) {
-            const float *x = float_rows(h, &in, d_len, n_call, mf, F);
-            run_fll(h, x, in.stride, d_len, n_call, h->d_fll_out[0], F, kt);
-            in = InRows{h->d_fll_out[0], h->n_max, kFmtCf32, 0.0f};
-        }
-        HIP_TRY(hipEventRecord(h->e_fll, F));
+        QPSK_HIP_TRY(hipEventRecord(h->e_fll, F));
         if (h->deferred) {
-            Call dc = h->dcall;
-            HIP_TRY(hipStreamWaitEvent(B, h->e_fll, 0));
-            const int db = h->dbuf;
+            QPSK_HIP_TRY(hipStreamWaitEvent(B, h->e_fll, 0));
             h->deferred = false;
-            if ((rc = run_loop(h, dc, h->dlen, h->d_mf[db], B, h->dkt, h->use_gate ? h->d_resident : nullptr)))
-                return rc;
-            HIP_TRY(hipEventRecord(h->e_back[db], B));
-            h->back_rec[db] = true;
-            h->last_back = db;
+            if ((rc = issue_back(h, h->dcall, h->dlen, h->dbuf, h->dkt, resident))) return rc;
         }
         if ((rc = gate_wait(h, F))) return rc;
         if ((rc = run_fir(h, in, d_len, n_call, mf, F, kt))) return rc;
-        HIP_TRY(hipEventRecord(h->e_front[b], F));
+        QPSK_HIP_TRY(hipEventRecord(h->e_front[b], F));
         h->front_rec[b] = true;
         h->dcall = c;
         h->dbuf = b;
@@ -1112,36 +1099,26 @@ int process_async_one(qpsk_demod *h, const Call &c) {
         // tools/anyorder_probe.hip), and either order then repeats call after
         // call.  So FIR(k+1) waits, on the device, until loop(k)'s workgroups
         // hold their CUs: each adds 1 to the residency counter as it starts,
-        // and the front stream waits for the count (hipStreamWaitValue64 on
-        // signal memory, gate_wait: bounded).  The order no longer depends on
-        // dispatch timing: the FIR cannot be dispatched before min(grid, CUs)
-        // loop workgroups run, and every one of those was dispatched before it.
+        // and a wave on the front stream waits for the count (gate_wait_kernel,
+        // bounded by a timeout).  The order no longer depends on dispatch
+        // timing: the FIR cannot be dispatched before min(grid, CUs) loop
+        // workgroups run, and every one of those was dispatched before it.
         if ((rc = gate_wait(h, F))) return rc;
         if ((rc = run_fir(h, in, d_len, n_call, mf, F, kt))) return rc;
-        HIP_TRY(hipEventRecord(h->e_front[b], F));
-        HIP_TRY(hipStreamWaitEvent(B, h->e_front[b], 0));
+        QPSK_HIP_TRY(hipEventRecord(h->e_front[b], F));
+        QPSK_HIP_TRY(hipStreamWaitEvent(B, h->e_front[b], 0));
     }
     h->front_rec[b] = true;
-    if ((rc = run_loop(h, c, d_len, mf, B, kt, h->use_gate ? h->d_resident : nullptr))) return rc;
-    HIP_TRY(hipEventRecord(h->e_back[b], B));
-    h->back_rec[b] = true;
-    h->last_back = b;
-    return QPSK_OK;
+    return issue_back(h, c, d_len, b, kt, resident);
 }
 
 // The deferred back stage (FLL on) after its own FIR only: nothing follows it.
 int flush_deferred(qpsk_demod *h) {
     if (!h->deferred) return QPSK_OK;
-    HIP_TRY(hipSetDevice(h->p.device));
-    const int db = h->dbuf;
+    QPSK_HIP_TRY(hipSetDevice(h->p.device));
     h->deferred = false;
-    HIP_TRY(hipStreamWaitEvent(h->s_back, h->e_front[db], 0));
-    int rc;
-    if ((rc = run_loop(h, h->dcall, h->dlen, h->d_mf[db], h->s_back, h->dkt))) return rc;
-    HIP_TRY(hipEventRecord(h->e_back[db], h->s_back));
-    h->back_rec[db] = true;
-    h->last_back = db;
-    return QPSK_OK;
+    QPSK_HIP_TRY(hipStreamWaitEvent(h->s_back, h->e_front[h->dbuf], 0));
+    return issue_back(h, h->dcall, h->dlen, h->dbuf, h->dkt, nullptr);
 }
 
 // QPSK_STATUS_* raised by the host-memory call that just finished -> status
@@ -1165,43 +1142,27 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
     const int S = h->S;
     const int64_t N = h->n_max;
     int rc;
-    HIP_TRY(hipSetDevice(h->p.device));
+    QPSK_HIP_TRY(hipSetDevice(h->p.device));
     if (!h->d_acc && (rc = dev_alloc(&h->d_acc, 2 * static_cast<size_t>(S)))) return rc;
-    if (c.syms && !h->d_syms && (rc = dev_alloc(&h->d_syms, static_cast<size_t>(2 * S * h->syms_cap))))
-        return rc;
-    const bool host = c.mem == QPSK_MEM_HOST;
+    const bool host = c.mem == QPSK_MEM_HOST;   // synchronous calls only: pipelined ones take device memory
     const int64_t bytes_row = (2 * c.max_sym + 7) / 8;
     uint8_t *dbits = c.bits;
     int64_t dbits_stride = c.bits_stride_bytes;
     float *dsyms = c.syms;
     int64_t dsyms_stride = c.syms_stride_floats;
     if (host) {
-        if (async) return fail(QPSK_ERR_ARGUMENT, "pipelined calls take device memory");
         if (c.bits) {
-            const size_t need = static_cast<size_t>(S) * bytes_row;
-            if (need > h->xbits_bytes) {
-                hipFree(h->d_xbits);
-                h->d_xbits = nullptr;
-                h->xbits_bytes = 0;
-                if ((rc = dev_alloc(&h->d_xbits, need))) return rc;
-                h->xbits_bytes = need;
-            }
+            if ((rc = ensure_bytes(&h->d_xbits, &h->xbits_bytes, static_cast<size_t>(S) * bytes_row))) return rc;
             dbits = h->d_xbits;
             dbits_stride = bytes_row;
         }
         if (c.syms) {
             const size_t need = static_cast<size_t>(S) * 2 * c.max_sym * sizeof(float);
-            if (need > h->xsyms_bytes) {
-                hipFree(h->d_xsyms);
-                h->d_xsyms = nullptr;
-                h->xsyms_bytes = 0;
-                if ((rc = dev_alloc(&h->d_xsyms, need / sizeof(float)))) return rc;
-                h->xsyms_bytes = need;
-            }
+            if ((rc = ensure_bytes(&h->d_xsyms, &h->xsyms_bytes, need))) return rc;
             dsyms = h->d_xsyms;
             dsyms_stride = 2 * c.max_sym;
         }
-        HIP_TRY(hipMemsetAsync(h->d_flags + 1, 0, sizeof(uint32_t), h->stream));
+        QPSK_HIP_TRY(hipMemsetAsync(h->d_flags + 1, 0, sizeof(uint32_t), h->stream));
     }
     const int64_t K = (c.n_call + N - 1) / N;
     std::vector<int64_t> len_k(c.lengths ? S : 0);
@@ -1252,34 +1213,31 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
     if (!host) return QPSK_OK;
     hipStream_t st = h->stream;
     if (c.bits && bytes_row > 0)
-        HIP_TRY(hipMemcpy2DAsync(c.bits, c.bits_stride_bytes, dbits, dbits_stride, bytes_row, S,
-                                 hipMemcpyDeviceToHost, st));
+        QPSK_HIP_TRY(hipMemcpy2DAsync(c.bits, c.bits_stride_bytes, dbits, dbits_stride, bytes_row, S,
+                                      hipMemcpyDeviceToHost, st));
     if (c.syms && c.max_sym > 0)
-        HIP_TRY(hipMemcpy2DAsync(c.syms, c.syms_stride_floats * sizeof(float), dsyms,
-                                 dsyms_stride * sizeof(float), 2 * c.max_sym * sizeof(float), S,
-                                 hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h->h_counts, h->d_acc, 2 * S * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h->h_flags, h->d_flags + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c.n_bits) std::memcpy(c.n_bits, h->h_counts, S * sizeof(int64_t));
-    if (c.n_syms) std::memcpy(c.n_syms, h->h_counts + S, S * sizeof(int64_t));
-    h->status_host |= *h->h_flags;
+        QPSK_HIP_TRY(hipMemcpy2DAsync(c.syms, c.syms_stride_floats * sizeof(float), dsyms,
+                                      dsyms_stride * sizeof(float), 2 * c.max_sym * sizeof(float), S,
+                                      hipMemcpyDeviceToHost, st));
+    if ((rc = host_epilogue(h, c, h->d_acc, st))) return rc;
     return host_call_status(h);
 }
 
-}  // namespace (calls)
-
-namespace qpsk {
-// The host waits for every call queued on the handle, pipelined or stream-ordered
-// (the multi-device group's join, qpsk_group.cpp).
-int handle_sync(qpsk_demod *h) {
+// Every qpsk_demod_process* entry point: check, then the path the call's
+// length and kind ask for.
+int submit(qpsk_demod *h, Call &c, bool pipelined) {
+    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    if (c.fmt == kFmtCs16) c.scale = h->cs16_scale;   // queued calls keep the scale they were issued with
     int rc;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipSetDevice(h->p.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return QPSK_OK;
+    if ((rc = check_call(h, h->S, c))) return rc;
+    if (c.syms && (rc = ensure_syms(h))) return rc;
+    if (c.n_call > h->n_max) return process_chunked(h, c, pipelined);
+    if (pipelined) return process_async_one(h, c);
+    if ((rc = process_one(h, c))) return rc;
+    return c.mem == QPSK_MEM_HOST ? host_call_status(h) : QPSK_OK;
 }
-}  // namespace qpsk
+
+}  // namespace (calls)
 
 extern "C" {
 
@@ -1287,25 +1245,18 @@ int qpsk_demod_process(qpsk_demod *h, int32_t mode, const float *iq, int64_t str
                        int64_t n_samples, const int64_t *lengths, int32_t mem, uint8_t *bits,
                        int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
                        int64_t syms_stride_floats, int64_t *n_syms) {
-    Call c{mode, iq, stride_floats, n_samples, lengths, mem, bits, bits_stride_bytes, n_bits,
-           syms, syms_stride_floats, n_syms};
-    int rc;
-    if ((rc = validate(h, c))) return rc;
-    if (c.n_call > h->n_max) return process_chunked(h, c, false);
-    if ((rc = process_one(h, c))) return rc;
-    return c.mem == QPSK_MEM_HOST ? host_call_status(h) : QPSK_OK;
+    Call c{{mode, iq, stride_floats, n_samples, lengths, mem, bits, bits_stride_bytes, n_bits, syms,
+            syms_stride_floats, n_syms}};
+    return submit(h, c, false);
 }
 
 int qpsk_demod_process_async(qpsk_demod *h, int32_t mode, const float *iq, int64_t stride_floats,
                              int64_t n_samples, const int64_t *lengths, uint8_t *bits,
                              int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
                              int64_t syms_stride_floats, int64_t *n_syms) {
-    Call c{mode, iq, stride_floats, n_samples, lengths, QPSK_MEM_DEVICE, bits, bits_stride_bytes,
-           n_bits, syms, syms_stride_floats, n_syms};
-    int rc;
-    if ((rc = validate(h, c))) return rc;
-    if (c.n_call > h->n_max) return process_chunked(h, c, true);
-    return process_async_one(h, c);
+    Call c{{mode, iq, stride_floats, n_samples, lengths, QPSK_MEM_DEVICE, bits, bits_stride_bytes, n_bits, syms,
+            syms_stride_floats, n_syms}};
+    return submit(h, c, true);
 }
 
 int qpsk_demod_set_cs16_scale(qpsk_demod *h, float scale) {
@@ -1326,31 +1277,18 @@ int qpsk_demod_process_cs16(qpsk_demod *h, int32_t mode, const int16_t *iq, int6
                             int64_t n_samples, const int64_t *lengths, int32_t mem, uint8_t *bits,
                             int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
                             int64_t syms_stride_floats, int64_t *n_syms) {
-    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    Call c{mode, iq, stride_i16, n_samples, lengths, mem, bits, bits_stride_bytes, n_bits,
-           syms, syms_stride_floats, n_syms};
-    c.fmt = kFmtCs16;
-    c.scale = h->cs16_scale;
-    int rc;
-    if ((rc = validate(h, c))) return rc;
-    if (c.n_call > h->n_max) return process_chunked(h, c, false);
-    if ((rc = process_one(h, c))) return rc;
-    return c.mem == QPSK_MEM_HOST ? host_call_status(h) : QPSK_OK;
+    Call c{{mode, iq, stride_i16, n_samples, lengths, mem, bits, bits_stride_bytes, n_bits, syms,
+            syms_stride_floats, n_syms, kFmtCs16}};
+    return submit(h, c, false);
 }
 
 int qpsk_demod_process_async_cs16(qpsk_demod *h, int32_t mode, const int16_t *iq, int64_t stride_i16,
                                   int64_t n_samples, const int64_t *lengths, uint8_t *bits,
                                   int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
                                   int64_t syms_stride_floats, int64_t *n_syms) {
-    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    Call c{mode, iq, stride_i16, n_samples, lengths, QPSK_MEM_DEVICE, bits, bits_stride_bytes,
-           n_bits, syms, syms_stride_floats, n_syms};
-    c.fmt = kFmtCs16;
-    c.scale = h->cs16_scale;
-    int rc;
-    if ((rc = validate(h, c))) return rc;
-    if (c.n_call > h->n_max) return process_chunked(h, c, true);
-    return process_async_one(h, c);
+    Call c{{mode, iq, stride_i16, n_samples, lengths, QPSK_MEM_DEVICE, bits, bits_stride_bytes, n_bits, syms,
+            syms_stride_floats, n_syms, kFmtCs16}};
+    return submit(h, c, true);
 }
 
 int qpsk_demod_last_mf(qpsk_demod *h, float *out, int64_t stride_floats, int64_t n_samples, int32_t mem) {
@@ -1358,23 +1296,21 @@ int qpsk_demod_last_mf(qpsk_demod *h, float *out, int64_t stride_floats, int64_t
     if (n_samples < 0 || n_samples > h->n_max || stride_floats < 2 * n_samples)
         return fail(QPSK_ERR_ARGUMENT, "n_samples / stride_floats out of range");
     if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
-    HIP_TRY(hipSetDevice(h->p.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    QPSK_HIP_TRY(hipSetDevice(h->p.device));
+    QPSK_HIP_TRY(hipStreamSynchronize(h->stream));
     if (n_samples == 0) return QPSK_OK;
-    HIP_TRY(hipMemcpy2D(out, stride_floats * sizeof(float), h->d_mf[0] + 2 * kMfPrefix,
-                        2 * h->mf_stride * sizeof(float), 2 * n_samples * sizeof(float), h->S,
-                        mem == QPSK_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    QPSK_HIP_TRY(hipMemcpy2D(out, stride_floats * sizeof(float), h->d_mf[0] + 2 * kMfPrefix,
+                             2 * h->mf_stride * sizeof(float), 2 * n_samples * sizeof(float), h->S,
+                             mem == QPSK_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
     return QPSK_OK;
 }
 
 int qpsk_demod_status(qpsk_demod *h, uint32_t *flags) {
     if (!h || !flags) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     int rc;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipSetDevice(h->p.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(h->h_flags, h->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(h->d_flags, 0, sizeof(uint32_t)));
+    if ((rc = handle_sync(h))) return rc;
+    QPSK_HIP_TRY(hipMemcpy(h->h_flags, h->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    QPSK_HIP_TRY(hipMemset(h->d_flags, 0, sizeof(uint32_t)));
     *flags = *h->h_flags | h->status_host;
     h->status_host = 0;
     return QPSK_OK;
@@ -1386,8 +1322,8 @@ int qpsk_demod_pipeline_wait(qpsk_demod *h, void *hip_stream) {
     if ((rc = flush_deferred(h))) return rc;
     hipEvent_t e = last_async(h);
     if (!e) return QPSK_OK;
-    if (hip_stream) HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), e, 0));
-    else HIP_TRY(hipEventSynchronize(e));
+    if (hip_stream) QPSK_HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), e, 0));
+    else QPSK_HIP_TRY(hipEventSynchronize(e));
     return QPSK_OK;
 }
 
@@ -1397,9 +1333,9 @@ int qpsk_demod_gate_timeouts(qpsk_demod *h, uint64_t *count) {
     if (!h->d_gate) return QPSK_OK;
     int rc;
     if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipSetDevice(h->p.device));
+    QPSK_HIP_TRY(hipSetDevice(h->p.device));
     unsigned v = 0;
-    HIP_TRY(hipMemcpy(&v, h->d_gate, sizeof(unsigned), hipMemcpyDeviceToHost));
+    QPSK_HIP_TRY(hipMemcpy(&v, h->d_gate, sizeof(unsigned), hipMemcpyDeviceToHost));
     *count = v;
     return QPSK_OK;
 }
@@ -1490,19 +1426,17 @@ int qpsk_demod_get_state(qpsk_demod *h, void *host_buf, int64_t buf_bytes) {
     const int64_t S = h->S, H = h->T - 1;
     char *p = static_cast<char *>(host_buf);
     int rc;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipSetDevice(h->p.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = handle_sync(h))) return rc;
     const StateHeader hd = state_header(h);
     std::memcpy(p, &hd, sizeof(hd));
     p += sizeof(hd);
-    HIP_TRY(hipMemcpy(p, h->d_state, S * sizeof(StreamState), hipMemcpyDeviceToHost));
+    QPSK_HIP_TRY(hipMemcpy(p, h->d_state, S * sizeof(StreamState), hipMemcpyDeviceToHost));
     p += S * sizeof(StreamState);
-    HIP_TRY(hipMemcpy(p, h->d_carry, S * 8 * kCarryMax, hipMemcpyDeviceToHost));
+    QPSK_HIP_TRY(hipMemcpy(p, h->d_carry, S * 8 * kCarryMax, hipMemcpyDeviceToHost));
     p += S * 8 * kCarryMax;
-    if (H > 0) HIP_TRY(hipMemcpy(p, h->d_hist[h->hist_cur], S * 8 * H, hipMemcpyDeviceToHost));
+    if (H > 0) QPSK_HIP_TRY(hipMemcpy(p, h->d_hist[h->hist_cur], S * 8 * H, hipMemcpyDeviceToHost));
     p += S * 8 * H;
-    HIP_TRY(hipMemcpy(p, h->d_fll_delay, S * 8 * 2 * kFllTaps, hipMemcpyDeviceToHost));
+    QPSK_HIP_TRY(hipMemcpy(p, h->d_fll_delay, S * 8 * 2 * kFllTaps, hipMemcpyDeviceToHost));
     return QPSK_OK;
 }
 
@@ -1526,25 +1460,15 @@ int qpsk_demod_set_state(qpsk_demod *h, const void *host_buf, int64_t buf_bytes)
     const int64_t S = h->S, H = h->T - 1;
     const char *p = static_cast<const char *>(host_buf) + sizeof(StateHeader);
     int rc;
-    if ((rc = drain_async(h))) return rc;
-    HIP_TRY(hipSetDevice(h->p.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(h->d_state, p, S * sizeof(StreamState), hipMemcpyHostToDevice));
+    if ((rc = handle_sync(h))) return rc;
+    QPSK_HIP_TRY(hipMemcpy(h->d_state, p, S * sizeof(StreamState), hipMemcpyHostToDevice));
     p += S * sizeof(StreamState);
-    HIP_TRY(hipMemcpy(h->d_carry, p, S * 8 * kCarryMax, hipMemcpyHostToDevice));
+    QPSK_HIP_TRY(hipMemcpy(h->d_carry, p, S * 8 * kCarryMax, hipMemcpyHostToDevice));
     p += S * 8 * kCarryMax;
-    if (H > 0) HIP_TRY(hipMemcpy(h->d_hist[h->hist_cur], p, S * 8 * H, hipMemcpyHostToDevice));
+    if (H > 0) QPSK_HIP_TRY(hipMemcpy(h->d_hist[h->hist_cur], p, S * 8 * H, hipMemcpyHostToDevice));
     p += S * 8 * H;
-    HIP_TRY(hipMemcpy(h->d_fll_delay, p, S * 8 * 2 * kFllTaps, hipMemcpyHostToDevice));
+    QPSK_HIP_TRY(hipMemcpy(h->d_fll_delay, p, S * 8 * 2 * kFllTaps, hipMemcpyHostToDevice));
     return QPSK_OK;
-}
-
-int32_t qpsk_demod_pick_loop_variant(int32_t requested, int32_t n_streams, double sps, int32_t cus) {
-    if (requested != 0 || !(sps >= 8.0) || cus <= 0 || n_streams <= 0) return requested;
-    const int64_t S = n_streams;
-    if ((S + 5) / 6 <= cus) return 7;
-    if ((S + 11) / 12 <= cus) return 6;
-    return 0;
 }
 
 int qpsk_demod_loop_shape(int32_t requested, int32_t n_streams, double sps, int32_t cus, int32_t rrc_taps,
@@ -1552,22 +1476,7 @@ int qpsk_demod_loop_shape(int32_t requested, int32_t n_streams, double sps, int3
     if (!out) return fail(QPSK_ERR_ARGUMENT_NULL, "out is NULL");
     if (requested < 0 || requested > 7 || n_streams <= 0 || !(sps > 0.0) || costas_trig < 0 || costas_trig > 1)
         return fail(QPSK_ERR_ARGUMENT, "loop shape arguments");
-    LoopShapeInfo i{};
-    loop_shape_info(qpsk_demod_pick_loop_variant(requested, n_streams, sps, cus), n_streams, sps, cus, rrc_taps,
-                    costas_trig, want_syms, &i);
-    out->streams = i.streams;
-    out->lanes = i.lanes;
-    out->round = i.round;
-    out->slots = i.slots;
-    out->prefix = i.prefix;
-    out->cap = i.cap;
-    out->lds_bytes = i.lds_bytes;
-    out->fir_beside = i.fir_beside;
-    out->fir_taps = i.fir_taps;
-    out->fir_lds_bytes = i.fir_lds_bytes;
-    out->lds_granule = i.lds_granule;
-    out->reserved = 0;
-    out->lag_max = i.lag_max;
+    loop_shape_info(requested, n_streams, sps, cus, rrc_taps, costas_trig, want_syms, out);
     return QPSK_OK;
 }
 

@@ -23,30 +23,15 @@
 // matched filter widens them (qpsk_demod_process_async_cs16).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "qpsk_demod.h"
-
-namespace qpsk {
-int set_last_error(int code, const std::string &msg);
-hipStream_t pipe_front_stream(const qpsk_demod *h);
-int handle_streams(const qpsk_demod *h);
-int64_t handle_max_samples(const qpsk_demod *h);
-int handle_device(const qpsk_demod *h);
-}  // namespace qpsk
+#include "qpsk_internal.h"
 
 namespace {
-int fail(int code, const std::string &msg) { return qpsk::set_last_error(code, msg); }
-
-#define RX_TRY(expr)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return fail(QPSK_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+using qpsk::fail;
 
 struct Slot {
     void *h_in = nullptr;       // pinned [S][in_stride] floats, or int16 (CS16 ring)
@@ -94,22 +79,22 @@ void release(qpsk_rx *r) {
 }
 
 int setup(qpsk_rx *r) {
-    RX_TRY(hipSetDevice(r->device));
-    RX_TRY(hipStreamCreateWithFlags(&r->up, hipStreamNonBlocking));
-    RX_TRY(hipStreamCreateWithFlags(&r->down, hipStreamNonBlocking));
+    QPSK_HIP_TRY(hipSetDevice(r->device));
+    QPSK_HIP_TRY(hipStreamCreateWithFlags(&r->up, hipStreamNonBlocking));
+    QPSK_HIP_TRY(hipStreamCreateWithFlags(&r->down, hipStreamNonBlocking));
     const size_t S = static_cast<size_t>(r->S);
     const size_t in_bytes = S * static_cast<size_t>(r->in_stride) * r->elem;
     const size_t bit_bytes = S * static_cast<size_t>(r->bits_stride);
     r->slots.resize(r->depth);
     for (auto &s : r->slots) {
-        RX_TRY(hipHostMalloc(&s.h_in, in_bytes));
-        RX_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_bits), bit_bytes));
-        RX_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_nb), S * sizeof(int64_t)));
-        RX_TRY(hipMalloc(&s.d_in, in_bytes));
-        RX_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_bits), bit_bytes));
-        RX_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_nb), S * sizeof(int64_t)));
-        RX_TRY(hipEventCreateWithFlags(&s.in_free, hipEventDisableTiming));
-        RX_TRY(hipEventCreateWithFlags(&s.out_done, hipEventDisableTiming));
+        QPSK_HIP_TRY(hipHostMalloc(&s.h_in, in_bytes));
+        QPSK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_bits), bit_bytes));
+        QPSK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_nb), S * sizeof(int64_t)));
+        QPSK_HIP_TRY(hipMalloc(&s.d_in, in_bytes));
+        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_bits), bit_bytes));
+        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_nb), S * sizeof(int64_t)));
+        QPSK_HIP_TRY(hipEventCreateWithFlags(&s.in_free, hipEventDisableTiming));
+        QPSK_HIP_TRY(hipEventCreateWithFlags(&s.out_done, hipEventDisableTiming));
     }
     return QPSK_OK;
 }
@@ -147,7 +132,7 @@ int next_slot(qpsk_rx *r, bool cs16, void **iq, int64_t *stride_floats) {
         return fail(QPSK_ERR_STATE, "every ring slot holds an uncollected chunk");
     Slot &sl = r->slots[r->submitted % r->depth];
     // the caller writes the slot next: its previous chunk must have been read
-    if (sl.in_rec) RX_TRY(hipEventSynchronize(sl.in_free));
+    if (sl.in_rec) QPSK_HIP_TRY(hipEventSynchronize(sl.in_free));
     *iq = sl.h_in;
     if (stride_floats) *stride_floats = r->in_stride;
     return QPSK_OK;
@@ -160,25 +145,23 @@ int submit(qpsk_rx *r, bool cs16, const void *iq, int64_t stride_floats, int64_t
     if (r->submitted - r->collected >= r->depth)
         return fail(QPSK_ERR_STATE, "every ring slot holds an uncollected chunk");
     const int S = r->S;
-    int64_t n_call = n_samples;
-    if (lengths) {
-        n_call = 0;
-        for (int s = 0; s < S; ++s) {
-            if (lengths[s] < 0) return fail(QPSK_ERR_ARGUMENT, "negative length");
-            n_call = std::max(n_call, lengths[s]);
-        }
-    } else if (n_samples < 0) {
-        return fail(QPSK_ERR_ARGUMENT, "negative n_samples");
-    }
-    if (n_call > r->n_max) return fail(QPSK_ERR_ARGUMENT, "chunk longer than the ring slots (max_samples_per_call)");
-    if (n_call > 0 && !iq) return fail(QPSK_ERR_ARGUMENT_NULL, "SamplesIQ is null");
-    if (n_call > 0 && stride_floats < 2 * n_call) return fail(QPSK_ERR_ARGUMENT, "stride too small");
-    RX_TRY(hipSetDevice(r->device));
     Slot &sl = r->slots[r->submitted % r->depth];
+    int rc;
+    int64_t n_call = 0;
+    // a slot is shorter than the longest call a handle takes, so the ring's own
+    // limit answers before the shared check's
+    if ((rc = qpsk::call_length(S, n_samples, lengths, &n_call))) return rc;
+    if (n_call > r->n_max) return fail(QPSK_ERR_ARGUMENT, "chunk longer than the ring slots (max_samples_per_call)");
+    // the call as the handle will see it, but on the caller's host rows (which
+    // no rule asks the sample format of)
+    qpsk::CallArgs c{QPSK_MODE_DEMODULATE, iq, stride_floats, n_samples, lengths, QPSK_MEM_HOST,
+                     sl.d_bits, r->bits_stride, sl.d_nb, nullptr, 0, nullptr};
+    if ((rc = qpsk::check_call(r->h, S, c))) return rc;
+    QPSK_HIP_TRY(hipSetDevice(r->device));
     // the slot's previous chunk: its input was consumed (front stage) and its
     // bits were downloaded before this chunk overwrites either (the back stage
     // of this chunk follows the upload through the handle's stream)
-    if (sl.in_rec) RX_TRY(hipEventSynchronize(sl.in_free));
+    if (sl.in_rec) QPSK_HIP_TRY(hipEventSynchronize(sl.in_free));
     if (n_call > 0 && iq != sl.h_in) {
         for (int s = 0; s < S; ++s) {
             const int64_t len = lengths ? lengths[s] : n_call;
@@ -189,26 +172,26 @@ int submit(qpsk_rx *r, bool cs16, const void *iq, int64_t stride_floats, int64_t
     } else if (n_call > 0 && stride_floats != r->in_stride) {
         return fail(QPSK_ERR_ARGUMENT, "a ring slot has a stride of 2 * max_samples_per_call elements");
     }
-    if (sl.out_rec) RX_TRY(hipStreamWaitEvent(r->up, sl.out_done, 0));
+    if (sl.out_rec) QPSK_HIP_TRY(hipStreamWaitEvent(r->up, sl.out_done, 0));
     if (n_call > 0)
-        RX_TRY(hipMemcpy2DAsync(sl.d_in, r->in_stride * r->elem, sl.h_in, r->in_stride * r->elem,
-                                2 * n_call * r->elem, S, hipMemcpyHostToDevice, r->up));
-    int rc = cs16 ? qpsk_demod_process_async_cs16(r->h, QPSK_MODE_DEMODULATE, static_cast<const int16_t *>(sl.d_in),
+        QPSK_HIP_TRY(hipMemcpy2DAsync(sl.d_in, r->in_stride * r->elem, sl.h_in, r->in_stride * r->elem,
+                                      2 * n_call * r->elem, S, hipMemcpyHostToDevice, r->up));
+    rc = cs16 ? qpsk_demod_process_async_cs16(r->h, QPSK_MODE_DEMODULATE, static_cast<const int16_t *>(sl.d_in),
                                                   r->in_stride, n_samples, lengths, sl.d_bits, r->bits_stride,
                                                   sl.d_nb, nullptr, 0, nullptr)
-                  : qpsk_demod_process_async(r->h, QPSK_MODE_DEMODULATE, static_cast<const float *>(sl.d_in),
-                                             r->in_stride, n_samples, lengths, sl.d_bits, r->bits_stride, sl.d_nb,
-                                             nullptr, 0, nullptr);
+              : qpsk_demod_process_async(r->h, QPSK_MODE_DEMODULATE, static_cast<const float *>(sl.d_in),
+                                         r->in_stride, n_samples, lengths, sl.d_bits, r->bits_stride, sl.d_nb,
+                                         nullptr, 0, nullptr);
     if (rc != QPSK_OK) return rc;
-    RX_TRY(hipEventRecord(sl.in_free, qpsk::pipe_front_stream(r->h)));
+    QPSK_HIP_TRY(hipEventRecord(sl.in_free, qpsk::pipe_front_stream(r->h)));
     sl.in_rec = true;
     if ((rc = qpsk_demod_pipeline_wait(r->h, r->down)) != QPSK_OK) return rc;
     sl.row_bytes = (2 * qpsk_demod_max_symbols(r->h, n_call) + 7) / 8;
-    RX_TRY(hipMemcpyAsync(sl.h_nb, sl.d_nb, S * sizeof(int64_t), hipMemcpyDeviceToHost, r->down));
+    QPSK_HIP_TRY(hipMemcpyAsync(sl.h_nb, sl.d_nb, S * sizeof(int64_t), hipMemcpyDeviceToHost, r->down));
     if (sl.row_bytes > 0)
-        RX_TRY(hipMemcpy2DAsync(sl.h_bits, r->bits_stride, sl.d_bits, r->bits_stride, sl.row_bytes, S,
-                                hipMemcpyDeviceToHost, r->down));
-    RX_TRY(hipEventRecord(sl.out_done, r->down));
+        QPSK_HIP_TRY(hipMemcpy2DAsync(sl.h_bits, r->bits_stride, sl.d_bits, r->bits_stride, sl.row_bytes, S,
+                                      hipMemcpyDeviceToHost, r->down));
+    QPSK_HIP_TRY(hipEventRecord(sl.out_done, r->down));
     sl.out_rec = true;
     if (ticket) *ticket = r->submitted;
     ++r->submitted;
@@ -256,8 +239,8 @@ int qpsk_rx_collect(qpsk_rx *r, uint8_t *bits, int64_t bits_stride_bytes, int64_
     Slot &sl = r->slots[r->collected % r->depth];
     if (bits_stride_bytes < sl.row_bytes)
         return fail(QPSK_ERR_ARGUMENT, "bits_stride_bytes smaller than 2*max_symbols/8");
-    RX_TRY(hipSetDevice(r->device));
-    RX_TRY(hipEventSynchronize(sl.out_done));
+    QPSK_HIP_TRY(hipSetDevice(r->device));
+    QPSK_HIP_TRY(hipEventSynchronize(sl.out_done));
     for (int s = 0; s < r->S; ++s) {
         const int64_t nb = sl.h_nb[s];
         n_bits[s] = nb;

@@ -227,9 +227,10 @@ GATE_ENV = ["QPSK_PIPELINE_GATE", "AMD_SERIALIZE_KERNEL", "AMD_SERIALIZE_COPY", 
     ({"AMD_SERIALIZE_KERNEL": ""}, 1),   # set but empty = unset
 ])
 def test_pipeline_gate_predicate(monkeypatch, env, want):
-    """The residency gate (qpsk_runtime.hip, process_async_one) parks the FIR's
-    stream on hipStreamWaitValue64 with no timeout, so it must be off wherever
-    dispatch is serialised (include/qpsk_demod.h, qpsk_pipeline_gate_enabled);
+    """The residency gate (qpsk_runtime.hip, gate_wait_kernel) holds the FIR's
+    stream until the loop kernel's workgroups have started, or a timeout; where
+    dispatch is serialised every wait would run to that timeout, so the gate
+    must be off there (include/qpsk_demod.h, qpsk_pipeline_gate_enabled);
     evaluated without a device."""
     for k in GATE_ENV:
         monkeypatch.delenv(k, raising=False)
