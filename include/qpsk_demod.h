@@ -450,6 +450,85 @@ int qpsk_rx_submit_cs16(qpsk_rx *r, const int16_t *iq, int64_t stride_i16, int64
                         const int64_t *lengths, int64_t *ticket);
 
 /* ---------------------------------------------------------------------------
+ * Format-tagged entry points, and 8-bit input (CS8, CU8).
+ *
+ * The reference asks its driver for ComplexFloat32 (ModDemodOverSDR.cs:63-64)
+ * and hands those buffers to DeModulate (the receive loop, :116-183).  HackRF
+ * and RTL-SDR hardware, whose SoapySDR modules the reference ships, deliver
+ * 8-bit samples natively: SoapySDR "CS8" (interleaved int8 I,Q) and the raw
+ * "CU8" (interleaved uint8 I,Q, offset 128) of rtl-sdr and most capture files.
+ * One family of entry points takes the sample format as an argument, so a
+ * format adds no functions; the float and _cs16 entry points above are these
+ * with their format fixed.
+ *
+ * A sample's value (SoapySDR's S8toF32 / U8toS8, full scale 128):
+ *   QPSK_FMT_CS8   (float)(int8)x * scale
+ *   QPSK_FMT_CU8   (float)((int)x - 128) * scale
+ * The integer is exact in float and the multiply is the one rounding (no fma),
+ * done inside the first kernel that reads the samples, as for CS16 input: the
+ * chain computes bit for bit what it computes from the widened floats, and
+ * all state stays float, so a handle may alternate all four formats call by
+ * call (the state blob and QPSK_ABI_VERSION are unchanged).
+ */
+#define QPSK_FMT_CF32 0   /* interleaved float32 I,Q: qpsk_demod_process           */
+#define QPSK_FMT_CS16 1   /* interleaved int16 I,Q:   qpsk_demod_process_cs16      */
+#define QPSK_FMT_CS8 2    /* interleaved int8 I,Q                                  */
+#define QPSK_FMT_CU8 3    /* interleaved uint8 I,Q, zero at 128                    */
+/* Bytes of one complex sample: 8 / 4 / 2 / 2; negative (QPSK_ERR_ARGUMENT) for
+ * an unknown format.  A row's stride_elems counts elements of half that size
+ * (floats, int16 or bytes).  Needs no device.  Every entry point below returns
+ * QPSK_ERR_ARGUMENT for an unknown fmt. */
+int qpsk_fmt_sample_bytes(int32_t fmt);
+/* The scale of an integer format, per handle and per format: 1.0f / 32768 for
+ * CS16 (the variable qpsk_demod_set_cs16_scale sets), 1.0f / 128 for CS8 and
+ * CU8.  Captured when a call is issued, as the CS16 scale is; finite and > 0,
+ * else QPSK_ERR_OUT_OF_RANGE (the scale is then unchanged).  CF32 has no
+ * scale: QPSK_ERR_ARGUMENT. */
+int qpsk_demod_set_input_scale(qpsk_demod *h, int32_t fmt, float scale);
+int qpsk_demod_get_input_scale(const qpsk_demod *h, int32_t fmt, float *scale);
+/* qpsk_demod_process / qpsk_demod_process_async with iq as
+ * [n_streams][stride_elems] elements of fmt, stream s holding 2*len(s) of
+ * them; every other argument, check, limit and result as there (longer calls
+ * chunk the same way; qpsk_demod_last_mf works after the synchronous one).
+ * Device rows of CF32 and CS16 follow the rules of their own entry points.
+ * Device rows of an 8-bit format must be 2-byte aligned with an even
+ * stride_elems, else QPSK_ERR_ARGUMENT; rows that are 16-byte aligned with
+ * stride_elems % 16 == 0 are read with 16-byte loads (8 samples; 8-byte loads
+ * of 4 samples, from 8-byte alignment and stride_elems % 8 == 0 on, for the 13-
+ * and 21-tap filters), others with 2-byte loads.  Host-memory calls are staged
+ * in rows pitched to 8 samples and always take the wide loads.  A device call
+ * longer than max_samples_per_call reads chunk k at iq + 2 * k *
+ * max_samples_per_call elements, so its chunks after the first keep the wide
+ * loads only when max_samples_per_call is a multiple of 8 (the same holds for
+ * CS16 rows and a multiple of 4); the results do not depend on it. */
+int qpsk_demod_process_fmt(qpsk_demod *h, int32_t fmt, int32_t mode, const void *iq, int64_t stride_elems,
+                           int64_t n_samples, const int64_t *lengths, int32_t mem, uint8_t *bits,
+                           int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                           int64_t syms_stride_floats, int64_t *n_syms);
+int qpsk_demod_process_async_fmt(qpsk_demod *h, int32_t fmt, int32_t mode, const void *iq, int64_t stride_elems,
+                                 int64_t n_samples, const int64_t *lengths, uint8_t *bits,
+                                 int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                                 int64_t syms_stride_floats, int64_t *n_syms);
+/* qpsk_rx_create / qpsk_rx_next_slot / qpsk_rx_submit for a ring of any one
+ * format: pinned slots of [n_streams][2 * max_samples_per_call] elements (an
+ * 8-bit ring: bytes, a quarter of the float ring's pinned memory and upload),
+ * queued as qpsk_demod_process_async_fmt with the handle's scale at submit.
+ * A ring has one format: next_slot / submit with another one (these or the
+ * float and _cs16 ones) return QPSK_ERR_STATE.  collect and destroy are the
+ * float ring's. */
+int qpsk_rx_create_fmt(qpsk_demod *h, int32_t depth, int32_t fmt, qpsk_rx **out);
+int qpsk_rx_next_slot_fmt(qpsk_rx *r, int32_t fmt, void **iq, int64_t *stride_elems);
+int qpsk_rx_submit_fmt(qpsk_rx *r, int32_t fmt, const void *iq, int64_t stride_elems, int64_t n_samples,
+                       const int64_t *lengths, int64_t *ticket);
+/* qpsk_demod_group_process for rows of any format (the group's only CS16 and
+ * 8-bit entry): shard k reads iq + first_k * stride_elems * element size.  The
+ * whole-batch argument check comes first, as there. */
+int qpsk_demod_group_process_fmt(qpsk_demod_group *g, int32_t fmt, int32_t mode, const void *iq,
+                                 int64_t stride_elems, int64_t n_samples, const int64_t *lengths, int32_t mem,
+                                 uint8_t *bits, int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                                 int64_t syms_stride_floats, int64_t *n_syms);
+
+/* ---------------------------------------------------------------------------
  * Byte framer (DeModulateBytes, QPSKDeModulator.cs:169-259), batched: one
  * framer per stream fed with the packed bits of each process() call.
  */

@@ -6,8 +6,8 @@
 // so S independent streams split into contiguous shards with no exchange at
 // all: shard k = streams [S*k/n, S*(k+1)/n) on devices[k], one ordinary handle
 // each.  A group call fans the caller's rows out by row offset -- shard k reads
-// iq + first_k * stride and writes bits + first_k * bits_stride, n_bits +
-// first_k, ... -- and joins.  Each shard runs in its own persistent worker
+// iq + first_k * stride (in elements of the call's sample format) and writes
+// bits + first_k * bits_stride, n_bits + first_k, ... -- and joins.  Each shard runs in its own persistent worker
 // thread (a host-memory process() is synchronous and its H2D / D2H copies hold
 // the thread), so the devices' calls, copies included, overlap.  Results are
 // those of one handle over the whole batch, stream for stream: nothing a
@@ -200,11 +200,23 @@ int qpsk_demod_group_process(qpsk_demod_group *g, int32_t mode, const float *iq,
                              int64_t n_samples, const int64_t *lengths, int32_t mem, uint8_t *bits,
                              int64_t bits_stride_bytes, int64_t *n_bits, float *syms, int64_t syms_stride_floats,
                              int64_t *n_syms) {
+    return qpsk_demod_group_process_fmt(g, QPSK_FMT_CF32, mode, iq, stride_floats, n_samples, lengths, mem, bits,
+                                        bits_stride_bytes, n_bits, syms, syms_stride_floats, n_syms);
+}
+
+int qpsk_demod_group_process_fmt(qpsk_demod_group *g, int32_t fmt, int32_t mode, const void *iq_rows,
+                                 int64_t stride_floats, int64_t n_samples, const int64_t *lengths, int32_t mem,
+                                 uint8_t *bits, int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                                 int64_t syms_stride_floats, int64_t *n_syms) {
     if (!g) return fail(QPSK_ERR_ARGUMENT_NULL, "null group");
+    const int sample_bytes = qpsk_fmt_sample_bytes(fmt);
+    if (sample_bytes < 0) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
+    const int64_t elem = sample_bytes / 2;   // bytes of one of a row's stride_elems elements
+    const char *iq = static_cast<const char *>(iq_rows);
     // the check every shard would make, made once on the whole batch first, so
     // a bad argument fails the call before any shard's state moves
     qpsk::CallArgs c{mode, iq, stride_floats, n_samples, lengths, mem, bits, bits_stride_bytes, n_bits,
-                     syms, syms_stride_floats, n_syms};
+                     syms, syms_stride_floats, n_syms, fmt};
     int rc;
     if ((rc = qpsk::check_call(g->shards[0].h, g->S, c))) return rc;
     if (mem == QPSK_MEM_DEVICE) {
@@ -218,11 +230,12 @@ int qpsk_demod_group_process(qpsk_demod_group *g, int32_t mode, const float *iq,
     return fan_out(g, [=](int k) {
         const Shard &sh = g->shards[k];
         const int64_t f = sh.first;
-        int rc = qpsk_demod_process(sh.h, mode, iq ? iq + f * stride_floats : nullptr, stride_floats, n_samples,
-                                    lengths ? lengths + f : nullptr, mem, bits ? bits + f * bits_stride_bytes : nullptr,
-                                    bits_stride_bytes, n_bits ? n_bits + f : nullptr,
-                                    syms ? syms + f * syms_stride_floats : nullptr, syms_stride_floats,
-                                    n_syms ? n_syms + f : nullptr);
+        int rc = qpsk_demod_process_fmt(sh.h, fmt, mode, iq ? iq + f * stride_floats * elem : nullptr, stride_floats,
+                                        n_samples, lengths ? lengths + f : nullptr, mem,
+                                        bits ? bits + f * bits_stride_bytes : nullptr, bits_stride_bytes,
+                                        n_bits ? n_bits + f : nullptr,
+                                        syms ? syms + f * syms_stride_floats : nullptr, syms_stride_floats,
+                                        n_syms ? n_syms + f : nullptr);
         // device-memory calls are stream-ordered per shard: the group joins
         if (rc == QPSK_OK && mem == QPSK_MEM_DEVICE) rc = qpsk::handle_sync(sh.h);
         return rc;

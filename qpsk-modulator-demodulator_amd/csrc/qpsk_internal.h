@@ -16,8 +16,8 @@ int fail(int code, const std::string &msg);
 // One call as its caller gave it (the arguments of qpsk_demod_process).
 struct CallArgs {
     int32_t mode;
-    const void *iq;          // float rows, or int16 rows (fmt = kFmtCs16)
-    int64_t stride_floats;   // row stride in elements of iq: two per sample in either format
+    const void *iq;          // float rows, int16 rows (CS16) or byte rows (CS8 / CU8)
+    int64_t stride_floats;   // row stride in elements of iq: two per sample in every format
     int64_t n_samples;
     const int64_t *lengths;
     int32_t mem;
@@ -27,7 +27,7 @@ struct CallArgs {
     float *syms;
     int64_t syms_stride_floats;
     int64_t *n_syms;
-    int32_t fmt = 0;         // kFmtCf32 / kFmtCs16 (qpsk_kernels.h)
+    int32_t fmt = 0;         // QPSK_FMT_* (= kFmt*, qpsk_kernels.h)
     int64_t n_call = 0;      // derived by check_call: the longest row, and
     int64_t max_sym = 0;     // qpsk_demod_max_symbols of it
 };
@@ -36,7 +36,7 @@ struct CallArgs {
 // negative count is QPSK_ERR_ARGUMENT.
 int call_length(int S, int64_t n_samples, const int64_t *lengths, int64_t *n_call);
 // The checks every call over S rows makes before anything is launched, copied
-// or allocated, in one order and with one text per rule: mode, mem,
+// or allocated, in one order and with one text per rule: the format, mode, mem,
 // call_length, the sample limit, iq and its stride, the outputs the mode needs
 // and their strides, and what device rows must satisfy.  h gives the symbol
 // bound (a group's shards share it).  Fills c.n_call and c.max_sym.

@@ -86,11 +86,20 @@ constexpr int32_t kFmtCs16 = 1;
 struct FirArgsCs16 : FirArgs {
     float x_scale;
 };
+// kFmtCs8 / kFmtCu8 = x points at [S][x_stride] byte pairs and a sample's value
+// is ((float)(uint8)(v ^ flip) - 128) * x_scale: flip = 0x80 in every byte for
+// CS8 (an int8 x is (uint8)(x ^ 0x80) - 128), 0 for CU8.  One set of kernels
+// serves both; the flip mask rides behind the scale.
+constexpr int32_t kFmtCs8 = 2;
+constexpr int32_t kFmtCu8 = 3;
+struct FirArgsI8 : FirArgsCs16 {
+    uint32_t x_flip;
+};
 
-// CS16 rows widened into float2 rows, for the serial pre-stages (IQ balancer,
-// FLL) that read one sample per step and already write a float row
+// CS16 or 8-bit rows widened into float2 rows, for the serial pre-stages (IQ
+// balancer, FLL) that read one sample per step and already write a float row
 struct WidenArgs {
-    const int16_t *x;      // [S][x_stride] int16 pairs
+    const void *x;         // [S][x_stride] int16 pairs, or byte pairs
     int64_t x_stride;      // in samples
     float *y;              // [S][y_stride] float2 output at y_offset
     int64_t y_stride;
@@ -181,7 +190,7 @@ bool launch_fir(const FirArgs &a, const float *hrev_dev, int T, int W, int S,
                 int64_t n_max, hipStream_t stream, int32_t x_fmt = kFmtCf32, float x_scale = 0.0f);
 void launch_fir_hist(const FirArgs &a, float *hist_new, int H, int S, hipStream_t stream,
                      int32_t x_fmt = kFmtCf32, float x_scale = 0.0f);
-void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream);
+void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream, int32_t x_fmt = kFmtCs16);
 // carry kernel + loop kernel; returns the loop kernel's workgroup count
 // variant = the requested qpsk_demod_params.loop_variant; cus = the device's CU
 // count, taps = the matched filter's (0: unknown), for the automatic shape

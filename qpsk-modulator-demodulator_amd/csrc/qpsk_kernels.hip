@@ -30,6 +30,11 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // CS16 input: one sample = an int16 pair, widened where it is loaded
 typedef short s2 __attribute__((ext_vector_type(2)));
 typedef short s8 __attribute__((ext_vector_type(8)));
+// CS8 / CU8 input: one sample = a byte pair; both formats go through one
+// element type (a uniform XOR of 0x80 on each byte tells them apart)
+typedef unsigned char b2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
 template <typename A, typename B> struct same_type { static constexpr bool value = false; };
 template <typename A> struct same_type<A, A> { static constexpr bool value = true; };
@@ -38,17 +43,46 @@ template <typename A> struct same_type<A, A> { static constexpr bool value = tru
 __device__ __forceinline__ f2 widen(s2 v, float scale) {
     return f2{static_cast<float>(v.x) * scale, static_cast<float>(v.y) * scale};
 }
+// Two 8-bit samples (I0 Q0 I1 Q1, one byte each, lowest first) of a word
+// already XORed with the format's flip mask: ((float)byte - 128) * scale.  The
+// byte and the difference are exact in float, so the multiply is the one
+// rounding (v_cvt_f32_ubyte0..3, a packed subtract, a packed multiply).
+__device__ __forceinline__ void widen8(unsigned w, float scale, f2 &u0, f2 &u1) {
+    const f2 bias = f2{128.0f, 128.0f};
+    u0 = (f2{static_cast<float>(w & 0xffu), static_cast<float>((w >> 8) & 0xffu)} - bias) * scale;
+    u1 = (f2{static_cast<float>((w >> 16) & 0xffu), static_cast<float>(w >> 24)} - bias) * scale;
+}
+// one sample: int8 x = (uint8)(x ^ 0x80) - 128 (CS8, flip = 0x80 in every
+// byte); CU8 is (uint8)x - 128 as it stands (flip = 0)
+__device__ __forceinline__ f2 widen(b2 v, float scale, unsigned flip) {
+    const unsigned w = (static_cast<unsigned>(v.x) | (static_cast<unsigned>(v.y) << 8)) ^ (flip & 0xffffu);
+    return (f2{static_cast<float>(w & 0xffu), static_cast<float>(w >> 8)} - f2{128.0f, 128.0f}) * scale;
+}
 // The kernel argument block of each element type, and its scale
 template <typename XT> struct fir_args { typedef FirArgs type; };
 template <> struct fir_args<s2> { typedef FirArgsCs16 type; };
+template <> struct fir_args<b2> { typedef FirArgsI8 type; };
 __device__ __forceinline__ float x_scale(const FirArgs &) { return 0.0f; }
 __device__ __forceinline__ float x_scale(const FirArgsCs16 &a) { return a.x_scale; }
+__device__ __forceinline__ float x_scale(const FirArgsI8 &a) { return a.x_scale; }
+__device__ __forceinline__ unsigned x_flip(const FirArgs &) { return 0u; }
+__device__ __forceinline__ unsigned x_flip(const FirArgsI8 &a) { return a.x_flip; }
 // Input sample g of a row of either element type; the float2 row is read as it
 // always was (scale unused).
 template <typename XT>
 __device__ __forceinline__ f2 load_x(const XT *x, int64_t g, float scale) {
     if constexpr (same_type<XT, f2>::value) return x[g];
     else return widen(x[g], scale);
+}
+// ... and of an 8-bit row
+__device__ __forceinline__ f2 load_x(const b2 *x, int64_t g, float scale, unsigned flip) {
+    return widen(x[g], scale, flip);
+}
+// load_x with the arguments the element type's block carries
+template <typename XT, typename A>
+__device__ __forceinline__ f2 load_xa(const XT *x, int64_t g, const A &a) {
+    if constexpr (same_type<XT, b2>::value) return load_x(x, g, x_scale(a), x_flip(a));
+    else return load_x(x, g, x_scale(a));
 }
 
 // ---------------------------------------------------------------------------
@@ -255,6 +289,49 @@ __device__ __forceinline__ void fir_stage_cs16(f2 *lds, const s2 *x, const f2 *h
     }
 }
 
+// The same LDS image from 8-bit rows (CS8 / CU8, two bytes a sample).  L = the
+// samples of one vector load: 8 (16 B) where T - 1 is a multiple of 8, so that
+// g0, a multiple of 8, keeps every load inside one 64-sample LDS row (four
+// 16-B LDS writes); 4 (8 B) for T - 1 = 4 mod 8 (T = 13, 21).
+template <int T> constexpr int i8_vec_samples() { return (T - 1) % 8 == 0 ? 8 : 4; }
+template <int T, int NIN, bool VEC, int NT>
+__device__ __forceinline__ void fir_stage_i8(f2 *lds, const b2 *x, const f2 *hist, int64_t tile0, int64_t n,
+                                             float scale, unsigned flip) {
+    const int tid = threadIdx.x;
+    const int64_t g0 = tile0 - (T - 1);
+    auto one = [&](int64_t g) -> f2 {
+        return g < 0 ? hist[T - 1 + g] : (g < n ? widen(x[g], scale, flip) : f2{0.f, 0.f});
+    };
+    if constexpr (VEC) {
+        constexpr int L = i8_vec_samples<T>();
+        static_assert((T - 1) % 4 == 0, "8-bit vector staging expects T = 1 mod 4");
+        for (int p = tid; p < (NIN + L - 1) / L; p += NT) {
+            const int64_t g = g0 + L * p;
+            f2 u[L];
+            if (g >= 0 && g + L - 1 < n) {
+                if constexpr (L == 8) {
+                    const u4 v = *reinterpret_cast<const u4 *>(x + g) ^ flip;   // one packed XOR per 4 bytes
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) widen8(v[k], scale, u[2 * k], u[2 * k + 1]);
+                } else {
+                    const u2 v = *reinterpret_cast<const u2 *>(x + g) ^ flip;
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) widen8(v[k], scale, u[2 * k], u[2 * k + 1]);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < L; ++k) u[k] = one(g + k);
+            }
+            f2 *dst = &lds[lds_slot(L * p)];
+#pragma unroll
+            for (int k = 0; k < L; k += 2)
+                *reinterpret_cast<f4 *>(dst + k) = f4{u[k].x, u[k].y, u[k + 1].x, u[k + 1].y};
+        }
+    } else {
+        for (int i = tid; i < NIN; i += NT) lds[lds_slot(i)] = one(g0 + i);
+    }
+}
+
 template <int T, int W, int Q, bool VEC, int NT, typename XT = f2>
 __global__ __launch_bounds__(NT) void fir_tile_kernel(typename fir_args<XT>::type a, const float *hrev) {
     constexpr int TILE = NT * Q;
@@ -296,7 +373,8 @@ __global__ __launch_bounds__(NT) void fir_tile_kernel(typename fir_args<XT>::typ
     }
 
     if constexpr (same_type<XT, f2>::value) fir_stage<T, NIN, VEC, NT>(lds, x, hist, tile0, n);
-    else fir_stage_cs16<T, NIN, VEC, NT>(lds, x, hist, tile0, n, x_scale(a));
+    else if constexpr (same_type<XT, s2>::value) fir_stage_cs16<T, NIN, VEC, NT>(lds, x, hist, tile0, n, x_scale(a));
+    else fir_stage_i8<T, NIN, VEC, NT>(lds, x, hist, tile0, n, x_scale(a), x_flip(a));
     __syncthreads();
     if (ph_wg) p1 = __builtin_amdgcn_s_memtime();
 
@@ -359,12 +437,19 @@ __global__ __launch_bounds__(NT) void fir_tile_kernel(typename fir_args<XT>::typ
                         return g < 0 ? hist[T - 1 + g] : x[g];
                     };
                     y[go] = fir_exact_one(xs, hrev, T, W);
-                } else {
+                } else if constexpr (same_type<XT, s2>::value) {
                     // CS16 rows: the history may hold a NaN or Inf of an earlier float call
                     const float scale = x_scale(a);
                     auto xs = [&](int k) -> f2 {
                         const int64_t g = w0 + k;
                         return g < 0 ? hist[T - 1 + g] : widen(x[g], scale);
+                    };
+                    y[go] = fir_exact_one(xs, hrev, T, W);
+                } else {
+                    // 8-bit rows, likewise
+                    auto xs = [&](int k) -> f2 {
+                        const int64_t g = w0 + k;
+                        return g < 0 ? hist[T - 1 + g] : load_xa(x, g, a);
                     };
                     y[go] = fir_exact_one(xs, hrev, T, W);
                 }
@@ -396,14 +481,14 @@ __global__ __launch_bounds__(256) void fir_generic_kernel(typename fir_args<XT>:
     const int64_t w0 = t - T + 1;
     auto xs = [&](int k) -> f2 {
         const int64_t g = w0 + k;
-        return g < 0 ? hist[T - 1 + g] : load_x(x, g, x_scale(a));
+        return g < 0 ? hist[T - 1 + g] : load_xa(x, g, a);
     };
     f2 *y = reinterpret_cast<f2 *>(a.y) + s * a.y_stride + a.y_offset;
     y[t] = fir_exact_one(xs, hrev, T, W);
 }
 
 // new_hist = last (T-1) samples of concat(old_hist, x[0..n)); the history is
-// float whatever the input format (CS16 samples enter it widened)
+// float whatever the input format (CS16 and 8-bit samples enter it widened)
 template <typename XT>
 __global__ void fir_hist_kernel(typename fir_args<XT>::type a, float *hist_new, int H, int S) {
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -415,7 +500,7 @@ __global__ void fir_hist_kernel(typename fir_args<XT>::type a, float *hist_new, 
     const f2 *ho = reinterpret_cast<const f2 *>(a.hist) + static_cast<int64_t>(s) * H;
     f2 *hn = reinterpret_cast<f2 *>(hist_new) + static_cast<int64_t>(s) * H;
     const int64_t m = n + k;
-    hn[k] = m < H ? ho[m] : load_x(x, m - H, x_scale(a));
+    hn[k] = m < H ? ho[m] : load_xa(x, m - H, a);
 }
 
 // ---------------------------------------------------------------------------
@@ -616,8 +701,47 @@ __global__ __launch_bounds__(256) void widen_kernel(WidenArgs a) {
     }
 }
 
-void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream) {
+// 8-bit rows: a 16-B load (8 samples) and four 16-B stores per thread where the
+// rows allow, 2-B loads and 8-B stores otherwise.
+template <bool VEC>
+__global__ __launch_bounds__(256) void widen8_kernel(WidenArgs a, unsigned flip) {
+    const int s = blockIdx.y;
+    const int64_t n = a.lengths ? a.lengths[s] : a.n;
+    const b2 *x = reinterpret_cast<const b2 *>(a.x) + s * a.x_stride;
+    f2 *y = reinterpret_cast<f2 *>(a.y) + s * a.y_stride + a.y_offset;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if constexpr (VEC) {
+        const int64_t g = 8 * i;
+        if (g + 7 < n) {
+            const u4 v = *reinterpret_cast<const u4 *>(x + g) ^ flip;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                f2 u0, u1;
+                widen8(v[k], a.scale, u0, u1);
+                *reinterpret_cast<f4 *>(y + g + 2 * k) = f4{u0.x, u0.y, u1.x, u1.y};
+            }
+        } else {
+            for (int64_t k = g; k < n; ++k) y[k] = widen(x[k], a.scale, flip);
+        }
+    } else {
+        if (i < n) y[i] = widen(x[i], a.scale, flip);
+    }
+}
+
+static unsigned flip_of(int32_t fmt) { return fmt == kFmtCs8 ? 0x80808080u : 0u; }
+
+void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream, int32_t x_fmt) {
     if (n_max <= 0 || S <= 0) return;
+    if (x_fmt == kFmtCs8 || x_fmt == kFmtCu8) {
+        const bool vec8 = ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.x_stride % 8 == 0) &&
+                          ((reinterpret_cast<uintptr_t>(a.y) & 15) == 0) && (a.y_stride % 2 == 0) &&
+                          (a.y_offset % 2 == 0);
+        const int64_t items = vec8 ? (n_max + 7) / 8 : n_max;
+        dim3 grid(static_cast<unsigned>((items + 255) / 256), static_cast<unsigned>(S));
+        if (vec8) hipLaunchKernelGGL(widen8_kernel<true>, grid, dim3(256), 0, stream, a, flip_of(x_fmt));
+        else hipLaunchKernelGGL(widen8_kernel<false>, grid, dim3(256), 0, stream, a, flip_of(x_fmt));
+        return;
+    }
     const bool vec = ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.x_stride % 4 == 0) &&
                      ((reinterpret_cast<uintptr_t>(a.y) & 15) == 0) && (a.y_stride % 2 == 0) &&
                      (a.y_offset % 2 == 0);
@@ -640,7 +764,7 @@ static void launch_fir_w8_nt(const typename fir_args<XT>::type &a, const float *
     constexpr int Q = 8;
     const int64_t tiles = (n_max + NT * Q - 1) / (NT * Q);
     dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(S));
-    constexpr bool kVecOk = same_type<XT, f2>::value || (T - 1) % 4 == 0;
+    constexpr bool kVecOk = same_type<XT, f2>::value || (T - 1) % 4 == 0;   // CS16 and 8-bit rows alike
     if constexpr (kVecOk) {
         if (vec) {
             hipLaunchKernelGGL((fir_tile_kernel<T, 8, Q, true, NT, XT>), grid, dim3(NT), 0, stream, a, hrev);
@@ -651,14 +775,15 @@ static void launch_fir_w8_nt(const typename fir_args<XT>::type &a, const float *
 }
 
 template <int T>
-static bool launch_fir_w8(const FirArgsCs16 &a, int32_t x_fmt, const float *hrev, int S,
+static bool launch_fir_w8(const FirArgsI8 &a, int32_t x_fmt, const float *hrev, int S,
                           int64_t n_max, bool vec, hipStream_t stream) {
     // 2048-output tiles; 1024- and 512-output tiles (128 / 64 threads, more
     // workgroups beside the loop kernel's) measured the same at C3 and C2
     // (pipelined bench, A/B x2 on one MI355X), and so did a
     // work-sharing tile whose waves take 512-output units from an LDS counter
     // (profiles/archive/r02_fir_share_ab.txt)
-    if (x_fmt == kFmtCs16) launch_fir_w8_nt<T, kFirThreads, s2>(a, hrev, S, n_max, vec, stream);
+    if (x_fmt == kFmtCs16) launch_fir_w8_nt<T, kFirThreads, s2>(static_cast<const FirArgsCs16 &>(a), hrev, S, n_max, vec, stream);
+    else if (x_fmt != kFmtCf32) launch_fir_w8_nt<T, kFirThreads, b2>(a, hrev, S, n_max, vec, stream);
     else launch_fir_w8_nt<T, kFirThreads, f2>(static_cast<const FirArgs &>(a), hrev, S, n_max, vec, stream);
     return true;
 }
@@ -667,10 +792,17 @@ bool launch_fir(const FirArgs &a0, const float *hrev_dev, int T, int W, int S,
                 int64_t n_max, hipStream_t stream, int32_t x_fmt, float x_scale) {
     if (n_max <= 0 || S <= 0) return true;
     const bool cs16 = x_fmt == kFmtCs16;
-    FirArgsCs16 a{};
+    const bool i8 = x_fmt == kFmtCs8 || x_fmt == kFmtCu8;
+    FirArgsI8 a{};
     static_cast<FirArgs &>(a) = a0;
     a.x_scale = x_scale;
-    const bool vec = cs16 ? (T % 4 == 1) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.x_stride % 4 == 0)
+    a.x_flip = flip_of(x_fmt);
+    // 8-bit rows: 16-B loads of 8 samples where T - 1 is a multiple of 8, else
+    // (T = 13, 21) 8-B loads of 4; the rows must be aligned to the load and
+    // keep that alignment from row to row
+    const int l8 = (T - 1) % 8 == 0 ? 8 : 4;
+    const bool vec = i8 ? (T % 4 == 1) && (reinterpret_cast<uintptr_t>(a.x) % (2 * l8) == 0) && (a.x_stride % l8 == 0)
+                     : cs16 ? (T % 4 == 1) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.x_stride % 4 == 0)
                           : (T % 2 == 1) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) &&
                                 (a.x_stride % 2 == 0) && ((reinterpret_cast<uintptr_t>(a.y) & 15) == 0) &&
                                 (a.y_stride % 2 == 0) && (a.y_offset % 2 == 0);
@@ -690,7 +822,10 @@ bool launch_fir(const FirArgs &a0, const float *hrev_dev, int T, int W, int S,
     }
     const int threads = 256;
     dim3 grid(static_cast<unsigned>((n_max + threads - 1) / threads), static_cast<unsigned>(S));
-    if (cs16) hipLaunchKernelGGL(fir_generic_kernel<s2>, grid, dim3(threads), 0, stream, a, hrev_dev, T, W);
+    if (cs16)
+        hipLaunchKernelGGL(fir_generic_kernel<s2>, grid, dim3(threads), 0, stream, static_cast<const FirArgsCs16 &>(a),
+                           hrev_dev, T, W);
+    else if (i8) hipLaunchKernelGGL(fir_generic_kernel<b2>, grid, dim3(threads), 0, stream, a, hrev_dev, T, W);
     else hipLaunchKernelGGL(fir_generic_kernel<f2>, grid, dim3(threads), 0, stream, a0, hrev_dev, T, W);
     return false;
 }
@@ -706,6 +841,12 @@ void launch_fir_hist(const FirArgs &a, float *hist_new, int H, int S, hipStream_
         static_cast<FirArgs &>(c) = a;
         c.x_scale = x_scale;
         hipLaunchKernelGGL(fir_hist_kernel<s2>, grid, dim3(threads), 0, stream, c, hist_new, H, S);
+    } else if (x_fmt == kFmtCs8 || x_fmt == kFmtCu8) {
+        FirArgsI8 c{};
+        static_cast<FirArgs &>(c) = a;
+        c.x_scale = x_scale;
+        c.x_flip = flip_of(x_fmt);
+        hipLaunchKernelGGL(fir_hist_kernel<b2>, grid, dim3(threads), 0, stream, c, hist_new, H, S);
     } else
         hipLaunchKernelGGL(fir_hist_kernel<f2>, grid, dim3(threads), 0, stream, a, hist_new, H, S);
 }

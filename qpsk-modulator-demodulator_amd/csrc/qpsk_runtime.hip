@@ -21,7 +21,9 @@
 // time axis contiguously):
 //   in      [S][n_max]              float2  staging for host input (CS16 calls:
 //                                           int16 pairs, rows of n_max rounded up to
-//                                           4 samples so they take 16-B loads)
+//                                           4 samples so they take 16-B loads;
+//                                           CS8 / CU8 calls: byte pairs, rows
+//                                           rounded up to 8 samples)
 //   fll_out [S][n_max]              float2  (FLL mode)
 //   hist    2 x [S][T-1]            float2  FIR delay line (ping-pong)
 //   mf      [2][S][256 + n_max]     float2  matched-filter output; the 256-slot
@@ -86,6 +88,10 @@ constexpr int64_t kMaxSamplesPerCall = int64_t(1) << 30;
 // the symbol loop keeps sample indices of one call in 32-bit integers
 constexpr int64_t kMaxCallSamples = (int64_t(1) << 31) - 129;
 static_assert(kFmtCf32 == 0, "CallArgs.fmt defaults to CF32");
+static_assert(QPSK_FMT_CF32 == kFmtCf32 && QPSK_FMT_CS16 == kFmtCs16 && QPSK_FMT_CS8 == kFmtCs8 &&
+                  QPSK_FMT_CU8 == kFmtCu8,
+              "the ABI's format tags are the kernels'");
+constexpr int kFmts = 4;
 
 struct Call : CallArgs {
     // internal chunk of a longer call: outputs appended to dst_* at the running
@@ -97,11 +103,23 @@ struct Call : CallArgs {
     int64_t dst_syms_stride = 0;
     int64_t *dst_n_bits = nullptr;   // device; written after the last chunk
     int64_t *dst_n_syms = nullptr;
-    // a CS16 call: the handle's scale when the call was issued
+    // an integer-format call: the handle's scale of that format when the call was issued
     float scale = 0.0f;
 };
 
-size_t elem_bytes(int32_t fmt) { return fmt == kFmtCs16 ? sizeof(int16_t) : sizeof(float); }
+bool fmt_known(int32_t fmt) { return fmt >= 0 && fmt < kFmts; }
+bool fmt_8bit(int32_t fmt) { return fmt == kFmtCs8 || fmt == kFmtCu8; }
+// bytes of one element of a row (two elements a sample)
+size_t elem_bytes(int32_t fmt) { return fmt == kFmtCf32 ? sizeof(float) : fmt == kFmtCs16 ? sizeof(int16_t) : 1; }
+// samples a staged host row's pitch is a multiple of, so that the staged rows
+// take the format's 16-byte loads whatever max_samples_per_call is
+int64_t stage_pitch(int32_t fmt, int64_t n_max) {
+    const int64_t m = fmt == kFmtCf32 ? 1 : fmt == kFmtCs16 ? 4 : 8;
+    return (n_max + m - 1) / m * m;
+}
+const char *fmt_name(int32_t fmt) {
+    return fmt == kFmtCs16 ? "CS16" : fmt == kFmtCs8 ? "CS8" : fmt == kFmtCu8 ? "CU8" : "CF32";
+}
 
 // The first stage's input rows: the caller's (or the staged) rows in the
 // call's own format, until a pre-stage has rewritten them as float rows.
@@ -131,7 +149,9 @@ struct qpsk_demod {
     float *d_hrev = nullptr;
     void *d_in = nullptr;            // host-input staging, in the call's format
     size_t in_bytes = 0;
-    float cs16_scale = 1.0f / 32768; // (float)int16 * scale; SoapySDR's CS16 -> CF32 convention
+    // per input format (CF32 has none): CS16 (float)int16 * scale, SoapySDR's
+    // CS16 -> CF32 convention; CS8 / CU8 full scale 128 (S8toF32, U8toS8)
+    float in_scale[kFmts] = {0.0f, 1.0f / 32768, 1.0f / 128, 1.0f / 128};
     float *d_fll_out[2] = {nullptr, nullptr};
     float *d_iqb = nullptr;          // [S][n_max] float2, IQ_Balancer output (iq_balance only)
     float *d_hist[2] = {nullptr, nullptr};
@@ -284,6 +304,7 @@ int qpsk::call_length(int S, int64_t n_samples, const int64_t *lengths, int64_t 
 }
 
 int qpsk::check_call(const qpsk_demod *h, int S, CallArgs &c) {
+    if (!fmt_known(c.fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
     if (c.mode != QPSK_MODE_DEMODULATE && c.mode != QPSK_MODE_CONSTELLATION)
         return fail(QPSK_ERR_ARGUMENT, "unknown mode");
     if (c.mem != QPSK_MEM_HOST && c.mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
@@ -304,10 +325,13 @@ int qpsk::check_call(const qpsk_demod *h, int S, CallArgs &c) {
     if (c.syms && c.syms_stride_floats < 2 * max_sym)
         return fail(QPSK_ERR_ARGUMENT, "syms_stride_floats smaller than 2*max_symbols");
     if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && (c.stride_floats & 1))
-        return fail(QPSK_ERR_ARGUMENT, c.fmt == kFmtCs16 ? "device stride_i16 must be even"
+        return fail(QPSK_ERR_ARGUMENT, c.fmt == kFmtCs16   ? "device stride_i16 must be even"
+                                       : fmt_8bit(c.fmt) ? "device stride_elems of 8-bit rows must be even"
                                                          : "device stride_floats must be even");
     if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && c.fmt == kFmtCs16 && (reinterpret_cast<uintptr_t>(c.iq) & 3))
         return fail(QPSK_ERR_ARGUMENT, "device CS16 rows must be 4-byte aligned");
+    if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && fmt_8bit(c.fmt) && (reinterpret_cast<uintptr_t>(c.iq) & 1))
+        return fail(QPSK_ERR_ARGUMENT, "device CS8 / CU8 rows must be 2-byte aligned");
     c.n_call = n_call;
     c.max_sym = max_sym;
     return QPSK_OK;
@@ -346,19 +370,19 @@ void run_fll(qpsk_demod *h, const float *x, int64_t x_stride, const int64_t *d_l
     launch_fll(fa, h->fp, st);
 }
 
-// CS16 rows ahead of a serial pre-stage (IQ balancer, FLL): widened into the
+// CS16 or 8-bit rows ahead of a serial pre-stage (IQ balancer, FLL): widened into the
 // call's own MF rows, which nothing reads until the matched filter, the last
 // stage in front of the loop, has rewritten them (DESIGN.md, CS16 input).
 // Float rows pass through.
 const float *float_rows(qpsk_demod *h, InRows *in, const int64_t *d_len, int64_t n_call, float *mf,
                         hipStream_t st) {
-    if (in->fmt == kFmtCs16) {
+    if (in->fmt != kFmtCf32) {
         WidenArgs wa{};
-        wa.x = static_cast<const int16_t *>(in->x); wa.x_stride = in->stride;
+        wa.x = in->x; wa.x_stride = in->stride;
         wa.y = mf; wa.y_stride = h->mf_stride; wa.y_offset = kMfPrefix;
         wa.lengths = d_len; wa.n = n_call;
         wa.scale = in->scale;
-        launch_widen(wa, h->S, n_call, st);
+        launch_widen(wa, h->S, n_call, st, in->fmt);
         *in = InRows{mf + 2 * kMfPrefix, h->mf_stride, kFmtCf32, 0.0f};
     }
     return static_cast<const float *>(in->x);
@@ -1003,9 +1027,10 @@ int process_one(qpsk_demod *h, const Call &c) {
     // ---- input -----------------------------------------------------------
     InRows in{c.iq, stride_floats / 2, c.fmt, c.scale};   // stride in samples
     if (n_call > 0 && mem == QPSK_MEM_HOST) {
-        // staged in the call's own format: a CS16 call uploads 4 bytes a sample
+        // staged in the call's own format: a CS16 call uploads 4 bytes a
+        // sample, a CS8 / CU8 call 2
         const size_t eb = elem_bytes(c.fmt);
-        const int64_t pitch = c.fmt == kFmtCs16 ? (h->n_max + 3) / 4 * 4 : h->n_max;   // samples
+        const int64_t pitch = stage_pitch(c.fmt, h->n_max);   // samples
         // the last host-memory call has returned, so nothing reads d_in
         if ((rc = ensure_bytes(&h->d_in, &h->in_bytes, static_cast<size_t>(S) * pitch * 2 * eb))) return rc;
         QPSK_HIP_TRY(hipMemcpy2DAsync(h->d_in, 2 * pitch * eb, c.iq, stride_floats * eb, 2 * n_call * eb, S,
@@ -1227,7 +1252,8 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
 // length and kind ask for.
 int submit(qpsk_demod *h, Call &c, bool pipelined) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    if (c.fmt == kFmtCs16) c.scale = h->cs16_scale;   // queued calls keep the scale they were issued with
+    if (!fmt_known(c.fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
+    c.scale = h->in_scale[c.fmt];   // queued calls keep the scale they were issued with
     int rc;
     if ((rc = check_call(h, h->S, c))) return rc;
     if (c.syms && (rc = ensure_syms(h))) return rc;
@@ -1259,18 +1285,50 @@ int qpsk_demod_process_async(qpsk_demod *h, int32_t mode, const float *iq, int64
     return submit(h, c, true);
 }
 
-int qpsk_demod_set_cs16_scale(qpsk_demod *h, float scale) {
+int qpsk_demod_set_input_scale(qpsk_demod *h, int32_t fmt, float scale) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    if (!fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
+    if (fmt == kFmtCf32) return fail(QPSK_ERR_ARGUMENT, "CF32 input has no scale");
     if (!std::isfinite(scale) || !(scale > 0.0f))
-        return fail(QPSK_ERR_OUT_OF_RANGE, "the CS16 scale must be finite and > 0");
-    h->cs16_scale = scale;   // calls issued from now on; queued ones carry their own
+        return fail(QPSK_ERR_OUT_OF_RANGE, std::string("the ") + fmt_name(fmt) + " scale must be finite and > 0");
+    h->in_scale[fmt] = scale;   // calls issued from now on; queued ones carry their own
     return QPSK_OK;
 }
 
-int qpsk_demod_get_cs16_scale(const qpsk_demod *h, float *scale) {
+int qpsk_demod_get_input_scale(const qpsk_demod *h, int32_t fmt, float *scale) {
     if (!h || !scale) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    *scale = h->cs16_scale;
+    if (!fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
+    if (fmt == kFmtCf32) return fail(QPSK_ERR_ARGUMENT, "CF32 input has no scale");
+    *scale = h->in_scale[fmt];
     return QPSK_OK;
+}
+
+int qpsk_demod_set_cs16_scale(qpsk_demod *h, float scale) { return qpsk_demod_set_input_scale(h, kFmtCs16, scale); }
+
+int qpsk_demod_get_cs16_scale(const qpsk_demod *h, float *scale) {
+    return qpsk_demod_get_input_scale(h, kFmtCs16, scale);
+}
+
+int qpsk_fmt_sample_bytes(int32_t fmt) {
+    return fmt_known(fmt) ? static_cast<int>(2 * elem_bytes(fmt)) : QPSK_ERR_ARGUMENT;
+}
+
+int qpsk_demod_process_fmt(qpsk_demod *h, int32_t fmt, int32_t mode, const void *iq, int64_t stride_elems,
+                           int64_t n_samples, const int64_t *lengths, int32_t mem, uint8_t *bits,
+                           int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                           int64_t syms_stride_floats, int64_t *n_syms) {
+    Call c{{mode, iq, stride_elems, n_samples, lengths, mem, bits, bits_stride_bytes, n_bits, syms,
+            syms_stride_floats, n_syms, fmt}};
+    return submit(h, c, false);
+}
+
+int qpsk_demod_process_async_fmt(qpsk_demod *h, int32_t fmt, int32_t mode, const void *iq, int64_t stride_elems,
+                                 int64_t n_samples, const int64_t *lengths, uint8_t *bits,
+                                 int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
+                                 int64_t syms_stride_floats, int64_t *n_syms) {
+    Call c{{mode, iq, stride_elems, n_samples, lengths, QPSK_MEM_DEVICE, bits, bits_stride_bytes, n_bits, syms,
+            syms_stride_floats, n_syms, fmt}};
+    return submit(h, c, true);
 }
 
 int qpsk_demod_process_cs16(qpsk_demod *h, int32_t mode, const int16_t *iq, int64_t stride_i16,

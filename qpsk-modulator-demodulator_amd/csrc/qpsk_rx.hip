@@ -20,7 +20,10 @@
 //
 // A CS16 ring (qpsk_rx_create_cs16) is the same ring with int16 slots: an SDR
 // driver's native CS16 buffers go up as they are, 4 bytes a sample, and the
-// matched filter widens them (qpsk_demod_process_async_cs16).
+// matched filter widens them (qpsk_demod_process_async_cs16).  A CS8 or CU8
+// ring (qpsk_rx_create_fmt) has byte slots, 2 bytes a sample; its device
+// slots' rows are pitched to 8 samples so the matched filter reads them with
+// 16-byte loads whatever max_samples_per_call is.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -34,8 +37,8 @@ namespace {
 using qpsk::fail;
 
 struct Slot {
-    void *h_in = nullptr;       // pinned [S][in_stride] floats, or int16 (CS16 ring)
-    void *d_in = nullptr;       // device, same layout
+    void *h_in = nullptr;       // pinned [S][in_stride] elements of the ring's format
+    void *d_in = nullptr;       // device [S][dev_stride]
     uint8_t *d_bits = nullptr;  // device [S][bits_stride]
     int64_t *d_nb = nullptr;    // device [S]
     uint8_t *h_bits = nullptr;  // pinned
@@ -51,8 +54,9 @@ struct qpsk_rx {
     int depth = 0;
     int S = 0;
     int64_t n_max = 0;
-    int64_t in_stride = 0;      // elements (floats, or int16): 2 * n_max
-    bool cs16 = false;
+    int64_t in_stride = 0;      // elements (floats, int16 or bytes): 2 * n_max
+    int64_t dev_stride = 0;     // elements of a device slot's row (8-bit: n_max rounded up to 8 samples)
+    int32_t fmt = QPSK_FMT_CF32;
     size_t elem = sizeof(float);   // bytes per element of a slot
     int64_t bits_stride = 0;    // bytes
     int device = 0;
@@ -84,13 +88,14 @@ int setup(qpsk_rx *r) {
     QPSK_HIP_TRY(hipStreamCreateWithFlags(&r->down, hipStreamNonBlocking));
     const size_t S = static_cast<size_t>(r->S);
     const size_t in_bytes = S * static_cast<size_t>(r->in_stride) * r->elem;
+    const size_t dev_bytes = S * static_cast<size_t>(r->dev_stride) * r->elem;
     const size_t bit_bytes = S * static_cast<size_t>(r->bits_stride);
     r->slots.resize(r->depth);
     for (auto &s : r->slots) {
         QPSK_HIP_TRY(hipHostMalloc(&s.h_in, in_bytes));
         QPSK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_bits), bit_bytes));
         QPSK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_nb), S * sizeof(int64_t)));
-        QPSK_HIP_TRY(hipMalloc(&s.d_in, in_bytes));
+        QPSK_HIP_TRY(hipMalloc(&s.d_in, dev_bytes));
         QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_bits), bit_bytes));
         QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_nb), S * sizeof(int64_t)));
         QPSK_HIP_TRY(hipEventCreateWithFlags(&s.in_free, hipEventDisableTiming));
@@ -99,9 +104,13 @@ int setup(qpsk_rx *r) {
     return QPSK_OK;
 }
 
-int create(qpsk_demod *h, int32_t depth, bool cs16, qpsk_rx **out) {
+const char *kUnknownFormat = "unknown sample format";
+
+int create(qpsk_demod *h, int32_t depth, int32_t fmt, qpsk_rx **out) {
     if (!h || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     *out = nullptr;
+    const int sample_bytes = qpsk_fmt_sample_bytes(fmt);
+    if (sample_bytes < 0) return fail(QPSK_ERR_ARGUMENT, kUnknownFormat);
     if (depth < 2 || depth > 8) return fail(QPSK_ERR_ARGUMENT, "depth must be 2..8");
     qpsk_rx *r = new qpsk_rx;
     r->h = h;
@@ -110,8 +119,9 @@ int create(qpsk_demod *h, int32_t depth, bool cs16, qpsk_rx **out) {
     r->n_max = qpsk::handle_max_samples(h);
     r->device = qpsk::handle_device(h);
     r->in_stride = 2 * r->n_max;
-    r->cs16 = cs16;
-    r->elem = cs16 ? sizeof(int16_t) : sizeof(float);
+    r->fmt = fmt;
+    r->elem = static_cast<size_t>(sample_bytes) / 2;
+    r->dev_stride = r->elem == 1 ? 2 * ((r->n_max + 7) / 8 * 8) : r->in_stride;
     r->bits_stride = ((2 * qpsk_demod_max_symbols(h, r->n_max) + 7) / 8 + 15) / 16 * 16;
     int rc = setup(r);
     if (rc == QPSK_OK) rc = qpsk_demod_set_stream(h, r->up);
@@ -123,11 +133,18 @@ int create(qpsk_demod *h, int32_t depth, bool cs16, qpsk_rx **out) {
     return QPSK_OK;
 }
 
-const char *kWrongFormat = "the ring was created for the other sample format (CF32 / CS16)";
+// a ring has one format; between the two formats of the untagged entry points
+// the text names them
+int wrong_format(int32_t ring_fmt, int32_t fmt) {
+    const bool pair = ring_fmt <= QPSK_FMT_CS16 && fmt <= QPSK_FMT_CS16;
+    return fail(QPSK_ERR_STATE, pair ? "the ring was created for the other sample format (CF32 / CS16)"
+                                     : "the ring was created for another sample format");
+}
 
-int next_slot(qpsk_rx *r, bool cs16, void **iq, int64_t *stride_floats) {
+int next_slot(qpsk_rx *r, int32_t fmt, void **iq, int64_t *stride_floats) {
     if (!r || !iq) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    if (r->cs16 != cs16) return fail(QPSK_ERR_STATE, kWrongFormat);
+    if (qpsk_fmt_sample_bytes(fmt) < 0) return fail(QPSK_ERR_ARGUMENT, kUnknownFormat);
+    if (r->fmt != fmt) return wrong_format(r->fmt, fmt);
     if (r->submitted - r->collected >= r->depth)
         return fail(QPSK_ERR_STATE, "every ring slot holds an uncollected chunk");
     Slot &sl = r->slots[r->submitted % r->depth];
@@ -138,10 +155,11 @@ int next_slot(qpsk_rx *r, bool cs16, void **iq, int64_t *stride_floats) {
     return QPSK_OK;
 }
 
-int submit(qpsk_rx *r, bool cs16, const void *iq, int64_t stride_floats, int64_t n_samples,
+int submit(qpsk_rx *r, int32_t fmt, const void *iq, int64_t stride_floats, int64_t n_samples,
            const int64_t *lengths, int64_t *ticket) {
     if (!r) return fail(QPSK_ERR_ARGUMENT_NULL, "null ring");
-    if (r->cs16 != cs16) return fail(QPSK_ERR_STATE, kWrongFormat);
+    if (qpsk_fmt_sample_bytes(fmt) < 0) return fail(QPSK_ERR_ARGUMENT, kUnknownFormat);
+    if (r->fmt != fmt) return wrong_format(r->fmt, fmt);
     if (r->submitted - r->collected >= r->depth)
         return fail(QPSK_ERR_STATE, "every ring slot holds an uncollected chunk");
     const int S = r->S;
@@ -155,7 +173,7 @@ int submit(qpsk_rx *r, bool cs16, const void *iq, int64_t stride_floats, int64_t
     // the call as the handle will see it, but on the caller's host rows (which
     // no rule asks the sample format of)
     qpsk::CallArgs c{QPSK_MODE_DEMODULATE, iq, stride_floats, n_samples, lengths, QPSK_MEM_HOST,
-                     sl.d_bits, r->bits_stride, sl.d_nb, nullptr, 0, nullptr};
+                     sl.d_bits, r->bits_stride, sl.d_nb, nullptr, 0, nullptr, fmt};
     if ((rc = qpsk::check_call(r->h, S, c))) return rc;
     QPSK_HIP_TRY(hipSetDevice(r->device));
     // the slot's previous chunk: its input was consumed (front stage) and its
@@ -174,14 +192,10 @@ int submit(qpsk_rx *r, bool cs16, const void *iq, int64_t stride_floats, int64_t
     }
     if (sl.out_rec) QPSK_HIP_TRY(hipStreamWaitEvent(r->up, sl.out_done, 0));
     if (n_call > 0)
-        QPSK_HIP_TRY(hipMemcpy2DAsync(sl.d_in, r->in_stride * r->elem, sl.h_in, r->in_stride * r->elem,
+        QPSK_HIP_TRY(hipMemcpy2DAsync(sl.d_in, r->dev_stride * r->elem, sl.h_in, r->in_stride * r->elem,
                                       2 * n_call * r->elem, S, hipMemcpyHostToDevice, r->up));
-    rc = cs16 ? qpsk_demod_process_async_cs16(r->h, QPSK_MODE_DEMODULATE, static_cast<const int16_t *>(sl.d_in),
-                                                  r->in_stride, n_samples, lengths, sl.d_bits, r->bits_stride,
-                                                  sl.d_nb, nullptr, 0, nullptr)
-              : qpsk_demod_process_async(r->h, QPSK_MODE_DEMODULATE, static_cast<const float *>(sl.d_in),
-                                         r->in_stride, n_samples, lengths, sl.d_bits, r->bits_stride, sl.d_nb,
-                                         nullptr, 0, nullptr);
+    rc = qpsk_demod_process_async_fmt(r->h, fmt, QPSK_MODE_DEMODULATE, sl.d_in, r->dev_stride, n_samples, lengths,
+                                      sl.d_bits, r->bits_stride, sl.d_nb, nullptr, 0, nullptr);
     if (rc != QPSK_OK) return rc;
     QPSK_HIP_TRY(hipEventRecord(sl.in_free, qpsk::pipe_front_stream(r->h)));
     sl.in_rec = true;
@@ -202,23 +216,31 @@ int submit(qpsk_rx *r, bool cs16, const void *iq, int64_t stride_floats, int64_t
 
 extern "C" {
 
-int qpsk_rx_create(qpsk_demod *h, int32_t depth, qpsk_rx **out) { return create(h, depth, false, out); }
-int qpsk_rx_create_cs16(qpsk_demod *h, int32_t depth, qpsk_rx **out) { return create(h, depth, true, out); }
+int qpsk_rx_create(qpsk_demod *h, int32_t depth, qpsk_rx **out) { return create(h, depth, QPSK_FMT_CF32, out); }
+int qpsk_rx_create_cs16(qpsk_demod *h, int32_t depth, qpsk_rx **out) { return create(h, depth, QPSK_FMT_CS16, out); }
+int qpsk_rx_create_fmt(qpsk_demod *h, int32_t depth, int32_t fmt, qpsk_rx **out) { return create(h, depth, fmt, out); }
 
 int qpsk_rx_next_slot(qpsk_rx *r, float **iq, int64_t *stride_floats) {
-    return next_slot(r, false, reinterpret_cast<void **>(iq), stride_floats);
+    return next_slot(r, QPSK_FMT_CF32, reinterpret_cast<void **>(iq), stride_floats);
 }
 int qpsk_rx_next_slot_cs16(qpsk_rx *r, int16_t **iq, int64_t *stride_i16) {
-    return next_slot(r, true, reinterpret_cast<void **>(iq), stride_i16);
+    return next_slot(r, QPSK_FMT_CS16, reinterpret_cast<void **>(iq), stride_i16);
+}
+int qpsk_rx_next_slot_fmt(qpsk_rx *r, int32_t fmt, void **iq, int64_t *stride_elems) {
+    return next_slot(r, fmt, iq, stride_elems);
 }
 
 int qpsk_rx_submit(qpsk_rx *r, const float *iq, int64_t stride_floats, int64_t n_samples,
                    const int64_t *lengths, int64_t *ticket) {
-    return submit(r, false, iq, stride_floats, n_samples, lengths, ticket);
+    return submit(r, QPSK_FMT_CF32, iq, stride_floats, n_samples, lengths, ticket);
 }
 int qpsk_rx_submit_cs16(qpsk_rx *r, const int16_t *iq, int64_t stride_i16, int64_t n_samples,
                         const int64_t *lengths, int64_t *ticket) {
-    return submit(r, true, iq, stride_i16, n_samples, lengths, ticket);
+    return submit(r, QPSK_FMT_CS16, iq, stride_i16, n_samples, lengths, ticket);
+}
+int qpsk_rx_submit_fmt(qpsk_rx *r, int32_t fmt, const void *iq, int64_t stride_elems, int64_t n_samples,
+                       const int64_t *lengths, int64_t *ticket) {
+    return submit(r, fmt, iq, stride_elems, n_samples, lengths, ticket);
 }
 
 int qpsk_rx_destroy(qpsk_rx *r) {

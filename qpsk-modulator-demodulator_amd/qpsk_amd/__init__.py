@@ -44,6 +44,29 @@ MODE_CONSTELLATION = 1
 COSTAS_TRIG_PORTABLE = 0      # table sincos, within 1 ulp of glibc (default, faster)
 COSTAS_TRIG_GLIBC = 1         # glibc's own sin/cos: symbols bit-identical to the libm oracle
 
+# sample formats of the *_fmt entry points (QPSK_FMT_*)
+FMT_CF32 = 0
+FMT_CS16 = 1
+FMT_CS8 = 2
+FMT_CU8 = 3
+# name -> (QPSK_FMT_*, numpy dtype of a row's elements, ctypes type)
+_FORMATS = {"cf32": (FMT_CF32, np.float32, C.c_float), "cs16": (FMT_CS16, np.int16, C.c_int16),
+            "cs8": (FMT_CS8, np.int8, C.c_int8), "cu8": (FMT_CU8, np.uint8, C.c_uint8)}
+
+
+def _format(fmt):
+    """(QPSK_FMT_*, numpy dtype, ctypes type) of a format name or tag."""
+    for name, rec in _FORMATS.items():
+        if fmt == name or (not isinstance(fmt, str) and fmt == rec[0]):
+            return rec
+    raise ValueError("fmt must be 'cf32', 'cs16', 'cs8' or 'cu8'")
+
+
+def fmt_sample_bytes(fmt: int) -> int:
+    """Bytes of one complex sample of QPSK_FMT_* fmt, negative if unknown (needs no device)."""
+    return int(lib().qpsk_fmt_sample_bytes(int(fmt)))
+
+
 _i64p = C.POINTER(C.c_int64)
 _u8p = C.POINTER(C.c_uint8)
 _f32p = C.POINTER(C.c_float)
@@ -169,6 +192,12 @@ def lib():
     L.qpsk_demod_process_async_cs16.argtypes = L.qpsk_demod_process_async.argtypes
     L.qpsk_demod_set_cs16_scale.argtypes = [C.c_void_p, C.c_float]
     L.qpsk_demod_get_cs16_scale.argtypes = [C.c_void_p, _f32p]
+    # format-tagged entry points: fmt in front of the float ones' arguments
+    L.qpsk_fmt_sample_bytes.argtypes = [C.c_int32]
+    L.qpsk_demod_process_fmt.argtypes = [C.c_void_p, C.c_int32] + L.qpsk_demod_process.argtypes[1:]
+    L.qpsk_demod_process_async_fmt.argtypes = [C.c_void_p, C.c_int32] + L.qpsk_demod_process_async.argtypes[1:]
+    L.qpsk_demod_set_input_scale.argtypes = [C.c_void_p, C.c_int32, C.c_float]
+    L.qpsk_demod_get_input_scale.argtypes = [C.c_void_p, C.c_int32, _f32p]
     L.qpsk_demod_pipeline_wait.argtypes = [C.c_void_p, C.c_void_p]
     L.qpsk_demod_status.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.qpsk_demod_last_mf.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]
@@ -236,6 +265,9 @@ def lib():
     L.qpsk_rx_create_cs16.argtypes = L.qpsk_rx_create.argtypes
     L.qpsk_rx_next_slot_cs16.argtypes = L.qpsk_rx_next_slot.argtypes
     L.qpsk_rx_submit_cs16.argtypes = L.qpsk_rx_submit.argtypes
+    L.qpsk_rx_create_fmt.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.qpsk_rx_next_slot_fmt.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.qpsk_rx_submit_fmt.argtypes = [C.c_void_p, C.c_int32] + L.qpsk_rx_submit.argtypes[1:]
     L.qpsk_shard_streams.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32)]
     L.qpsk_demod_group_create.argtypes = [C.POINTER(DemodParams), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
@@ -247,6 +279,7 @@ def lib():
     L.qpsk_demod_group_process.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                            _i64p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.c_void_p]
+    L.qpsk_demod_group_process_fmt.argtypes = [C.c_void_p, C.c_int32] + L.qpsk_demod_group_process.argtypes[1:]
     L.qpsk_demod_group_state_bytes.argtypes = [C.c_void_p, C.c_int32]
     L.qpsk_demod_group_state_bytes.restype = C.c_int64
     L.qpsk_demod_group_get_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
@@ -279,6 +312,9 @@ EXPORTED_SYMBOLS = [
     "qpsk_demod_group_get_state", "qpsk_demod_group_set_state",
     "qpsk_demod_set_cs16_scale", "qpsk_demod_get_cs16_scale", "qpsk_demod_process_cs16",
     "qpsk_demod_process_async_cs16", "qpsk_rx_create_cs16", "qpsk_rx_next_slot_cs16", "qpsk_rx_submit_cs16",
+    "qpsk_fmt_sample_bytes", "qpsk_demod_process_fmt", "qpsk_demod_process_async_fmt",
+    "qpsk_demod_set_input_scale", "qpsk_demod_get_input_scale", "qpsk_rx_create_fmt", "qpsk_rx_next_slot_fmt",
+    "qpsk_rx_submit_fmt", "qpsk_demod_group_process_fmt",
 ]
 
 _EXC = {
@@ -501,18 +537,57 @@ class BatchDemodulator:
                             syms_dev=None, n_syms_dev=None, lengths=None):
         """process_device() on an int16 [S, >= 2n] torch CUDA tensor; lengths:
         optional host int64 array of per-stream sample counts."""
-        self._device_call(lib().qpsk_demod_process_cs16, True, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev,
+        self._device_call(lib().qpsk_demod_process_cs16, FMT_CS16, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev,
                           n_syms_dev, lengths, False)
 
     def process_device_async_cs16(self, iq_dev, n, bits_dev, n_bits_dev, mode=MODE_DEMODULATE,
                                   syms_dev=None, n_syms_dev=None, lengths=None):
         """process_device_async() on an int16 [S, >= 2n] torch CUDA tensor."""
-        self._device_call(lib().qpsk_demod_process_async_cs16, True, iq_dev, n, bits_dev, n_bits_dev, mode,
+        self._device_call(lib().qpsk_demod_process_async_cs16, FMT_CS16, iq_dev, n, bits_dev, n_bits_dev, mode,
                           syms_dev, n_syms_dev, lengths, True)
 
-    def _device_call(self, fn, cs16, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev, n_syms_dev, lengths,
+    # ---- any format (CF32, CS16, CS8, CU8) through the *_fmt entry points --
+    def set_input_scale(self, fmt, scale: float):
+        """The scale of an integer format ("cs16": the one set_cs16_scale sets;
+        "cs8" / "cu8": default 1 / 128); applies to calls issued from now on.
+        Finite and > 0, else ValueError; "cf32" has none (ValueError)."""
+        _check(lib().qpsk_demod_set_input_scale(self._h, _format(fmt)[0], C.c_float(float(np.float32(scale)))))
+
+    def input_scale(self, fmt) -> float:
+        v = C.c_float()
+        _check(lib().qpsk_demod_get_input_scale(self._h, _format(fmt)[0], C.byref(v)))
+        return float(v.value)
+
+    def process_fmt(self, iq: np.ndarray, fmt, mode=MODE_DEMODULATE, lengths=None, want_syms=False):
+        """process() on an [S, 2n] host array of the format's element type
+        (float32, int16, int8 for "cs8", uint8 for "cu8"); any other dtype
+        raises: nothing is converted on the way."""
+        tag, dtype, _ = _format(fmt)
+        if np.asarray(iq).dtype != dtype:
+            raise ValueError(f"process_fmt({fmt!r}) takes {np.dtype(dtype).name} samples")
+        fn = lib().qpsk_demod_process_fmt
+        return self._process_host(lambda h, *a: fn(h, tag, *a), np.ascontiguousarray(iq), mode, lengths, want_syms)
+
+    def process_device_fmt(self, iq_dev, n, bits_dev, n_bits_dev, fmt, mode=MODE_DEMODULATE,
+                           syms_dev=None, n_syms_dev=None, lengths=None):
+        """process_device() on an [S, >= 2n] torch CUDA tensor of the format's
+        element type; lengths: optional host int64 array of per-stream counts."""
+        tag = _format(fmt)[0]
+        fn = lib().qpsk_demod_process_fmt
+        self._device_call(lambda h, *a: fn(h, tag, *a), tag, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev,
+                          n_syms_dev, lengths, False)
+
+    def process_device_async_fmt(self, iq_dev, n, bits_dev, n_bits_dev, fmt, mode=MODE_DEMODULATE,
+                                 syms_dev=None, n_syms_dev=None, lengths=None):
+        """process_device_async() on a tensor of the format's element type."""
+        tag = _format(fmt)[0]
+        fn = lib().qpsk_demod_process_async_fmt
+        self._device_call(lambda h, *a: fn(h, tag, *a), tag, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev,
+                          n_syms_dev, lengths, True)
+
+    def _device_call(self, fn, fmt, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev, n_syms_dev, lengths,
                      is_async):
-        self._check_device_args(iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev, cs16=cs16)
+        self._check_device_args(iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev, fmt=int(fmt))
         self._after_torch(iq_dev)
         bstride = bits_dev.stride(0) * bits_dev.element_size() if bits_dev is not None else 0
         sstride = syms_dev.stride(0) if syms_dev is not None else 0
@@ -564,9 +639,9 @@ class BatchDemodulator:
         return bits, n_bits, syms, n_syms
 
     # ---- device path (torch tensors resident in HBM) ---------------------
-    def _check_device_args(self, iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev, cs16=False):
+    def _check_device_args(self, iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev, fmt=FMT_CF32):
         import torch
-        want = torch.int16 if cs16 else torch.float32
+        want = {FMT_CF32: torch.float32, FMT_CS16: torch.int16, FMT_CS8: torch.int8, FMT_CU8: torch.uint8}[fmt]
         if iq_dev.dtype != want or iq_dev.dim() != 2 or iq_dev.shape[0] != self.S:
             raise ValueError(f"iq_dev must be a {want} [n_streams, >= 2n] tensor")
         if iq_dev.stride(1) != 1 or iq_dev.shape[1] < 2 * int(n):
@@ -687,7 +762,19 @@ class DemodGroup:
     def process(self, iq: np.ndarray, mode=MODE_DEMODULATE, lengths=None, want_syms=False):
         """iq: [S, 2n] float32 host rows of the whole batch; returns (bits,
         n_bits, syms or None, n_syms) exactly as BatchDemodulator.process."""
-        iq = np.ascontiguousarray(iq, dtype=np.float32)
+        return self._process_host(lib().qpsk_demod_group_process, np.ascontiguousarray(iq, dtype=np.float32), mode,
+                                  lengths, want_syms)
+
+    def process_fmt(self, iq: np.ndarray, fmt, mode=MODE_DEMODULATE, lengths=None, want_syms=False):
+        """process() on host rows of any format (qpsk_demod_group_process_fmt):
+        [S, 2n] of the format's element type, nothing converted on the way."""
+        tag, dtype, _ = _format(fmt)
+        if np.asarray(iq).dtype != dtype:
+            raise ValueError(f"process_fmt({fmt!r}) takes {np.dtype(dtype).name} samples")
+        fn = lib().qpsk_demod_group_process_fmt
+        return self._process_host(lambda g, *a: fn(g, tag, *a), np.ascontiguousarray(iq), mode, lengths, want_syms)
+
+    def _process_host(self, fn, iq, mode, lengths, want_syms):
         if iq.ndim != 2 or iq.shape[0] != self.S or iq.shape[1] & 1:
             raise ValueError("iq must be [n_streams, 2*n]")
         n = iq.shape[1] // 2
@@ -702,7 +789,7 @@ class DemodGroup:
         n_bits = np.zeros(self.S, dtype=np.int64)
         n_syms = np.zeros(self.S, dtype=np.int64)
         syms = np.zeros((self.S, 2 * ms), dtype=np.float32) if (want_syms or mode == MODE_CONSTELLATION) else None
-        _check(lib().qpsk_demod_group_process(
+        _check(fn(
             self._g, int(mode), iq.ctypes.data if iq.size else None, iq.shape[1], n,
             lengths.ctypes.data_as(_i64p) if lengths is not None else None, MEM_HOST,
             bits.ctypes.data if mode == MODE_DEMODULATE else None, bstride,
@@ -715,11 +802,28 @@ class DemodGroup:
         """Device rows of the whole batch (every shard on one device): returns
         with the outputs written.  The shards run on their handles' own
         streams, so the call first waits for torch's current stream."""
+        self._process_device(lib().qpsk_demod_group_process, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev,
+                             n_syms_dev)
+
+    def process_device_fmt(self, iq_dev, n, bits_dev, n_bits_dev, fmt, mode=MODE_DEMODULATE, syms_dev=None,
+                           n_syms_dev=None):
+        """process_device() on device rows of any format (a tensor of the
+        format's element type)."""
+        import torch
+        tag = _format(fmt)[0]
+        want = {FMT_CF32: torch.float32, FMT_CS16: torch.int16, FMT_CS8: torch.int8, FMT_CU8: torch.uint8}[tag]
+        if iq_dev.dtype != want:
+            raise ValueError(f"process_device_fmt({fmt!r}) takes a {want} tensor")
+        fn = lib().qpsk_demod_group_process_fmt
+        self._process_device(lambda g, *a: fn(g, tag, *a), iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev,
+                             n_syms_dev)
+
+    def _process_device(self, fn, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev, n_syms_dev):
         import torch
         torch.cuda.current_stream(iq_dev.device).synchronize()
         bstride = bits_dev.stride(0) * bits_dev.element_size() if bits_dev is not None else 0
         sstride = syms_dev.stride(0) if syms_dev is not None else 0
-        _check(lib().qpsk_demod_group_process(
+        _check(fn(
             self._g, int(mode), iq_dev.data_ptr(), iq_dev.stride(0), int(n), None, MEM_DEVICE,
             bits_dev.data_ptr() if bits_dev is not None else None, bstride,
             n_bits_dev.data_ptr() if n_bits_dev is not None else None,
@@ -734,20 +838,29 @@ class HostRing:
     handle must not be used directly while the ring lives."""
 
     def __init__(self, demod: "BatchDemodulator", depth: int = 2, fmt: str = "cf32"):
-        """fmt "cf32": float32 slots; "cs16": int16 slots (qpsk_rx_*_cs16), half
-        the pinned memory and upload bytes, widened by the matched filter."""
+        """fmt "cf32": float32 slots; "cs16": int16 slots, half the pinned memory
+        and upload bytes, widened by the matched filter."""
         if fmt not in ("cf32", "cs16"):
-            raise ValueError("fmt must be 'cf32' or 'cs16'")
+            raise ValueError("fmt must be 'cf32' or 'cs16' (HostRing.create_fmt makes a ring of any format)")
+        self._open(demod, depth, fmt)
+
+    @classmethod
+    def create_fmt(cls, demod: "BatchDemodulator", depth: int = 2, fmt: str = "cs8") -> "HostRing":
+        """A ring of any one format: "cs8" (int8 slots) and "cu8" (uint8 slots)
+        are a quarter of the float ring's pinned memory and upload bytes; "cf32"
+        and "cs16" are the constructor's rings."""
+        ring = cls.__new__(cls)
+        ring._open(demod, depth, fmt)
+        return ring
+
+    def _open(self, demod, depth, fmt):
+        """Every ring goes through qpsk_rx_create_fmt / _next_slot_fmt / _submit_fmt."""
+        self._r = C.c_void_p()
+        self._tag, self._dtype, self._ctype = _format(fmt)
+        self.fmt = next(k for k, v in _FORMATS.items() if v[0] == self._tag)
         self._demod = demod
         self.S = demod.S
-        self.fmt = fmt
-        cs16 = fmt == "cs16"
-        self._dtype, self._ctype = (np.int16, C.c_int16) if cs16 else (np.float32, C.c_float)
-        L = lib()
-        self._next_slot = L.qpsk_rx_next_slot_cs16 if cs16 else L.qpsk_rx_next_slot
-        self._submit = L.qpsk_rx_submit_cs16 if cs16 else L.qpsk_rx_submit
-        self._r = C.c_void_p()
-        _check((L.qpsk_rx_create_cs16 if cs16 else L.qpsk_rx_create)(demod._h, int(depth), C.byref(self._r)))
+        _check(lib().qpsk_rx_create_fmt(demod._h, int(depth), self._tag, C.byref(self._r)))
         ms = demod.max_symbols(int(demod.p.max_samples_per_call))
         self.bits_stride = (2 * ms + 7) // 8
 
@@ -755,7 +868,7 @@ class HostRing:
         """The pinned slot the next submit reads, as a writable (S, stride) view
         of the ring's sample type (float32, or int16 for a CS16 ring)."""
         ptr, stride = C.c_void_p(), C.c_int64()
-        _check(self._next_slot(self._r, C.byref(ptr), C.byref(stride)))
+        _check(lib().qpsk_rx_next_slot_fmt(self._r, self._tag, C.byref(ptr), C.byref(stride)))
         buf = (self._ctype * (self.S * stride.value)).from_address(ptr.value)
         return np.ctypeslib.as_array(buf).reshape(self.S, stride.value)
 
@@ -766,8 +879,8 @@ class HostRing:
             slot = self.next_slot()
             ptr, stride = slot.ctypes.data, slot.shape[1]
         else:
-            if self.fmt == "cs16" and np.asarray(iq).dtype != np.int16:
-                raise ValueError("a CS16 ring takes int16 samples")
+            if self.fmt != "cf32" and np.asarray(iq).dtype != self._dtype:
+                raise ValueError(f"a {self.fmt.upper()} ring takes {np.dtype(self._dtype).name} samples")
             iq = np.ascontiguousarray(iq, dtype=self._dtype)
             assert iq.shape[0] == self.S
             ptr, stride = iq.ctypes.data, iq.shape[1]
@@ -775,8 +888,8 @@ class HostRing:
             n = stride // 2
         lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
         t = C.c_int64()
-        _check(self._submit(self._r, C.c_void_p(ptr), int(stride), int(n),
-                            lens.ctypes.data_as(_i64p) if lens is not None else None, C.byref(t)))
+        _check(lib().qpsk_rx_submit_fmt(self._r, self._tag, C.c_void_p(ptr), int(stride), int(n),
+                                        lens.ctypes.data_as(_i64p) if lens is not None else None, C.byref(t)))
         return t.value
 
     def collect(self):
@@ -789,7 +902,7 @@ class HostRing:
         return bits, nb, t.value
 
     def close(self):
-        if self._r:
+        if getattr(self, "_r", None):
             _check(lib().qpsk_rx_destroy(self._r))
             self._r = C.c_void_p()
 
