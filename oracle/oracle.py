@@ -91,6 +91,7 @@ def lib():
         L.or_fll_taps.argtypes = [C.c_void_p, _f32p, _f32p, C.c_int]
         L.or_fll_taps.restype = C.c_int
         L.or_fll_state.argtypes = [C.c_void_p, _f32p, _f32p]
+        L.or_fll_set_state.argtypes = [C.c_void_p, C.c_float, C.c_float]
         L.or_demod_cfg_default.argtypes = [C.POINTER(DemodCfg), C.c_int, C.c_int]
         L.or_demod_new.argtypes = [C.POINTER(DemodCfg), C.POINTER(C.c_int)]
         L.or_demod_new.restype = C.c_void_p
@@ -225,6 +226,13 @@ class OracleFLL:
         p, f = C.c_float(), C.c_float()
         lib().or_fll_state(self._h, C.byref(p), C.byref(f))
         return p.value, f.value
+
+    def set_state(self, phase, freq):
+        """Tests only (the reference has no setter): the loop's phase and
+        frequency as a restored state blob sets the kernel's.  The values cross
+        as float32 bit patterns in a C float argument (NaN payloads may not
+        survive; the tests compare NaN as NaN)."""
+        lib().or_fll_set_state(self._h, C.c_float(float(phase)), C.c_float(float(freq)))
 
     def __del__(self):
         if getattr(self, "_h", None):

@@ -515,6 +515,14 @@ void or_fll_state(const or_fll *f, float *phase, float *freq)
     *freq = f->freq;
 }
 
+/* Test infrastructure: the reference has no setter; this puts the loop where a
+ * restored state blob puts the kernel's (the delay line stays as it is). */
+void or_fll_set_state(or_fll *f, float phase, float freq)
+{
+    f->phase = phase;
+    f->freq = freq;
+}
+
 /* :102-129 Process(sample) */
 static inline void fll_sample(or_fll *f, float in_i, float in_q, float *out_i, float *out_q)
 {

@@ -58,6 +58,7 @@ void or_fll_free(or_fll *f);
 void or_fll_process(or_fll *f, const float *in_iq, float *out_iq, long n_complex);
 int or_fll_taps(const or_fll *f, float *lower_iq, float *upper_iq, int cap_floats);
 void or_fll_state(const or_fll *f, float *phase, float *freq);
+void or_fll_set_state(or_fll *f, float phase, float freq);   /* tests only: no reference counterpart */
 
 /* QPSKDeModulator.cs:11-457 */
 /* IQ_Balancer (IQ Balancer.cs:10-26): a DC blocker, exponential averages of I

@@ -288,8 +288,10 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
     // put there).  EXACT: the IEEERemainder wrap (:185-189) behind a vote and the
     // frequency clamp (:191-195).  Without EXACT the step tracks max |phase| and
     // max |freq| instead, and the block is redone exactly if either left its
-    // range (the phase every ~2pi/|freq| samples, the clamp essentially never),
-    // so a block is branch-free straight-line code.
+    // range (the phase every ~2pi/|freq| samples; the clamp never on a
+    // unit-amplitude signal, at most samples from amplitude ~1e3 on: DESIGN
+    // "Which inputs live in the redo"), so a block is branch-free straight-line
+    // code.
     // REG: a uniform block's step -- the partial sums read the block's register
     // window X (x[t0-32 .. t0-1]; x[t0] is this block's first output, xmv[0])
     // and the outputs stay in xmv until the block writes them to the ring at its

@@ -328,7 +328,16 @@ __global__ void __launch_bounds__(kFrThreads) framer_push_kernel(FrArgs a) {
             if (m == a.ne) atomicMin(&best_end, static_cast<unsigned long long>(i));
         }
         __syncthreads();
-        if (best_end != ULLONG_MAX) break;                   // the first occurrence is in this chunk
+        // The exit must be one decision for the whole workgroup: every wave
+        // reads the flag, and only after a second barrier may any wave go on
+        // to the next chunk's atomicMin.  Without it a wave late to read could
+        // see a match a faster wave had already posted for the NEXT chunk and
+        // leave with a partial minimum.  (The window is a few instructions
+        // inside one workgroup, so no test goes red on it reliably; the chunk
+        // edge cases of tests/test_framer.py put matches where it would bite.)
+        const bool found = best_end != ULLONG_MAX;           // the first occurrence is in this chunk
+        __syncthreads();
+        if (found) break;
     }
     const int64_t end_at = best_end == ULLONG_MAX ? -1 : static_cast<int64_t>(best_end);
     if (end_at >= 0) {                                       // RingCopyOut + ResetFramer (:223-226)
@@ -425,7 +434,11 @@ tsc_find_kernel(const uint8_t *bits, int64_t stride, const int64_t *n_bits, TscP
             }
         }
         __syncthreads();
-        if (best != ULLONG_MAX) break;                       // no later chunk holds a smaller one
+        // a uniform exit, as in the framer's end search: flag into a register,
+        // a barrier, then the break, so no wave reads a match of the next chunk
+        const bool found = best != ULLONG_MAX;               // no later chunk holds a smaller one
+        __syncthreads();
+        if (found) break;
     }
     if (threadIdx.x == 0) offsets[s] = best == ULLONG_MAX ? -1 : static_cast<int64_t>(best) + m;
 }
