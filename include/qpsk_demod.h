@@ -353,6 +353,21 @@ int64_t qpsk_demod_state_bytes(const qpsk_demod *h);
 int qpsk_demod_get_state(qpsk_demod *h, void *host_buf, int64_t buf_bytes);
 int qpsk_demod_set_state(qpsk_demod *h, const void *host_buf, int64_t buf_bytes);
 
+/* A blob is external input (a file, another host): the kernels use a record's
+ * integers and its timing phase as addresses, so every blob is checked on the
+ * host before a byte of it reaches the device.  Needs no device and no handle:
+ * the tap count and the M&M samples per symbol come from p as in
+ * qpsk_demod_design.  Checks the length, the header against (p, n_streams),
+ * then every record: carry_n in [0, 256], fll_pos in [0, 40), tofs == 0,
+ * has_prev and diff_have 0 or 1, error in [0, 3], base in [0, 1 + ceil(sps +
+ * 0.1)], mu in [+0, 1) (DESIGN.md "State blob" derives each range).  Every
+ * other float is data and is taken as it is, NaN and Inf included.  Returns
+ * QPSK_OK or QPSK_ERR_ARGUMENT; qpsk_last_error names the stream, the field,
+ * its value and the allowed range.  set_state runs it with the handle's own
+ * params first; a rejected blob leaves the handle untouched.  (Added within
+ * ABI version 3: no existing entry point or the blob layout changed.) */
+int qpsk_state_blob_check(const qpsk_demod_params *p, int32_t n_streams, const void *buf, int64_t buf_bytes);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU group: one batch of n_streams over several GPUs,
  * for a host (the C# shim, a C++ driver) that wants the whole node behind one

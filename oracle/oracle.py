@@ -58,6 +58,22 @@ class IQB(C.Structure):
     _fields_ = [("avg_re", C.c_float), ("avg_im", C.c_float)]
 
 
+class DemodState(C.Structure):
+    """or_demod_state (qpsk_oracle.h): the reference instance's private fields."""
+    _fields_ = [
+        ("mm_base_index", C.c_int), ("mm_has_prev", C.c_int),
+        ("mm_mu", C.c_double), ("mm_nco_integral", C.c_double),
+        ("mm_prev_sample", C.c_float * 2), ("mm_prev_decision", C.c_float * 2),
+        ("mm_buf_count", C.c_long),
+        ("costas_theta", C.c_double), ("costas_freq", C.c_double),
+        ("diff_have_prev", C.c_int), ("diff_prev", C.c_float * 2),
+        ("iqb_avg_real", C.c_float), ("iqb_avg_img", C.c_float),
+        ("fll_phase", C.c_float), ("fll_freq", C.c_float),
+        ("fll_pos", C.c_int), ("fll_taps", C.c_int),
+        ("rrc_pos", C.c_int), ("rrc_taps", C.c_int),
+    ]
+
+
 def build():
     subprocess.check_call(["make", "-s", "-C", _HERE])
 
@@ -109,6 +125,10 @@ def lib():
         L.or_demod_gains.argtypes = [C.c_void_p] + [_f64p] * 5
         L.or_demod_rrc_f32.argtypes = [C.c_void_p, _f32p, C.c_int]
         L.or_demod_rrc_f32.restype = C.c_int
+        L.or_demod_read_state.argtypes = [C.c_void_p, C.POINTER(DemodState), _f32p, C.c_long, _f32p, C.c_long,
+                                          _f32p, C.c_long]
+        L.or_demod_read_state.restype = C.c_int
+        L.or_demod_set_lanes.argtypes = [C.c_void_p, C.c_int]
         L.or_bits_to_bytes.argtypes = [C.c_char_p, C.c_long, C.c_int, _u8p, C.c_long]
         L.or_bits_to_bytes.restype = C.c_long
         L.or_index_of.argtypes = [_u8p, C.c_long, _u8p, C.c_long]
@@ -361,6 +381,40 @@ class OracleDemod:
         out = np.zeros(4096, dtype=np.float32)
         n = lib().or_demod_rrc_f32(self._h, _fp(out), 4096)
         return out[:n].copy()
+
+    def set_lanes(self, lanes: int):
+        """Tests only (or_demod_set_lanes): the Vector width of every filter from
+        the next call on; the delay lines stay."""
+        lib().or_demod_set_lanes(self._h, int(lanes))
+
+    def read_state(self) -> dict:
+        """Tests only (or_demod_read_state): the instance's private fields under
+        the reference's names, scalars as numpy values of their own type, plus
+        mm_queue [count, 2] (the retained M&M samples), fll_delay [80, 2] and
+        rrc_delay [2 T, 2] (the 2 N delay lines as the reference holds them,
+        with fll_pos / rrc_pos their write positions)."""
+        st = DemodState()
+        lib().or_demod_read_state(self._h, C.byref(st), None, 0, None, 0, None, 0)
+        q = np.zeros(2 * max(st.mm_buf_count, 1), dtype=np.float32)
+        fd = np.zeros(4 * st.fll_taps, dtype=np.float32)
+        rd = np.zeros(4 * st.rrc_taps, dtype=np.float32)
+        rc = lib().or_demod_read_state(self._h, C.byref(st), _fp(q), q.size, _fp(fd), fd.size, _fp(rd), rd.size)
+        assert rc == 0
+        f32, f64 = np.float32, np.float64
+        return {
+            "mm_base_index": int(st.mm_base_index), "mm_has_prev": int(st.mm_has_prev),
+            "mm_mu": f64(st.mm_mu), "mm_nco_integral": f64(st.mm_nco_integral),
+            "mm_prev_sample": np.array(st.mm_prev_sample[:], dtype=f32),
+            "mm_prev_decision": np.array(st.mm_prev_decision[:], dtype=f32),
+            "mm_buf_count": int(st.mm_buf_count),
+            "mm_queue": q[: 2 * st.mm_buf_count].reshape(-1, 2).copy(),
+            "costas_theta": f64(st.costas_theta), "costas_freq": f64(st.costas_freq),
+            "diff_have_prev": int(st.diff_have_prev), "diff_prev": np.array(st.diff_prev[:], dtype=f32),
+            "iqb_avg_real": f32(st.iqb_avg_real), "iqb_avg_img": f32(st.iqb_avg_img),
+            "fll_phase": f32(st.fll_phase), "fll_freq": f32(st.fll_freq),
+            "fll_pos": int(st.fll_pos), "fll_delay": fd.reshape(-1, 2),
+            "rrc_pos": int(st.rrc_pos), "rrc_taps": int(st.rrc_taps), "rrc_delay": rd.reshape(-1, 2),
+        }
 
     def __del__(self):
         if getattr(self, "_h", None):

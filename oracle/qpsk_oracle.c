@@ -724,6 +724,63 @@ int or_demod_rrc_f32(const or_demod *d, float *taps, int cap)
     return d->n_taps;
 }
 
+/* a ComplexFIRFilter's 2 N delay line, interleaved */
+static int cfir_read_delay(const or_cfir *f, float *out_iq, long cap)
+{
+    if (!out_iq) return 0;
+    if (cap < 4L * f->n) return -1;
+    for (int i = 0; i < 2 * f->n; i++) {
+        out_iq[2 * i] = f->di[i];
+        out_iq[2 * i + 1] = f->dq[i];
+    }
+    return 0;
+}
+
+/* Test infrastructure: see qpsk_oracle.h */
+int or_demod_read_state(const or_demod *d, or_demod_state *st, float *mm_queue_iq, long mm_queue_cap,
+                        float *fll_delay_iq, long fll_delay_cap, float *rrc_delay_iq, long rrc_delay_cap)
+{
+    const or_mm *m = d->mm;
+    memset(st, 0, sizeof(*st));
+    st->mm_base_index = m->base;
+    st->mm_has_prev = m->has_prev;
+    st->mm_mu = m->mu;
+    st->mm_nco_integral = m->integ;
+    st->mm_prev_sample[0] = m->psi; st->mm_prev_sample[1] = m->psq;
+    st->mm_prev_decision[0] = m->pdi; st->mm_prev_decision[1] = m->pdq;
+    st->mm_buf_count = m->count;
+    st->costas_theta = d->costas->theta;
+    st->costas_freq = d->costas->freq;
+    st->diff_have_prev = d->diff_have_prev;
+    st->diff_prev[0] = d->prev_i; st->diff_prev[1] = d->prev_q;
+    st->iqb_avg_real = d->iqb.avg_re;
+    st->iqb_avg_img = d->iqb.avg_im;
+    st->fll_phase = d->fll->phase;
+    st->fll_freq = d->fll->freq;
+    st->fll_pos = d->fll->f_upper->pos;
+    st->fll_taps = d->fll->f_upper->n;
+    st->rrc_pos = d->rrc->pos;
+    st->rrc_taps = d->rrc->n;
+    if (mm_queue_iq) {
+        if (mm_queue_cap < 2 * m->count) return -1;
+        memcpy(mm_queue_iq, m->buf + 2 * m->start, (size_t)(2 * m->count) * sizeof(float));
+    }
+    if (cfir_read_delay(d->fll->f_upper, fll_delay_iq, fll_delay_cap)) return -1;
+    if (cfir_read_delay(d->rrc, rrc_delay_iq, rrc_delay_cap)) return -1;
+    return 0;
+}
+
+/* Test infrastructure: the reference's Vector<float>.Count is fixed per machine;
+ * this moves a running instance to another width, as a state blob restored
+ * into a handle of another vector_lanes does (the delay lines stay). */
+void or_demod_set_lanes(or_demod *d, int lanes)
+{
+    d->cfg.lanes = lanes;
+    d->rrc->lanes = lanes;
+    d->fll->f_lower->lanes = lanes;
+    d->fll->f_upper->lanes = lanes;
+}
+
 static void ensure_tmp(or_demod *d, long n_floats)               /* :290-302 */
 {
     if (d->tmp_cap >= n_floats) return;

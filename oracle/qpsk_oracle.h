@@ -101,6 +101,39 @@ long or_demod_bytes(or_demod *d, const float *iq, long n_floats, const uint8_t *
 void or_demod_gains(const or_demod *d, double *mm_sps, double *kp, double *ki, double *c_alpha,
                     double *c_beta);
 int or_demod_rrc_f32(const or_demod *d, float *taps, int cap);
+/* Tests only: the instance's private fields, under the reference's names, read
+ * and never written (the reference has no such accessor).
+ *   MuellerMuller.cs:24-36     baseIndex (relative to the retained queue), mu,
+ *                              ncoIntegral, hasPrev, prevSample, prevDecision,
+ *                              _bufCount and the retained queue's samples
+ *   CostasLoopQpsk.cs:25-27    theta, freq
+ *   QPSKDeModulator.cs:72-73   _diffHavePrev and the previous decision
+ *   IQ Balancer.cs:13          _avgReal, _avgImg
+ *   Band-Edge Filter.cs:25-26  phase, freq; FIRFilter.cs:18-22 the delay line
+ *                              (_delayI2N / _delayQ2N, 2 N entries) and _pos of
+ *                              its band-edge filters (both are fed the same
+ *                              samples: the upper one's is returned)
+ *   FIRFilter.cs:18-22         the matched filter's delay line and _pos
+ * Arrays are interleaved I,Q; each is filled up to its cap (in floats) and may
+ * be NULL.  Returns 0, or -1 when an array is too small for its line. */
+typedef struct or_demod_state {
+    int mm_base_index, mm_has_prev;
+    double mm_mu, mm_nco_integral;
+    float mm_prev_sample[2], mm_prev_decision[2];
+    long mm_buf_count;
+    double costas_theta, costas_freq;
+    int diff_have_prev;
+    float diff_prev[2];
+    float iqb_avg_real, iqb_avg_img;
+    float fll_phase, fll_freq;
+    int fll_pos, fll_taps;
+    int rrc_pos, rrc_taps;
+} or_demod_state;
+int or_demod_read_state(const or_demod *d, or_demod_state *st, float *mm_queue_iq, long mm_queue_cap,
+                        float *fll_delay_iq, long fll_delay_cap, float *rrc_delay_iq, long rrc_delay_cap);
+/* tests only, no reference counterpart: Vector<float>.Count of every filter
+ * from the next call on (a blob restored into a handle of another vector_lanes) */
+void or_demod_set_lanes(or_demod *d, int lanes);
 
 /* Framer pieces on a bit string (HelperFunctions.cs:11-71) */
 long or_bits_to_bytes(const char *bits, long n_bits, int bit_offset, uint8_t *out, long cap);

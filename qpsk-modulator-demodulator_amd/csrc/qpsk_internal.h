@@ -1,7 +1,8 @@
 // qpsk_internal.h -- what the host code behind the C ABI shares between its
 // translation units: the error channel, the per-call argument check and the
 // few things the ring (qpsk_rx.hip) and the group (qpsk_group.cpp) need from a
-// handle.  Private and host-only; all of it is defined in qpsk_runtime.hip.
+// handle.  Private and host-only; the error channel is defined in
+// qpsk_error.cpp (no HIP), the rest in qpsk_runtime.hip.
 #pragma once
 #include <cstdint>
 #include <string>

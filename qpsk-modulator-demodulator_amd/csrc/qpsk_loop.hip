@@ -817,7 +817,11 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
         psq = static_cast<float>(psqd);
         pdi = static_cast<float>(pdid);
         pdq = static_cast<float>(pdqd);
-        g->psi = psi; g->psq = psq; g->pdi = pdi; g->pdq = pdq;
+        g->psi = psi; g->psq = psq;
+        // before the stream's first symbol the registers hold the sign of the
+        // stored decision (+1 for the fresh 0), not the decision: the record
+        // keeps what it has (prevDecision is (0, 0) until hasPrev)
+        if (has_prev) { g->pdi = pdi; g->pdq = pdq; }
         g->has_prev = has_prev;
         return;
     }

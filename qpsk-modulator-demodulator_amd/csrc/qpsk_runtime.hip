@@ -51,17 +51,9 @@
 #include "qpsk_design.h"
 #include "qpsk_internal.h"
 #include "qpsk_kernels.h"
+#include "qpsk_state_blob.h"
 
 using namespace qpsk;
-
-namespace {
-thread_local std::string g_last_error;
-}  // namespace
-
-int qpsk::fail(int code, const std::string &msg) {
-    g_last_error = msg;
-    return code;
-}
 
 namespace {
 template <typename T>
@@ -649,8 +641,6 @@ int pipe_setup(qpsk_demod *h) {
 extern "C" {
 
 int qpsk_abi_version(void) { return QPSK_ABI_VERSION; }
-
-const char *qpsk_last_error(void) { return g_last_error.c_str(); }
 
 void qpsk_demod_params_init(qpsk_demod_params *p, int32_t sample_rate, int32_t symbol_rate) {
     std::memset(p, 0, sizeof(*p));
@@ -1453,29 +1443,13 @@ int qpsk_demod_design(const qpsk_demod_params *p, float *rrc_taps, int32_t cap, 
     return T;
 }
 
-// State blob (format 2): a header naming the layout, then the per-stream
-// records, the M&M carries, the FIR histories and the FLL delay lines.  Format
-// 1 (round 3 and before) had no header and a 64-sample carry; set_state
-// rejects any blob whose header or length does not match this handle.
-namespace {
-constexpr uint32_t kStateMagic = 0x4b535051u;   // "QPSK"
-constexpr uint32_t kStateFormat = 2;
-struct StateHeader {
-    uint32_t magic, format;
-    int32_t streams, taps, carry_max, fll_taps, record_bytes, reserved;
-};
-static_assert(sizeof(StateHeader) == 32, "state blob header");
-StateHeader state_header(const qpsk_demod *h) {
-    return StateHeader{kStateMagic, kStateFormat, h->S, h->T, kCarryMax, kFllTaps,
-                       static_cast<int32_t>(sizeof(StreamState)), 0};
-}
-}  // namespace
-
+// State blob (qpsk_state_blob.h): set_state rejects, before it touches the
+// handle, any blob whose length or header does not match this handle or whose
+// records hold a value a kernel would misuse as an address
+// (qpsk_state_blob_check, qpsk_state_blob.cpp).
 int64_t qpsk_demod_state_bytes(const qpsk_demod *h) {
     if (!h) return 0;
-    const int64_t S = h->S, H = h->T - 1;
-    return static_cast<int64_t>(sizeof(StateHeader)) +
-           S * (static_cast<int64_t>(sizeof(StreamState)) + 8 * kCarryMax + 8 * H + 8 * 2 * kFllTaps);
+    return state_blob_bytes(h->S, h->T);
 }
 
 int qpsk_demod_get_state(qpsk_demod *h, void *host_buf, int64_t buf_bytes) {
@@ -1485,7 +1459,7 @@ int qpsk_demod_get_state(qpsk_demod *h, void *host_buf, int64_t buf_bytes) {
     char *p = static_cast<char *>(host_buf);
     int rc;
     if ((rc = handle_sync(h))) return rc;
-    const StateHeader hd = state_header(h);
+    const StateHeader hd = state_header(h->S, h->T);
     std::memcpy(p, &hd, sizeof(hd));
     p += sizeof(hd);
     QPSK_HIP_TRY(hipMemcpy(p, h->d_state, S * sizeof(StreamState), hipMemcpyDeviceToHost));
@@ -1500,24 +1474,12 @@ int qpsk_demod_get_state(qpsk_demod *h, void *host_buf, int64_t buf_bytes) {
 
 int qpsk_demod_set_state(qpsk_demod *h, const void *host_buf, int64_t buf_bytes) {
     if (!h || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    if (buf_bytes != qpsk_demod_state_bytes(h))
-        return fail(QPSK_ERR_ARGUMENT, "state blob length does not match this handle (" +
-                                           std::to_string(buf_bytes) + " vs " +
-                                           std::to_string(qpsk_demod_state_bytes(h)) + " bytes)");
-    const StateHeader want = state_header(h);
-    StateHeader got;
-    std::memcpy(&got, host_buf, sizeof(got));
-    if (got.magic != want.magic || got.format != want.format)
-        return fail(QPSK_ERR_ARGUMENT, "not a state blob of this library version (format " +
-                                           std::to_string(got.format) + ", expected " +
-                                           std::to_string(want.format) + ")");
-    if (got.streams != want.streams || got.taps != want.taps || got.carry_max != want.carry_max ||
-        got.fll_taps != want.fll_taps || got.record_bytes != want.record_bytes)
-        return fail(QPSK_ERR_ARGUMENT, "state blob layout (streams, taps, carry, record size) does not "
-                                       "match this handle");
+    int rc;
+    // on the host, before the handle is waited for or a byte is copied: a
+    // rejected blob leaves the handle as it was
+    if ((rc = qpsk_state_blob_check(&h->p, h->S, host_buf, buf_bytes))) return rc;
     const int64_t S = h->S, H = h->T - 1;
     const char *p = static_cast<const char *>(host_buf) + sizeof(StateHeader);
-    int rc;
     if ((rc = handle_sync(h))) return rc;
     QPSK_HIP_TRY(hipMemcpy(h->d_state, p, S * sizeof(StreamState), hipMemcpyHostToDevice));
     p += S * sizeof(StreamState);

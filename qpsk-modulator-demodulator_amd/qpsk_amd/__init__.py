@@ -228,6 +228,7 @@ def lib():
     L.qpsk_demod_state_bytes.restype = C.c_int64
     L.qpsk_demod_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.qpsk_demod_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_state_blob_check.argtypes = [C.POINTER(DemodParams), C.c_int32, C.c_void_p, C.c_int64]
     L.qpsk_pipeline_gate_enabled.restype = C.c_int
     L.qpsk_demod_gate_timeouts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.qpsk_demod_pick_loop_variant.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_int32]
@@ -315,6 +316,7 @@ EXPORTED_SYMBOLS = [
     "qpsk_fmt_sample_bytes", "qpsk_demod_process_fmt", "qpsk_demod_process_async_fmt",
     "qpsk_demod_set_input_scale", "qpsk_demod_get_input_scale", "qpsk_rx_create_fmt", "qpsk_rx_next_slot_fmt",
     "qpsk_rx_submit_fmt", "qpsk_demod_group_process_fmt",
+    "qpsk_state_blob_check",
 ]
 
 _EXC = {
@@ -382,6 +384,35 @@ STREAM_STATE_DTYPE = np.dtype([("mu", "f8"), ("integ", "f8"), ("theta", "f8"), (
                                ("diff_pi", "f4"), ("diff_pq", "f4"), ("fll_phase", "f4"),
                                ("fll_freq", "f4"), ("fll_pos", "i4"), ("error", "i4"), ("tofs", "i8"),
                                ("iqb_re", "f4"), ("iqb_im", "f4"), ("_pad", "V8")])   # alignas(16): 112 B
+STATE_CARRY_MAX = 256   # kCarryMax
+STATE_FLL_TAPS = 40     # kFllTaps
+
+
+def state_blob_check(p: DemodParams, n_streams: int, blob: bytes):
+    """qpsk_state_blob_check: what set_state checks of a blob for a handle of
+    n_streams streams and params p, on the host (needs no device).  Raises
+    ValueError naming the stream, the field, its value and the allowed range."""
+    buf = C.create_string_buffer(bytes(blob), max(len(blob), 1))
+    _check(lib().qpsk_state_blob_check(C.byref(p), int(n_streams), buf, len(blob)))
+
+
+def state_blob_parts(blob: bytes, n_streams: int, taps: int):
+    """The sections of a blob as arrays (copies): records [S] (STREAM_STATE_DTYPE),
+    carries [S, 256, 2], FIR histories [S, taps - 1, 2] (oldest sample first),
+    FLL delay lines [S, 80, 2] (the reference's doubled line: entry q and
+    q + 40 hold the sample last written at position q)."""
+    S, H = int(n_streams), int(taps) - 1
+    o = STATE_HEADER_BYTES
+    rec = np.frombuffer(blob, dtype=STREAM_STATE_DTYPE, count=S, offset=o).copy()
+    o += S * STREAM_STATE_DTYPE.itemsize
+    carry = np.frombuffer(blob, dtype=np.float32, count=S * STATE_CARRY_MAX * 2, offset=o)
+    o += carry.nbytes
+    hist = np.frombuffer(blob, dtype=np.float32, count=S * H * 2, offset=o)
+    o += hist.nbytes
+    dl = np.frombuffer(blob, dtype=np.float32, count=S * 2 * STATE_FLL_TAPS * 2, offset=o)
+    assert o + dl.nbytes == len(blob)
+    return (rec, carry.reshape(S, STATE_CARRY_MAX, 2).copy(), hist.reshape(S, H, 2).copy(),
+            dl.reshape(S, 2 * STATE_FLL_TAPS, 2).copy())
 
 
 class BatchDemodulator:
@@ -510,7 +541,8 @@ class BatchDemodulator:
 
     def set_state(self, blob: bytes):
         """Restore a get_state() blob of a handle of the same shape (streams,
-        taps); any other blob raises (QPSK_ERR_ARGUMENT)."""
+        taps); any other blob, and one whose records fail state_blob_check,
+        raises (QPSK_ERR_ARGUMENT) and leaves the handle as it was."""
         buf = C.create_string_buffer(bytes(blob), len(blob))
         _check(lib().qpsk_demod_set_state(self._h, buf, len(blob)))
 

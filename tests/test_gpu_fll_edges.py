@@ -33,9 +33,11 @@ clamp alone decides.  And at amplitude 1e20 these rows do not overflow the
 band powers yet; the overflow case adds rows at 1e21 (error +-Inf) and 1e22
 (error NaN).
 
-Stored states (set_state): no value is rejected -- qpsk_demod_set_state checks
-the blob's header and length only -- so every listed phase and frequency,
-NaN and Inf included, is run.
+Stored states (set_state): no phase or frequency is rejected --
+qpsk_demod_set_state checks the blob's header and length and the fields the
+kernels use as addresses (qpsk_state_blob_check: carry_n, fll_pos, tofs, the
+flags, base, mu), never a float that is data -- so every listed phase and
+frequency, NaN and Inf included, is run.
 """
 import functools
 
