@@ -57,9 +57,24 @@ __device__ __forceinline__ unsigned cu_key() {
 // shared = the loop kernel held the workgroup's CU when it started (cu_map)
 constexpr int kFirPhaseWords = 16;
 
+// Input element format of the matched filter's rows (QPSK_FMT_*).  x_stride
+// counts samples whatever the format, and a row's samples are widened to
+// float2 by the kernel that loads them:
+//   kFmtCf32  float pairs, read as they stand;
+//   kFmtCs16  int16 pairs, (float)v * x_scale;
+//   kFmtCs8 / kFmtCu8  byte pairs, ((float)(uint8)(v ^ x_flip) - 128) * x_scale:
+//             x_flip = 0x80 in every byte for CS8 (an int8 x is
+//             (uint8)(x ^ 0x80) - 128), 0 for CU8, so one set of kernels serves both.
+// The launchers fill x_scale and x_flip from their x_fmt and x_scale
+// arguments.  Both sit behind the members the float kernels read, whose
+// offsets (and so the float kernels' code) stay as they were.
+constexpr int32_t kFmtCf32 = 0;
+constexpr int32_t kFmtCs16 = 1;
+constexpr int32_t kFmtCs8 = 2;
+constexpr int32_t kFmtCu8 = 3;
 struct FirArgs {
-    const float *x;        // [S][x_stride] float2 input
-    int64_t x_stride;      // in float2
+    const float *x;        // [S][x_stride] input samples (float2, int16 pairs or byte pairs)
+    int64_t x_stride;      // in samples
     const float *hist;     // [S][T-1] float2: previous call's last T-1 inputs
     const int64_t *lengths;
     int64_t n;             // uniform length when lengths == nullptr
@@ -74,27 +89,10 @@ struct FirArgs {
     // split by whether a loop workgroup held its CU (cu_map, kCuKeys words)
     unsigned long long *phases;
     const unsigned *cu_map;
+    float x_scale;         // integer formats (set by the launcher)
+    uint32_t x_flip;       // 8-bit formats (set by the launcher)
 };
 constexpr unsigned kFirClockEvery = 64;
-// Input element format of the matched filter's rows: kFmtCf32 = float2 as
-// above; kFmtCs16 = x points at [S][x_stride] int16 pairs (x_stride still in
-// samples) and a sample's value is (float)v * x_scale, widened by the kernel
-// that loads it.  The CS16 kernels take the scale behind the float kernels'
-// arguments, whose layout (and so the float kernels' code) stays as it was.
-constexpr int32_t kFmtCf32 = 0;
-constexpr int32_t kFmtCs16 = 1;
-struct FirArgsCs16 : FirArgs {
-    float x_scale;
-};
-// kFmtCs8 / kFmtCu8 = x points at [S][x_stride] byte pairs and a sample's value
-// is ((float)(uint8)(v ^ flip) - 128) * x_scale: flip = 0x80 in every byte for
-// CS8 (an int8 x is (uint8)(x ^ 0x80) - 128), 0 for CU8.  One set of kernels
-// serves both; the flip mask rides behind the scale.
-constexpr int32_t kFmtCs8 = 2;
-constexpr int32_t kFmtCu8 = 3;
-struct FirArgsI8 : FirArgsCs16 {
-    uint32_t x_flip;
-};
 
 // CS16 or 8-bit rows widened into float2 rows, for the serial pre-stages (IQ
 // balancer, FLL) that read one sample per step and already write a float row
@@ -106,7 +104,8 @@ struct WidenArgs {
     int64_t y_offset;
     const int64_t *lengths;
     int64_t n;
-    float scale;
+    float x_scale;
+    uint32_t x_flip;       // set by the launcher
 };
 
 struct LoopArgs {

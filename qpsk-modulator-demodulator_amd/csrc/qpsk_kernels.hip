@@ -33,8 +33,6 @@ typedef short s8 __attribute__((ext_vector_type(8)));
 // CS8 / CU8 input: one sample = a byte pair; both formats go through one
 // element type (a uniform XOR of 0x80 on each byte tells them apart)
 typedef unsigned char b2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
 template <typename A, typename B> struct same_type { static constexpr bool value = false; };
 template <typename A> struct same_type<A, A> { static constexpr bool value = true; };
@@ -58,31 +56,103 @@ __device__ __forceinline__ f2 widen(b2 v, float scale, unsigned flip) {
     const unsigned w = (static_cast<unsigned>(v.x) | (static_cast<unsigned>(v.y) << 8)) ^ (flip & 0xffffu);
     return (f2{static_cast<float>(w & 0xffu), static_cast<float>(w >> 8)} - f2{128.0f, 128.0f}) * scale;
 }
-// The kernel argument block of each element type, and its scale
-template <typename XT> struct fir_args { typedef FirArgs type; };
-template <> struct fir_args<s2> { typedef FirArgsCs16 type; };
-template <> struct fir_args<b2> { typedef FirArgsI8 type; };
-__device__ __forceinline__ float x_scale(const FirArgs &) { return 0.0f; }
-__device__ __forceinline__ float x_scale(const FirArgsCs16 &a) { return a.x_scale; }
-__device__ __forceinline__ float x_scale(const FirArgsI8 &a) { return a.x_scale; }
-__device__ __forceinline__ unsigned x_flip(const FirArgs &) { return 0u; }
-__device__ __forceinline__ unsigned x_flip(const FirArgsI8 &a) { return a.x_flip; }
-// Input sample g of a row of either element type; the float2 row is read as it
-// always was (scale unused).
-template <typename XT>
-__device__ __forceinline__ f2 load_x(const XT *x, int64_t g, float scale) {
-    if constexpr (same_type<XT, f2>::value) return x[g];
-    else return widen(x[g], scale);
+
+// ---------------------------------------------------------------------------
+// Sample<XT>: everything that depends on a row's element type (f2 = CF32, s2 =
+// CS16, b2 = CS8 and CU8).  Nothing below asks which format it has.
+//   one(x, g, a)       sample g of a row as float2; a = any argument block
+//                      with x_scale and x_flip (FirArgs, WidenArgs)
+//   many<L>(x, g, a, u) L samples from g in one vector load of L * sizeof(XT)
+//                      bytes, which must be aligned to its size
+//   kWide              the samples of the widest such load (16 B)
+//   group(T)           the samples per load when a T-tap tile is staged
+//   vec_supported(T)   whether a T-tap tile can be staged by such loads: the
+//                      tile's first input, tile0 - (T - 1), must be a multiple
+//                      of group(T), and a group must not straddle a 64-sample
+//                      LDS row.  What the kernel asserts (fir_stage) ...
+//   vec_ok(a, T)       ... and what the launcher adds to it at run time: rows
+//                      aligned to the load, and keeping that from row to row.
+// ---------------------------------------------------------------------------
+// p + stride * row + offset (in samples) is aligned to L samples for every row
+static bool rows_aligned(const void *p, int64_t stride, int64_t offset, int L, size_t sample_bytes) {
+    return reinterpret_cast<uintptr_t>(p) % (L * sample_bytes) == 0 && stride % L == 0 && offset % L == 0;
 }
-// ... and of an 8-bit row
-__device__ __forceinline__ f2 load_x(const b2 *x, int64_t g, float scale, unsigned flip) {
-    return widen(x[g], scale, flip);
+template <typename XT> struct Sample;
+template <> struct Sample<f2> {
+    static constexpr int kWide = 2;
+    static constexpr int group(int) { return 2; }
+    static constexpr bool vec_supported(int T) { return T % 2 == 1; }
+    // the float path also asks for its output rows 16-B aligned
+    static bool vec_ok(const FirArgs &a, int T) {
+        return vec_supported(T) && rows_aligned(a.x, a.x_stride, 0, 2, sizeof(f2)) &&
+               rows_aligned(a.y, a.y_stride, a.y_offset, 2, sizeof(f2));
+    }
+    template <typename A> __device__ static __forceinline__ f2 one(const f2 *x, int64_t g, const A &) { return x[g]; }
+    template <int L, typename A>
+    __device__ static __forceinline__ void many(const f2 *x, int64_t g, const A &, f2 (&u)[L]) {
+        static_assert(L == 2, "one float4 = 2 samples");
+        const f4 v = *reinterpret_cast<const f4 *>(x + g);
+        u[0] = f2{v.x, v.y};
+        u[1] = f2{v.z, v.w};
+    }
+};
+template <> struct Sample<s2> {
+    static constexpr int kWide = 4;
+    static constexpr int group(int) { return 4; }
+    static constexpr bool vec_supported(int T) { return (T - 1) % 4 == 0; }
+    static bool vec_ok(const FirArgs &a, int T) {
+        return vec_supported(T) && rows_aligned(a.x, a.x_stride, 0, 4, sizeof(s2));
+    }
+    template <typename A> __device__ static __forceinline__ f2 one(const s2 *x, int64_t g, const A &a) {
+        return widen(x[g], a.x_scale);
+    }
+    template <int L, typename A>
+    __device__ static __forceinline__ void many(const s2 *x, int64_t g, const A &a, f2 (&u)[L]) {
+        static_assert(L == 4, "one 16-B load = 4 samples");
+        const s8 v = *reinterpret_cast<const s8 *>(x + g);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) u[k] = widen(s2{v[2 * k], v[2 * k + 1]}, a.x_scale);
+    }
+};
+template <> struct Sample<b2> {
+    static constexpr int kWide = 8;
+    // 16-B loads of 8 samples where T - 1 is a multiple of 8, so that every
+    // load stays inside one 64-sample LDS row; 8-B loads of 4 for
+    // T - 1 = 4 mod 8 (T = 13, 21)
+    static constexpr int group(int T) { return (T - 1) % 8 == 0 ? 8 : 4; }
+    static constexpr bool vec_supported(int T) { return (T - 1) % 4 == 0; }
+    static bool vec_ok(const FirArgs &a, int T) {
+        return vec_supported(T) && rows_aligned(a.x, a.x_stride, 0, group(T), sizeof(b2));
+    }
+    template <typename A> __device__ static __forceinline__ f2 one(const b2 *x, int64_t g, const A &a) {
+        return widen(x[g], a.x_scale, a.x_flip);
+    }
+    template <int L, typename A>
+    __device__ static __forceinline__ void many(const b2 *x, int64_t g, const A &a, f2 (&u)[L]) {
+        static_assert(L == 8 || L == 4, "a 16-B or an 8-B load");
+        typedef unsigned int uw __attribute__((ext_vector_type(L / 2)));
+        const uw v = *reinterpret_cast<const uw *>(x + g) ^ a.x_flip;   // one packed XOR per 4 bytes
+#pragma unroll
+        for (int k = 0; k < L / 2; ++k) widen8(v[k], a.x_scale, u[2 * k], u[2 * k + 1]);
+    }
+};
+// f(XT{}) for the element type of QPSK_FMT_* x_fmt; CS8 and CU8 differ only in
+// the flip mask their argument block carries
+static unsigned flip_of(int32_t fmt) { return fmt == kFmtCs8 ? 0x80808080u : 0u; }
+template <typename F>
+static void with_format(int32_t x_fmt, F f) {
+    switch (x_fmt) {
+    case kFmtCs16: return f(s2{});
+    case kFmtCs8:
+    case kFmtCu8: return f(b2{});
+    default: return f(f2{});
+    }
 }
-// load_x with the arguments the element type's block carries
+// Sample g of a stream's row, g < 0 reaching back into its H-sample history
+// (float whatever the row's format)
 template <typename XT, typename A>
-__device__ __forceinline__ f2 load_xa(const XT *x, int64_t g, const A &a) {
-    if constexpr (same_type<XT, b2>::value) return load_x(x, g, x_scale(a), x_flip(a));
-    else return load_x(x, g, x_scale(a));
+__device__ __forceinline__ f2 row_sample(const XT *x, const f2 *hist, int H, int64_t g, const A &a) {
+    return g < 0 ? hist[H + g] : Sample<XT>::one(x, g, a);
 }
 
 // ---------------------------------------------------------------------------
@@ -227,97 +297,28 @@ __device__ __forceinline__ void fir_core(const f2 *row, int r, const float *hrev
 __device__ __forceinline__ int fir_nonfinite(float v) { return __builtin_amdgcn_classf(v, 0x207); }   // NaN, +-Inf
 
 // Stage x[tile0-(T-1) .. tile0+TILE) into LDS; t<0 from the previous call's
-// history, t>=n as zeros (those outputs are not stored).
-template <int T, int NIN, bool VEC, int NT>
-__device__ __forceinline__ void fir_stage(f2 *lds, const f2 *x, const f2 *hist, int64_t tile0, int64_t n) {
-    const int tid = threadIdx.x;
-    const int64_t g0 = tile0 - (T - 1);
-    if constexpr (VEC) {
-        // g0 is even (T odd) and rows are 16-B aligned: one float4 = 2 samples.
-        for (int p = tid; p < (NIN + 1) / 2; p += NT) {
-            const int64_t g = g0 + 2 * p;
-            f4 v;
-            if (g >= 0 && g + 1 < n) {
-                v = *reinterpret_cast<const f4 *>(x + g);
-            } else {
-                f2 lo = g < 0 ? hist[T - 1 + g] : (g < n ? x[g] : f2{0.f, 0.f});
-                f2 hi = (g + 1) < 0 ? hist[T + g] : ((g + 1) < n ? x[g + 1] : f2{0.f, 0.f});
-                v = f4{lo.x, lo.y, hi.x, hi.y};
-            }
-            *reinterpret_cast<f4 *>(&lds[lds_slot(2 * p)]) = v;
-        }
-    } else {
-        for (int i = tid; i < NIN; i += NT) {
-            const int64_t g = g0 + i;
-            lds[lds_slot(i)] = g < 0 ? hist[T - 1 + g] : (g < n ? x[g] : f2{0.f, 0.f});
-        }
-    }
-}
-
-// The same LDS image from CS16 rows: the int16 pairs are widened on their way
-// into LDS, so fir_core reads what it reads from a float row.
-template <int T, int NIN, bool VEC, int NT>
-__device__ __forceinline__ void fir_stage_cs16(f2 *lds, const s2 *x, const f2 *hist, int64_t tile0, int64_t n,
-                                               float scale) {
+// history, t>=n as zeros (those outputs are not stored).  Integer rows are
+// widened on their way into LDS, so fir_core reads what it reads from a float
+// row.  VEC: groups of L samples, a whole group in range by one vector load;
+// g0 is a multiple of L and rows are aligned to the load (Sample<XT>), so a
+// group shares a 64-sample LDS row and slot L p + 8 floor(L p / 64) is
+// 8L-byte aligned: L / 2 16-B LDS writes.
+template <int T, int NIN, bool VEC, int NT, typename XT>
+__device__ __forceinline__ void fir_stage(f2 *lds, const XT *x, const f2 *hist, int64_t tile0, int64_t n,
+                                          const FirArgs &a) {
     const int tid = threadIdx.x;
     const int64_t g0 = tile0 - (T - 1);
     auto one = [&](int64_t g) -> f2 {
-        return g < 0 ? hist[T - 1 + g] : (g < n ? widen(x[g], scale) : f2{0.f, 0.f});
+        return g < 0 ? hist[T - 1 + g] : (g < n ? Sample<XT>::one(x, g, a) : f2{0.f, 0.f});
     };
     if constexpr (VEC) {
-        // g0 is a multiple of 4 (T - 1 is) and rows are 16-B aligned: one
-        // 16-B load = 4 samples, which share a 64-sample LDS row (two 16-B
-        // LDS writes; slot 4p + 8 floor(4p / 64) is 32-B aligned)
-        static_assert((T - 1) % 4 == 0, "CS16 vector staging expects T = 1 mod 4");
-        for (int p = tid; p < (NIN + 3) / 4; p += NT) {
-            const int64_t g = g0 + 4 * p;
-            f2 u[4];
-            if (g >= 0 && g + 3 < n) {
-                const s8 v = *reinterpret_cast<const s8 *>(x + g);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) u[k] = widen(s2{v[2 * k], v[2 * k + 1]}, scale);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) u[k] = one(g + k);
-            }
-            f2 *dst = &lds[lds_slot(4 * p)];
-            *reinterpret_cast<f4 *>(dst) = f4{u[0].x, u[0].y, u[1].x, u[1].y};
-            *reinterpret_cast<f4 *>(dst + 2) = f4{u[2].x, u[2].y, u[3].x, u[3].y};
-        }
-    } else {
-        for (int i = tid; i < NIN; i += NT) lds[lds_slot(i)] = one(g0 + i);
-    }
-}
-
-// The same LDS image from 8-bit rows (CS8 / CU8, two bytes a sample).  L = the
-// samples of one vector load: 8 (16 B) where T - 1 is a multiple of 8, so that
-// g0, a multiple of 8, keeps every load inside one 64-sample LDS row (four
-// 16-B LDS writes); 4 (8 B) for T - 1 = 4 mod 8 (T = 13, 21).
-template <int T> constexpr int i8_vec_samples() { return (T - 1) % 8 == 0 ? 8 : 4; }
-template <int T, int NIN, bool VEC, int NT>
-__device__ __forceinline__ void fir_stage_i8(f2 *lds, const b2 *x, const f2 *hist, int64_t tile0, int64_t n,
-                                             float scale, unsigned flip) {
-    const int tid = threadIdx.x;
-    const int64_t g0 = tile0 - (T - 1);
-    auto one = [&](int64_t g) -> f2 {
-        return g < 0 ? hist[T - 1 + g] : (g < n ? widen(x[g], scale, flip) : f2{0.f, 0.f});
-    };
-    if constexpr (VEC) {
-        constexpr int L = i8_vec_samples<T>();
-        static_assert((T - 1) % 4 == 0, "8-bit vector staging expects T = 1 mod 4");
+        constexpr int L = Sample<XT>::group(T);
+        static_assert(Sample<XT>::vec_supported(T), "vector staging of this format at this tap count");
         for (int p = tid; p < (NIN + L - 1) / L; p += NT) {
             const int64_t g = g0 + L * p;
             f2 u[L];
             if (g >= 0 && g + L - 1 < n) {
-                if constexpr (L == 8) {
-                    const u4 v = *reinterpret_cast<const u4 *>(x + g) ^ flip;   // one packed XOR per 4 bytes
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) widen8(v[k], scale, u[2 * k], u[2 * k + 1]);
-                } else {
-                    const u2 v = *reinterpret_cast<const u2 *>(x + g) ^ flip;
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) widen8(v[k], scale, u[2 * k], u[2 * k + 1]);
-                }
+                Sample<XT>::many(x, g, a, u);
             } else {
 #pragma unroll
                 for (int k = 0; k < L; ++k) u[k] = one(g + k);
@@ -333,7 +334,7 @@ __device__ __forceinline__ void fir_stage_i8(f2 *lds, const b2 *x, const f2 *his
 }
 
 template <int T, int W, int Q, bool VEC, int NT, typename XT = f2>
-__global__ __launch_bounds__(NT) void fir_tile_kernel(typename fir_args<XT>::type a, const float *hrev) {
+__global__ __launch_bounds__(NT) void fir_tile_kernel(FirArgs a, const float *hrev) {
     constexpr int TILE = NT * Q;
     constexpr int NIN = TILE + T - 1;
     __shared__ f2 lds[lds_slots(NIN)];
@@ -372,9 +373,7 @@ __global__ __launch_bounds__(NT) void fir_tile_kernel(typename fir_args<XT>::typ
         p0 = __builtin_amdgcn_s_memtime();
     }
 
-    if constexpr (same_type<XT, f2>::value) fir_stage<T, NIN, VEC, NT>(lds, x, hist, tile0, n);
-    else if constexpr (same_type<XT, s2>::value) fir_stage_cs16<T, NIN, VEC, NT>(lds, x, hist, tile0, n, x_scale(a));
-    else fir_stage_i8<T, NIN, VEC, NT>(lds, x, hist, tile0, n, x_scale(a), x_flip(a));
+    fir_stage<T, NIN, VEC, NT>(lds, x, hist, tile0, n, a);
     __syncthreads();
     if (ph_wg) p1 = __builtin_amdgcn_s_memtime();
 
@@ -431,28 +430,9 @@ __global__ __launch_bounds__(NT) void fir_tile_kernel(typename fir_args<XT>::typ
                 const int64_t go = tile0 + o0 + W * q;   // output sample
                 if (!((bad >> q) & 1u) || go >= n) continue;
                 const int64_t w0 = go - (T - 1);         // its oldest window sample
-                if constexpr (same_type<XT, f2>::value) {
-                    auto xs = [&](int k) -> f2 {
-                        const int64_t g = w0 + k;
-                        return g < 0 ? hist[T - 1 + g] : x[g];
-                    };
-                    y[go] = fir_exact_one(xs, hrev, T, W);
-                } else if constexpr (same_type<XT, s2>::value) {
-                    // CS16 rows: the history may hold a NaN or Inf of an earlier float call
-                    const float scale = x_scale(a);
-                    auto xs = [&](int k) -> f2 {
-                        const int64_t g = w0 + k;
-                        return g < 0 ? hist[T - 1 + g] : widen(x[g], scale);
-                    };
-                    y[go] = fir_exact_one(xs, hrev, T, W);
-                } else {
-                    // 8-bit rows, likewise
-                    auto xs = [&](int k) -> f2 {
-                        const int64_t g = w0 + k;
-                        return g < 0 ? hist[T - 1 + g] : load_xa(x, g, a);
-                    };
-                    y[go] = fir_exact_one(xs, hrev, T, W);
-                }
+                // integer rows too: the history may hold a NaN or Inf of an earlier float call
+                auto xs = [&](int k) -> f2 { return row_sample(x, hist, T - 1, w0 + k, a); };
+                y[go] = fir_exact_one(xs, hrev, T, W);
             }
         }
     }
@@ -467,8 +447,7 @@ __global__ __launch_bounds__(NT) void fir_tile_kernel(typename fir_args<XT>::typ
 // Any (T, W) without a specialised tile kernel: the reference's formula
 // itself, full complex products included (not on the benchmarked path).
 template <typename XT>
-__global__ __launch_bounds__(256) void fir_generic_kernel(typename fir_args<XT>::type a, const float *hrev, int T,
-                                                          int W) {
+__global__ __launch_bounds__(256) void fir_generic_kernel(FirArgs a, const float *hrev, int T, int W) {
     const int s = blockIdx.y;
     const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const int64_t n = a.lengths ? a.lengths[s] : a.n;
@@ -479,10 +458,7 @@ __global__ __launch_bounds__(256) void fir_generic_kernel(typename fir_args<XT>:
     const XT *x = reinterpret_cast<const XT *>(a.x) + s * a.x_stride;
     const f2 *hist = reinterpret_cast<const f2 *>(a.hist) + static_cast<int64_t>(s) * (T - 1);
     const int64_t w0 = t - T + 1;
-    auto xs = [&](int k) -> f2 {
-        const int64_t g = w0 + k;
-        return g < 0 ? hist[T - 1 + g] : load_xa(x, g, a);
-    };
+    auto xs = [&](int k) -> f2 { return row_sample(x, hist, T - 1, w0 + k, a); };
     f2 *y = reinterpret_cast<f2 *>(a.y) + s * a.y_stride + a.y_offset;
     y[t] = fir_exact_one(xs, hrev, T, W);
 }
@@ -490,7 +466,7 @@ __global__ __launch_bounds__(256) void fir_generic_kernel(typename fir_args<XT>:
 // new_hist = last (T-1) samples of concat(old_hist, x[0..n)); the history is
 // float whatever the input format (CS16 and 8-bit samples enter it widened)
 template <typename XT>
-__global__ void fir_hist_kernel(typename fir_args<XT>::type a, float *hist_new, int H, int S) {
+__global__ void fir_hist_kernel(FirArgs a, float *hist_new, int H, int S) {
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (idx >= static_cast<int64_t>(S) * H) return;
     const int s = static_cast<int>(idx / H);
@@ -500,7 +476,7 @@ __global__ void fir_hist_kernel(typename fir_args<XT>::type a, float *hist_new, 
     const f2 *ho = reinterpret_cast<const f2 *>(a.hist) + static_cast<int64_t>(s) * H;
     f2 *hn = reinterpret_cast<f2 *>(hist_new) + static_cast<int64_t>(s) * H;
     const int64_t m = n + k;
-    hn[k] = m < H ? ho[m] : load_xa(x, m - H, a);
+    hn[k] = m < H ? ho[m] : Sample<XT>::one(x, m - H, a);
 }
 
 // ---------------------------------------------------------------------------
@@ -674,183 +650,120 @@ void launch_append(const AppendArgs &a, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------
-// CS16 -> float2 rows ahead of the serial pre-stages (IQ balancer, FLL)
+// CS16 / 8-bit -> float2 rows ahead of the serial pre-stages (IQ balancer, FLL)
 // ---------------------------------------------------------------------------
-// 16-B loads (4 samples) and two 16-B stores per thread where the rows allow,
-// 4-B loads and 8-B stores otherwise.
-template <bool VEC>
+// One 16-B load (L = 4 CS16 or 8 8-bit samples) and L / 2 16-B stores per
+// thread where the rows allow, one sample per thread otherwise.
+template <typename XT, bool VEC>
 __global__ __launch_bounds__(256) void widen_kernel(WidenArgs a) {
     const int s = blockIdx.y;
     const int64_t n = a.lengths ? a.lengths[s] : a.n;
-    const s2 *x = reinterpret_cast<const s2 *>(a.x) + s * a.x_stride;
+    const XT *x = reinterpret_cast<const XT *>(a.x) + s * a.x_stride;
     f2 *y = reinterpret_cast<f2 *>(a.y) + s * a.y_stride + a.y_offset;
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if constexpr (VEC) {
-        const int64_t g = 4 * i;
-        if (g + 3 < n) {
-            const s8 v = *reinterpret_cast<const s8 *>(x + g);
-            const f2 u0 = widen(s2{v[0], v[1]}, a.scale), u1 = widen(s2{v[2], v[3]}, a.scale);
-            const f2 u2 = widen(s2{v[4], v[5]}, a.scale), u3 = widen(s2{v[6], v[7]}, a.scale);
-            *reinterpret_cast<f4 *>(y + g) = f4{u0.x, u0.y, u1.x, u1.y};
-            *reinterpret_cast<f4 *>(y + g + 2) = f4{u2.x, u2.y, u3.x, u3.y};
-        } else {
-            for (int64_t k = g; k < n; ++k) y[k] = widen(x[k], a.scale);
-        }
-    } else {
-        if (i < n) y[i] = widen(x[i], a.scale);
-    }
-}
-
-// 8-bit rows: a 16-B load (8 samples) and four 16-B stores per thread where the
-// rows allow, 2-B loads and 8-B stores otherwise.
-template <bool VEC>
-__global__ __launch_bounds__(256) void widen8_kernel(WidenArgs a, unsigned flip) {
-    const int s = blockIdx.y;
-    const int64_t n = a.lengths ? a.lengths[s] : a.n;
-    const b2 *x = reinterpret_cast<const b2 *>(a.x) + s * a.x_stride;
-    f2 *y = reinterpret_cast<f2 *>(a.y) + s * a.y_stride + a.y_offset;
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if constexpr (VEC) {
-        const int64_t g = 8 * i;
-        if (g + 7 < n) {
-            const u4 v = *reinterpret_cast<const u4 *>(x + g) ^ flip;
+        constexpr int L = Sample<XT>::kWide;
+        const int64_t g = L * i;
+        if (g + L - 1 < n) {
+            f2 u[L];
+            Sample<XT>::many(x, g, a, u);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                f2 u0, u1;
-                widen8(v[k], a.scale, u0, u1);
-                *reinterpret_cast<f4 *>(y + g + 2 * k) = f4{u0.x, u0.y, u1.x, u1.y};
-            }
+            for (int k = 0; k < L; k += 2)
+                *reinterpret_cast<f4 *>(y + g + k) = f4{u[k].x, u[k].y, u[k + 1].x, u[k + 1].y};
         } else {
-            for (int64_t k = g; k < n; ++k) y[k] = widen(x[k], a.scale, flip);
+            for (int64_t k = g; k < n; ++k) y[k] = Sample<XT>::one(x, k, a);
         }
     } else {
-        if (i < n) y[i] = widen(x[i], a.scale, flip);
+        if (i < n) y[i] = Sample<XT>::one(x, i, a);
     }
 }
 
-static unsigned flip_of(int32_t fmt) { return fmt == kFmtCs8 ? 0x80808080u : 0u; }
-
-void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream, int32_t x_fmt) {
+void launch_widen(const WidenArgs &a0, int S, int64_t n_max, hipStream_t stream, int32_t x_fmt) {
     if (n_max <= 0 || S <= 0) return;
-    if (x_fmt == kFmtCs8 || x_fmt == kFmtCu8) {
-        const bool vec8 = ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.x_stride % 8 == 0) &&
-                          ((reinterpret_cast<uintptr_t>(a.y) & 15) == 0) && (a.y_stride % 2 == 0) &&
-                          (a.y_offset % 2 == 0);
-        const int64_t items = vec8 ? (n_max + 7) / 8 : n_max;
-        dim3 grid(static_cast<unsigned>((items + 255) / 256), static_cast<unsigned>(S));
-        if (vec8) hipLaunchKernelGGL(widen8_kernel<true>, grid, dim3(256), 0, stream, a, flip_of(x_fmt));
-        else hipLaunchKernelGGL(widen8_kernel<false>, grid, dim3(256), 0, stream, a, flip_of(x_fmt));
-        return;
-    }
-    const bool vec = ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.x_stride % 4 == 0) &&
-                     ((reinterpret_cast<uintptr_t>(a.y) & 15) == 0) && (a.y_stride % 2 == 0) &&
-                     (a.y_offset % 2 == 0);
-    const int threads = 256;
-    const int64_t items = vec ? (n_max + 3) / 4 : n_max;
-    dim3 grid(static_cast<unsigned>((items + threads - 1) / threads), static_cast<unsigned>(S));
-    if (vec) hipLaunchKernelGGL(widen_kernel<true>, grid, dim3(threads), 0, stream, a);
-    else hipLaunchKernelGGL(widen_kernel<false>, grid, dim3(threads), 0, stream, a);
+    WidenArgs a = a0;
+    a.x_flip = flip_of(x_fmt);
+    with_format(x_fmt, [&](auto tag) {
+        typedef decltype(tag) XT;
+        if constexpr (!same_type<XT, f2>::value) {   // float rows are what the pre-stages read
+            constexpr int L = Sample<XT>::kWide;
+            const bool vec = rows_aligned(a.x, a.x_stride, 0, L, sizeof(XT)) &&
+                             rows_aligned(a.y, a.y_stride, a.y_offset, 2, sizeof(f2));
+            const int64_t items = vec ? (n_max + L - 1) / L : n_max;
+            dim3 grid(static_cast<unsigned>((items + 255) / 256), static_cast<unsigned>(S));
+            if (vec) hipLaunchKernelGGL((widen_kernel<XT, true>), grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((widen_kernel<XT, false>), grid, dim3(256), 0, stream, a);
+        }
+    });
 }
 
 // ---------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------
-// vec: float rows 16-B aligned, even stride (2 samples a load).  CS16 rows take
-// their own rule (launch_fir): 16-B aligned, stride a multiple of 4 samples and
-// T = 1 mod 4 (4 samples a load), which every specialised tap count meets.
-template <int T, int NT, typename XT>
-static void launch_fir_w8_nt(const typename fir_args<XT>::type &a, const float *hrev, int S,
-                             int64_t n_max, bool vec, hipStream_t stream) {
-    constexpr int Q = 8;
+// 2048-output tiles; 1024- and 512-output tiles (128 / 64 threads, more
+// workgroups beside the loop kernel's) measured the same at C3 and C2
+// (pipelined bench, A/B x2 on one MI355X), and so did a
+// work-sharing tile whose waves take 512-output units from an LDS counter
+// (profiles/archive/r02_fir_share_ab.txt)
+template <int T>
+static bool launch_fir_w8(const FirArgs &a, int32_t x_fmt, const float *hrev, int S, int64_t n_max,
+                          hipStream_t stream) {
+    constexpr int Q = 8, NT = kFirThreads;
     const int64_t tiles = (n_max + NT * Q - 1) / (NT * Q);
     dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(S));
-    constexpr bool kVecOk = same_type<XT, f2>::value || (T - 1) % 4 == 0;   // CS16 and 8-bit rows alike
-    if constexpr (kVecOk) {
-        if (vec) {
-            hipLaunchKernelGGL((fir_tile_kernel<T, 8, Q, true, NT, XT>), grid, dim3(NT), 0, stream, a, hrev);
-            return;
+    with_format(x_fmt, [&](auto tag) {
+        typedef decltype(tag) XT;
+        if constexpr (Sample<XT>::vec_supported(T)) {
+            if (Sample<XT>::vec_ok(a, T)) {
+                hipLaunchKernelGGL((fir_tile_kernel<T, 8, Q, true, NT, XT>), grid, dim3(NT), 0, stream, a, hrev);
+                return;
+            }
         }
-    }
-    hipLaunchKernelGGL((fir_tile_kernel<T, 8, Q, false, NT, XT>), grid, dim3(NT), 0, stream, a, hrev);
-}
-
-template <int T>
-static bool launch_fir_w8(const FirArgsI8 &a, int32_t x_fmt, const float *hrev, int S,
-                          int64_t n_max, bool vec, hipStream_t stream) {
-    // 2048-output tiles; 1024- and 512-output tiles (128 / 64 threads, more
-    // workgroups beside the loop kernel's) measured the same at C3 and C2
-    // (pipelined bench, A/B x2 on one MI355X), and so did a
-    // work-sharing tile whose waves take 512-output units from an LDS counter
-    // (profiles/archive/r02_fir_share_ab.txt)
-    if (x_fmt == kFmtCs16) launch_fir_w8_nt<T, kFirThreads, s2>(static_cast<const FirArgsCs16 &>(a), hrev, S, n_max, vec, stream);
-    else if (x_fmt != kFmtCf32) launch_fir_w8_nt<T, kFirThreads, b2>(a, hrev, S, n_max, vec, stream);
-    else launch_fir_w8_nt<T, kFirThreads, f2>(static_cast<const FirArgs &>(a), hrev, S, n_max, vec, stream);
+        hipLaunchKernelGGL((fir_tile_kernel<T, 8, Q, false, NT, XT>), grid, dim3(NT), 0, stream, a, hrev);
+    });
     return true;
 }
 
 bool launch_fir(const FirArgs &a0, const float *hrev_dev, int T, int W, int S,
                 int64_t n_max, hipStream_t stream, int32_t x_fmt, float x_scale) {
     if (n_max <= 0 || S <= 0) return true;
-    const bool cs16 = x_fmt == kFmtCs16;
-    const bool i8 = x_fmt == kFmtCs8 || x_fmt == kFmtCu8;
-    FirArgsI8 a{};
-    static_cast<FirArgs &>(a) = a0;
+    FirArgs a = a0;
     a.x_scale = x_scale;
     a.x_flip = flip_of(x_fmt);
-    // 8-bit rows: 16-B loads of 8 samples where T - 1 is a multiple of 8, else
-    // (T = 13, 21) 8-B loads of 4; the rows must be aligned to the load and
-    // keep that alignment from row to row
-    const int l8 = (T - 1) % 8 == 0 ? 8 : 4;
-    const bool vec = i8 ? (T % 4 == 1) && (reinterpret_cast<uintptr_t>(a.x) % (2 * l8) == 0) && (a.x_stride % l8 == 0)
-                     : cs16 ? (T % 4 == 1) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.x_stride % 4 == 0)
-                          : (T % 2 == 1) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) &&
-                                (a.x_stride % 2 == 0) && ((reinterpret_cast<uintptr_t>(a.y) & 15) == 0) &&
-                                (a.y_stride % 2 == 0) && (a.y_offset % 2 == 0);
     if (W == 8) {
         switch (T) {
-        case 13: return launch_fir_w8<13>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
-        case 17: return launch_fir_w8<17>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
-        case 21: return launch_fir_w8<21>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
-        case 33: return launch_fir_w8<33>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
-        case 41: return launch_fir_w8<41>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
-        case 49: return launch_fir_w8<49>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
-        case 65: return launch_fir_w8<65>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
-        case 97: return launch_fir_w8<97>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
-        case 129: return launch_fir_w8<129>(a, x_fmt, hrev_dev, S, n_max, vec, stream);
+        case 13: return launch_fir_w8<13>(a, x_fmt, hrev_dev, S, n_max, stream);
+        case 17: return launch_fir_w8<17>(a, x_fmt, hrev_dev, S, n_max, stream);
+        case 21: return launch_fir_w8<21>(a, x_fmt, hrev_dev, S, n_max, stream);
+        case 33: return launch_fir_w8<33>(a, x_fmt, hrev_dev, S, n_max, stream);
+        case 41: return launch_fir_w8<41>(a, x_fmt, hrev_dev, S, n_max, stream);
+        case 49: return launch_fir_w8<49>(a, x_fmt, hrev_dev, S, n_max, stream);
+        case 65: return launch_fir_w8<65>(a, x_fmt, hrev_dev, S, n_max, stream);
+        case 97: return launch_fir_w8<97>(a, x_fmt, hrev_dev, S, n_max, stream);
+        case 129: return launch_fir_w8<129>(a, x_fmt, hrev_dev, S, n_max, stream);
         default: break;
         }
     }
     const int threads = 256;
     dim3 grid(static_cast<unsigned>((n_max + threads - 1) / threads), static_cast<unsigned>(S));
-    if (cs16)
-        hipLaunchKernelGGL(fir_generic_kernel<s2>, grid, dim3(threads), 0, stream, static_cast<const FirArgsCs16 &>(a),
-                           hrev_dev, T, W);
-    else if (i8) hipLaunchKernelGGL(fir_generic_kernel<b2>, grid, dim3(threads), 0, stream, a, hrev_dev, T, W);
-    else hipLaunchKernelGGL(fir_generic_kernel<f2>, grid, dim3(threads), 0, stream, a0, hrev_dev, T, W);
+    with_format(x_fmt, [&](auto tag) {
+        hipLaunchKernelGGL(fir_generic_kernel<decltype(tag)>, grid, dim3(threads), 0, stream, a, hrev_dev, T, W);
+    });
     return false;
 }
 
-void launch_fir_hist(const FirArgs &a, float *hist_new, int H, int S, hipStream_t stream, int32_t x_fmt,
+void launch_fir_hist(const FirArgs &a0, float *hist_new, int H, int S, hipStream_t stream, int32_t x_fmt,
                      float x_scale) {
     if (H <= 0 || S <= 0) return;
+    FirArgs a = a0;
+    a.x_scale = x_scale;
+    a.x_flip = flip_of(x_fmt);
     const int64_t total = static_cast<int64_t>(S) * H;
     const int threads = 256;
     const dim3 grid(static_cast<unsigned>((total + threads - 1) / threads));
-    if (x_fmt == kFmtCs16) {
-        FirArgsCs16 c{};
-        static_cast<FirArgs &>(c) = a;
-        c.x_scale = x_scale;
-        hipLaunchKernelGGL(fir_hist_kernel<s2>, grid, dim3(threads), 0, stream, c, hist_new, H, S);
-    } else if (x_fmt == kFmtCs8 || x_fmt == kFmtCu8) {
-        FirArgsI8 c{};
-        static_cast<FirArgs &>(c) = a;
-        c.x_scale = x_scale;
-        c.x_flip = flip_of(x_fmt);
-        hipLaunchKernelGGL(fir_hist_kernel<b2>, grid, dim3(threads), 0, stream, c, hist_new, H, S);
-    } else
-        hipLaunchKernelGGL(fir_hist_kernel<f2>, grid, dim3(threads), 0, stream, a, hist_new, H, S);
+    with_format(x_fmt, [&](auto tag) {
+        hipLaunchKernelGGL(fir_hist_kernel<decltype(tag)>, grid, dim3(threads), 0, stream, a, hist_new, H, S);
+    });
 }
-
 
 void launch_fll(const FllArgs &a, const FllParams &P, hipStream_t stream) {
     // the systolic 8-lane kernel (qpsk_fll.hip) for the reference's Vector<float>

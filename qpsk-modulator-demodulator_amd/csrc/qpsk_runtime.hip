@@ -373,7 +373,7 @@ const float *float_rows(qpsk_demod *h, InRows *in, const int64_t *d_len, int64_t
         wa.x = in->x; wa.x_stride = in->stride;
         wa.y = mf; wa.y_stride = h->mf_stride; wa.y_offset = kMfPrefix;
         wa.lengths = d_len; wa.n = n_call;
-        wa.scale = in->scale;
+        wa.x_scale = in->scale;
         launch_widen(wa, h->S, n_call, st, in->fmt);
         *in = InRows{mf + 2 * kMfPrefix, h->mf_stride, kFmtCf32, 0.0f};
     }

@@ -49,7 +49,8 @@ FMT_CF32 = 0
 FMT_CS16 = 1
 FMT_CS8 = 2
 FMT_CU8 = 3
-# name -> (QPSK_FMT_*, numpy dtype of a row's elements, ctypes type)
+# name -> (QPSK_FMT_*, numpy dtype of a row's elements, ctypes type): the one
+# table of per-format facts (_torch_dtype derives a tensor's dtype from it)
 _FORMATS = {"cf32": (FMT_CF32, np.float32, C.c_float), "cs16": (FMT_CS16, np.int16, C.c_int16),
             "cs8": (FMT_CS8, np.int8, C.c_int8), "cu8": (FMT_CU8, np.uint8, C.c_uint8)}
 
@@ -60,6 +61,32 @@ def _format(fmt):
         if fmt == name or (not isinstance(fmt, str) and fmt == rec[0]):
             return rec
     raise ValueError("fmt must be 'cf32', 'cs16', 'cs8' or 'cu8'")
+
+
+def _torch_dtype(fmt):
+    """The torch dtype of a format's elements: the numpy dtype's namesake
+    (torch is imported here, on first use, not with the module)."""
+    import torch
+    return getattr(torch, np.dtype(_format(fmt)[1]).name)
+
+
+def _host_call(fn, handle, n_streams, max_syms, iq, mode, lengths, want_syms):
+    """One host call of a process entry point fn (a handle's or a group's) on
+    checked [S, 2n] rows: allocates the output rows for up to max_syms symbols
+    a stream and returns (bits, n_bits, syms or None, n_syms)."""
+    ms = max(int(max_syms), 1)
+    bstride = (2 * ms + 7) // 8 + 8
+    bits = np.zeros((n_streams, bstride), dtype=np.uint8)
+    n_bits = np.zeros(n_streams, dtype=np.int64)
+    n_syms = np.zeros(n_streams, dtype=np.int64)
+    syms = np.zeros((n_streams, 2 * ms), dtype=np.float32) if (want_syms or mode == MODE_CONSTELLATION) else None
+    _check(fn(
+        handle, int(mode), iq.ctypes.data if iq.size else None, iq.shape[1], iq.shape[1] // 2,
+        lengths.ctypes.data_as(_i64p) if lengths is not None else None, MEM_HOST,
+        bits.ctypes.data if mode == MODE_DEMODULATE else None, bstride,
+        n_bits.ctypes.data if mode == MODE_DEMODULATE else None,
+        syms.ctypes.data if syms is not None else None, 2 * ms, n_syms.ctypes.data))
+    return bits, n_bits, syms, n_syms
 
 
 def fmt_sample_bytes(fmt: int) -> int:
@@ -655,25 +682,12 @@ class BatchDemodulator:
                 raise ValueError("a length exceeds the row (iq.shape[1] // 2 samples)")
         else:
             nmax = n
-        ms = max(self.max_symbols(nmax), 1)
-        bstride = (2 * ms + 7) // 8 + 8
-        bits = np.zeros((self.S, bstride), dtype=np.uint8)
-        n_bits = np.zeros(self.S, dtype=np.int64)
-        n_syms = np.zeros(self.S, dtype=np.int64)
-        syms = np.zeros((self.S, 2 * ms), dtype=np.float32) if (want_syms or mode == MODE_CONSTELLATION) else None
-        _check(fn(
-            self._h, int(mode), iq.ctypes.data if iq.size else None, iq.shape[1], n,
-            lengths.ctypes.data_as(_i64p) if lengths is not None else None, MEM_HOST,
-            bits.ctypes.data if mode == MODE_DEMODULATE else None, bstride,
-            n_bits.ctypes.data if mode == MODE_DEMODULATE else None,
-            syms.ctypes.data if syms is not None else None, 2 * ms,
-            n_syms.ctypes.data))
-        return bits, n_bits, syms, n_syms
+        return _host_call(fn, self._h, self.S, self.max_symbols(nmax), iq, mode, lengths, want_syms)
 
     # ---- device path (torch tensors resident in HBM) ---------------------
     def _check_device_args(self, iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev, fmt=FMT_CF32):
         import torch
-        want = {FMT_CF32: torch.float32, FMT_CS16: torch.int16, FMT_CS8: torch.int8, FMT_CU8: torch.uint8}[fmt]
+        want = _torch_dtype(fmt)
         if iq_dev.dtype != want or iq_dev.dim() != 2 or iq_dev.shape[0] != self.S:
             raise ValueError(f"iq_dev must be a {want} [n_streams, >= 2n] tensor")
         if iq_dev.stride(1) != 1 or iq_dev.shape[1] < 2 * int(n):
@@ -690,35 +704,16 @@ class BatchDemodulator:
         """All arguments are torch CUDA tensors; stream-ordered on the handle's
         stream (bind torch's stream with set_stream first; without it the call
         first waits for torch's current stream)."""
-        self._check_device_args(iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev)
-        self._after_torch(iq_dev)
-        bstride = bits_dev.stride(0) * bits_dev.element_size() if bits_dev is not None else 0
-        sstride = syms_dev.stride(0) if syms_dev is not None else 0
-        _check(lib().qpsk_demod_process(
-            self._h, int(mode), iq_dev.data_ptr(), iq_dev.stride(0), int(n), None, MEM_DEVICE,
-            bits_dev.data_ptr() if bits_dev is not None else None, bstride,
-            n_bits_dev.data_ptr() if n_bits_dev is not None else None,
-            syms_dev.data_ptr() if syms_dev is not None else None, sstride,
-            n_syms_dev.data_ptr() if n_syms_dev is not None else None))
+        self._device_call(lib().qpsk_demod_process, FMT_CF32, iq_dev, n, bits_dev, n_bits_dev, mode, syms_dev,
+                          n_syms_dev, None, False)
 
     def process_device_async(self, iq_dev, n, bits_dev, n_bits_dev, mode=MODE_DEMODULATE,
                              syms_dev=None, n_syms_dev=None, lengths=None):
         """Pipelined call (qpsk_demod_process_async): returns once queued; the
         outputs are complete after pipeline_wait().  lengths: optional host
         int64 array of per-stream sample counts."""
-        self._check_device_args(iq_dev, n, bits_dev, n_bits_dev, syms_dev, n_syms_dev)
-        self._after_torch(iq_dev)
-        bstride = bits_dev.stride(0) * bits_dev.element_size() if bits_dev is not None else 0
-        sstride = syms_dev.stride(0) if syms_dev is not None else 0
-        if lengths is not None:
-            lengths = np.ascontiguousarray(lengths, dtype=np.int64)
-        _check(lib().qpsk_demod_process_async(
-            self._h, int(mode), iq_dev.data_ptr(), iq_dev.stride(0), int(n),
-            lengths.ctypes.data_as(_i64p) if lengths is not None else None,
-            bits_dev.data_ptr() if bits_dev is not None else None, bstride,
-            n_bits_dev.data_ptr() if n_bits_dev is not None else None,
-            syms_dev.data_ptr() if syms_dev is not None else None, sstride,
-            n_syms_dev.data_ptr() if n_syms_dev is not None else None))
+        self._device_call(lib().qpsk_demod_process_async, FMT_CF32, iq_dev, n, bits_dev, n_bits_dev, mode,
+                          syms_dev, n_syms_dev, lengths, True)
 
     def pipeline_wait(self, hip_stream_ptr: int | None = None):
         """hip_stream_ptr waits for every pipelined call (None: block the host)."""
@@ -815,19 +810,7 @@ class DemodGroup:
             nmax = int(lengths.max()) if lengths.size else 0
         else:
             nmax = n
-        ms = max(self.max_symbols(nmax), 1)
-        bstride = (2 * ms + 7) // 8 + 8
-        bits = np.zeros((self.S, bstride), dtype=np.uint8)
-        n_bits = np.zeros(self.S, dtype=np.int64)
-        n_syms = np.zeros(self.S, dtype=np.int64)
-        syms = np.zeros((self.S, 2 * ms), dtype=np.float32) if (want_syms or mode == MODE_CONSTELLATION) else None
-        _check(fn(
-            self._g, int(mode), iq.ctypes.data if iq.size else None, iq.shape[1], n,
-            lengths.ctypes.data_as(_i64p) if lengths is not None else None, MEM_HOST,
-            bits.ctypes.data if mode == MODE_DEMODULATE else None, bstride,
-            n_bits.ctypes.data if mode == MODE_DEMODULATE else None,
-            syms.ctypes.data if syms is not None else None, 2 * ms, n_syms.ctypes.data))
-        return bits, n_bits, syms, n_syms
+        return _host_call(fn, self._g, self.S, self.max_symbols(nmax), iq, mode, lengths, want_syms)
 
     def process_device(self, iq_dev, n, bits_dev, n_bits_dev, mode=MODE_DEMODULATE, syms_dev=None,
                        n_syms_dev=None):
@@ -841,9 +824,8 @@ class DemodGroup:
                            n_syms_dev=None):
         """process_device() on device rows of any format (a tensor of the
         format's element type)."""
-        import torch
         tag = _format(fmt)[0]
-        want = {FMT_CF32: torch.float32, FMT_CS16: torch.int16, FMT_CS8: torch.int8, FMT_CU8: torch.uint8}[tag]
+        want = _torch_dtype(tag)
         if iq_dev.dtype != want:
             raise ValueError(f"process_device_fmt({fmt!r}) takes a {want} tensor")
         fn = lib().qpsk_demod_group_process_fmt
