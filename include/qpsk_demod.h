@@ -247,7 +247,8 @@ int32_t qpsk_demod_pick_loop_variant(int32_t requested, int32_t n_streams, doubl
  * a requested loop_variant (through qpsk_demod_pick_loop_variant and the
  * launcher's own rule for what that leaves at 0), on a device of cus CUs
  * (0 = unknown) with a matched filter of rrc_taps taps (rrc_span * sps + 1),
- * for costas_trig 0 / 1 and with (1) or without (0) symbol output.  The
+ * for costas_trig 0 / 1 and with (1) or without (0) symbol output (a handle
+ * with link statistics enabled runs the with-symbols form in every call).  The
  * launcher's rule: at 4 <= sps < 8 and costas_trig 0, 64 streams x 64-sample
  * rounds on the two-slot ring where n_streams * rrc_taps >= cus * 16 * 129
  * (the matched filter of the next pipelined call sets the step: C3), else
@@ -369,6 +370,60 @@ int qpsk_demod_set_state(qpsk_demod *h, const void *host_buf, int64_t buf_bytes)
 int qpsk_state_blob_check(const qpsk_demod_params *p, int32_t n_streams, const void *buf, int64_t buf_bytes);
 
 /* ---------------------------------------------------------------------------
+ * Per-stream link statistics: which of the batch's receivers are locked, in 64
+ * bytes a stream, without symbol rows and without the state blob.  (Added
+ * within ABI version 3: no existing entry point or the blob layout changed.)
+ *
+ * The reference computes each symbol's squared distance to its decision and
+ * drops it (QPSKDeModulator.cs:381-384), and offers the Costas NCO state
+ * through CostasLoopQpsk.GetState() (CostasLoopQpsk.cs:127-130).  While
+ * statistics are enabled, every symbol the Costas loop produces adds to three
+ * running sums of its stream.  Per symbol, in float, one rounding per
+ * operation (no fused multiply-add):
+ *     dec  = rot >= 0 ? 1 : -1          (GetSign, so a NaN gives -1), I and Q
+ *     e    = rot - dec
+ *     dist2 = eI*eI + eQ*eQ
+ *     pw    = rotI*rotI + rotQ*rotQ
+ * then sum_dist2 += (double)dist2 and sum_power += (double)pw, in symbol order
+ * from the running value.  The sums therefore do not depend on how the
+ * samples were cut into calls or internal chunks.  They run across calls
+ * (synchronous, chunked, pipelined, through a qpsk_rx ring or a group) until a
+ * read resets them; a host that wants per-call figures reads with reset = 1
+ * after each call.  Both modes count, and a symbol counts even where a symbol
+ * row hit its capacity.  A stream with no samples in a call is untouched.
+ * qpsk_demod_set_state leaves the sums alone.  No thresholds are applied: the
+ * host judges mean dist2 against mean power and |costas_freq|.
+ */
+typedef struct qpsk_link_stats {      /* 64 bytes, no padding */
+    int64_t n_symbols;    /* symbols the Costas loop produced since the last reset           */
+    double  sum_dist2;    /* sum of (double)dist2, dist2 in float as QPSKDeModulator.cs:381-384 */
+    double  sum_power;    /* sum of (double)(rotI*rotI + rotQ*rotQ), the products and the add in float */
+    double  costas_freq;  /* CostasLoopQpsk.GetState().freq  (rad/symbol) after the last call */
+    double  costas_theta; /* ... .theta                                                       */
+    double  mm_mu;        /* MuellerMuller.mu                                                 */
+    double  mm_rate;      /* MuellerMuller.ncoIntegral                                        */
+    float   fll_freq;     /* Band-Edge FLL freq (0 with the FLL off)                          */
+    int32_t error;        /* the stream record's sticky `error`, as get_state returns it      */
+} qpsk_link_stats;
+/* sizeof(qpsk_link_stats) = 64; needs no device. */
+int qpsk_link_stats_size(void);
+/* Waits for every queued call (as qpsk_demod_set_stream does), then turns the
+ * statistics on or off.  Turning them on, also when they are on already,
+ * zeroes the three sums of every stream.  While they are off (the default)
+ * every launch is exactly what it is without this feature.  While they are on,
+ * the symbol loop runs its symbol-carrying form whether or not a call asks for
+ * symbol rows (results are identical; DESIGN.md 3.11 has the cost). */
+int qpsk_demod_enable_link_stats(qpsk_demod *h, int32_t on);
+/* Waits for every queued call (as qpsk_demod_status does), then writes one row
+ * per stream to out: host memory (mem = QPSK_MEM_HOST) or device memory
+ * (QPSK_MEM_DEVICE; 8-byte aligned, else QPSK_ERR_ARGUMENT; written in order
+ * on the handle's stream).  reset != 0 then zeroes the three sums; the loop
+ * state fields are a copy of the state and are never reset.  QPSK_ERR_STATE
+ * while statistics are not enabled.  Like qpsk_demod_status it may be called
+ * on a handle that feeds a qpsk_rx ring. */
+int qpsk_demod_link_stats(qpsk_demod *h, qpsk_link_stats *out, int32_t mem, int32_t reset);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU group: one batch of n_streams over several GPUs,
  * for a host (the C# shim, a C++ driver) that wants the whole node behind one
  * object.  Every reference instance owns its loop state (QPSKDeModulator.cs:20-73),
@@ -415,6 +470,10 @@ int qpsk_demod_group_process(qpsk_demod_group *g, int32_t mode, const float *iq,
 int64_t qpsk_demod_group_state_bytes(const qpsk_demod_group *g, int32_t k);
 int qpsk_demod_group_get_state(qpsk_demod_group *g, int32_t k, void *host_buf, int64_t buf_bytes);
 int qpsk_demod_group_set_state(qpsk_demod_group *g, int32_t k, const void *host_buf, int64_t buf_bytes);
+/* qpsk_demod_enable_link_stats / qpsk_demod_link_stats on every shard: the
+ * rows of all n_streams streams in stream order, in host memory. */
+int qpsk_demod_group_enable_link_stats(qpsk_demod_group *g, int32_t on);
+int qpsk_demod_group_link_stats(qpsk_demod_group *g, qpsk_link_stats *out_host, int32_t reset);
 
 /* ---------------------------------------------------------------------------
  * Host-fed streaming front-end: the deployment shape of

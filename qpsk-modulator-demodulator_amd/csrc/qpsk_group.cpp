@@ -259,4 +259,18 @@ int qpsk_demod_group_set_state(qpsk_demod_group *g, int32_t k, const void *host_
     return qpsk_demod_set_state(g->shards[k].h, host_buf, buf_bytes);
 }
 
+int qpsk_demod_group_enable_link_stats(qpsk_demod_group *g, int32_t on) {
+    if (!g) return fail(QPSK_ERR_ARGUMENT_NULL, "null group");
+    return fan_out(g, [=](int k) { return qpsk_demod_enable_link_stats(g->shards[k].h, on); });
+}
+
+int qpsk_demod_group_link_stats(qpsk_demod_group *g, qpsk_link_stats *out_host, int32_t reset) {
+    if (!g || !out_host) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    // shard k's rows land at its first stream: stream order over the batch
+    return fan_out(g, [=](int k) {
+        const Shard &sh = g->shards[k];
+        return qpsk_demod_link_stats(sh.h, out_host + sh.first, QPSK_MEM_HOST, reset);
+    });
+}
+
 }  // extern "C"

@@ -108,6 +108,14 @@ struct WidenArgs {
     uint32_t x_flip;       // set by the launcher
 };
 
+// Per-stream link statistics (qpsk_demod_link_stats): the running sums the
+// decode wave forms from the rotated symbols, one record per stream.
+struct LinkAcc {
+    double sum_dist2;      // sum of (double)dist2, dist2 in float
+    double sum_power;      // sum of (double)(rotI*rotI + rotQ*rotQ)
+    int64_t n;             // symbols the Costas loop produced
+};
+
 struct LoopArgs {
     float *mf;             // [S][mf_stride] float2, MF output at kMfPrefix
     int64_t mf_stride;
@@ -124,9 +132,11 @@ struct LoopArgs {
     int64_t syms_cap;
     int64_t *n_syms;
     int S;
+    uint32_t link_lo;      // link(), low word
     unsigned long long *probe;   // diagnostic cycle stamps (QPSK_LOOP_STAMPS builds only)
     uint32_t *flags;       // per-handle OR of QPSK_STATUS_* raised by this call (or nullptr)
     int chunked;           // 1: an internal chunk of a longer call (StreamState.tofs runs on)
+    uint32_t link_hi;      // link(), high word
     unsigned long long *kt;   // launch timestamps or nullptr
     // residency counter (signal memory) or nullptr: every workgroup adds 1 as it
     // starts, so the next pipelined call's FIR can wait until the loop kernel
@@ -136,6 +146,31 @@ struct LoopArgs {
     // or nullptr: cu_map[cu_key()] counts the workgroups of this launch that
     // hold that CU (FIR phase sample, FirArgs.phases)
     unsigned *cu_map;
+    // [S] running sums, or nullptr (statistics off).  With it the launcher takes
+    // the symbol-carrying instantiation whether or not syms is set, and the
+    // decode wave adds every symbol of the call to its stream's record.  The
+    // pointer is kept as two words in what were the struct's two padding
+    // words: a member behind cu_map would move LoopParams and the hidden
+    // arguments (gridDim) in the kernel argument block, and with them loads of
+    // the bits-only instantiations, which read none of this
+    __host__ __device__ LinkAcc *link() const {
+        return reinterpret_cast<LinkAcc *>((static_cast<uint64_t>(link_hi) << 32) | link_lo);
+    }
+    void set_link(LinkAcc *p) {
+        link_lo = static_cast<uint32_t>(reinterpret_cast<uint64_t>(p));
+        link_hi = static_cast<uint32_t>(reinterpret_cast<uint64_t>(p) >> 32);
+    }
+};
+static_assert(sizeof(LoopArgs) == 176, "LoopParams and the hidden kernel arguments follow at fixed offsets");
+
+// qpsk_link_stats rows composed from the stream records and the accumulators
+struct LinkGatherArgs {
+    const StreamState *state;
+    LinkAcc *acc;
+    void *out;             // [S] qpsk_link_stats (8-byte aligned)
+    int S;
+    int fll;               // the handle runs the FLL (else fll_freq reads 0)
+    int reset;             // zero the accumulators behind the read
 };
 
 // One internal chunk's rows appended behind what earlier chunks of the same
@@ -199,6 +234,7 @@ int launch_loop(const LoopArgs &a, const LoopParams &P, int mode, int variant, h
 // (qpsk_demod_loop_shape)
 void loop_shape_info(int variant, int S, double sps, int cus, int taps, int trig, int syms, qpsk_loop_shape *out);
 void launch_append(const AppendArgs &a, hipStream_t stream);
+void launch_link_gather(const LinkGatherArgs &a, hipStream_t stream);
 void launch_iq_balance(const IqbArgs &a, hipStream_t stream);
 void launch_fll(const FllArgs &a, const FllParams &P, hipStream_t stream);
 void launch_fll_sys(const FllArgs &a, const FllParams &P, hipStream_t stream);   // qpsk_fll.hip

@@ -20,6 +20,7 @@
 
 #include <cstdint>
 
+#include "qpsk_demod.h"
 #include "qpsk_kernels.h"
 #include "qpsk_sincos.h"
 
@@ -647,6 +648,35 @@ __global__ __launch_bounds__(256) void append_rows_kernel(AppendArgs a) {
 
 void launch_append(const AppendArgs &a, hipStream_t stream) {
     hipLaunchKernelGGL(append_rows_kernel, dim3(a.S), dim3(256), 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------
+// Link statistics (qpsk_demod_link_stats): one qpsk_link_stats row per stream,
+// the three running sums from the accumulators and a copy of the loop state
+// from the stream record.  One lane per stream; reset zeroes the sums behind
+// the read (the lane that read them, so nothing is lost in between).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void link_stats_gather_kernel(LinkGatherArgs a) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.S) return;
+    const LinkAcc acc = a.acc[s];
+    const StreamState &st = a.state[s];
+    qpsk_link_stats r;
+    r.n_symbols = acc.n;
+    r.sum_dist2 = acc.sum_dist2;
+    r.sum_power = acc.sum_power;
+    r.costas_freq = st.freq;
+    r.costas_theta = st.theta;
+    r.mm_mu = st.mu;
+    r.mm_rate = st.integ;
+    r.fll_freq = a.fll ? st.fll_freq : 0.0f;
+    r.error = st.error;
+    static_cast<qpsk_link_stats *>(a.out)[s] = r;
+    if (a.reset) a.acc[s] = LinkAcc{0.0, 0.0, 0};
+}
+
+void launch_link_gather(const LinkGatherArgs &a, hipStream_t stream) {
+    hipLaunchKernelGGL(link_stats_gather_kernel, dim3((a.S + 255) / 256), dim3(256), 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------

@@ -16,7 +16,8 @@
 //     wave 1  M&M     timing recovery: ring -> interpolated symbols (round r)
 //     wave 2  Costas  carrier recovery on the symbols of round r-1 -> rotated
 //     wave 3  decode  decision + differential decode + bit packing + stores of
-//                     the rotated symbols of round r-2
+//                     the rotated symbols of round r-2; with link statistics on
+//                     (qpsk_demod_link_stats) also their sums of dist2 and power
 //   round r = samples [r*kB, (r+1)*kB) of every stream's queue; one raw
 //   s_barrier per round hands every ring slot one stage forward.
 //   (64 streams x 64-sample rounds, loop_variant 5 and the automatic shape at
@@ -196,7 +197,8 @@ struct RowStride { static constexpr int value = CAP + 1; };
 // do_sin rows at 0, do_cos rows at 440), no tails
 // ROTB: the Costas wave hands the decode wave only the two decisions (the
 // sign bytes of +-1.0, 2 B per symbol) instead of the rotated symbol (8 B)
-// when no symbols are written out: at C3 the workgroup drops from 125 KB to
+// when no symbols are written out and no link statistics are kept (the
+// decode wave forms those from the rotated symbols): at C3 the workgroup drops from 125 KB to
 // 114 KB of LDS, and two matched-filter workgroups of the next pipelined
 // call fit beside it instead of one
 template <int SPW, int CAP, int KB, int TRIG, bool ROTB, int SLOTS>
@@ -1028,7 +1030,18 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
         dpq = a.state[s].diff_pq;
     }
     uint32_t *bits = (MODE == kModeDemodulate && dmine) ? a.bits + s * a.bits_stride_words : nullptr;
-    f2 *syms = (SYMS && dmine) ? reinterpret_cast<f2 *>(a.syms) + s * a.syms_stride : nullptr;
+    // SYMS: symbol rows, link statistics or both; each is wave-uniform (a
+    // scalar branch in the per-lane loop).  Without rows nothing is stored and
+    // no row can be truncated
+    const bool rows = SYMS && a.syms != nullptr;
+    f2 *syms = (rows && dmine) ? reinterpret_cast<f2 *>(a.syms) + s * a.syms_stride : nullptr;
+    // Link statistics (qpsk_demod_link_stats): the stream's running sums, loaded
+    // once, continued symbol by symbol in symbol order and stored once, by the
+    // lane that owns the stream (shadow lanes and streams without samples in
+    // this call touch nothing)
+    LinkAcc *const link = SYMS ? a.link() : nullptr;
+    LinkAcc lk{0.0, 0.0, 0};
+    if (link && dmine) lk = link[s];
     uint32_t word = 0;
     int wbits = 0;
     int64_t widx = 0, nbits = 0, ncs = 0;
@@ -1047,13 +1060,25 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
                 eq = (db & 0x8000u) ? -1.0f : 1.0f;
             } else {
                 const f2 rr = in[k];
-                if (SYMS) {
+                if (rows) {
                     if (ncs < a.syms_cap) syms[ncs] = rr;
                     else err |= 2;
                 }
                 // decision (QPSKDeModulator.cs:379-407)
                 ei = rr.x >= 0.0f ? 1.0f : -1.0f;
                 eq = rr.y >= 0.0f ? 1.0f : -1.0f;
+                if (link) {
+                    // the distance to the decision (QPSKDeModulator.cs:381-384)
+                    // and the power, in float with one rounding per operation
+                    // (never a fused multiply-add), then added as doubles to the
+                    // running sums
+                    const float di = __fsub_rn(rr.x, ei), dq = __fsub_rn(rr.y, eq);
+                    const float dist2 = __fadd_rn(__fmul_rn(di, di), __fmul_rn(dq, dq));
+                    const float pw = __fadd_rn(__fmul_rn(rr.x, rr.x), __fmul_rn(rr.y, rr.y));
+                    lk.sum_dist2 = __dadd_rn(lk.sum_dist2, static_cast<double>(dist2));
+                    lk.sum_power = __dadd_rn(lk.sum_power, static_cast<double>(pw));
+                    ++lk.n;
+                }
             }
             ++ncs;
             if (MODE == kModeDemodulate) {
@@ -1096,6 +1121,7 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
         if (widx < a.bits_cap_words) bits[widx] = __builtin_bswap32(word << (32 - wbits));
         else err |= 2;
     }
+    if (link) link[s] = lk;
     StreamState *g = a.state + s;
     if (MODE == kModeDemodulate) {
         g->diff_have = diff_have;
@@ -1112,7 +1138,8 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
 template <int SPW, int CAP, int KB, int TRIG, int ACT, int SLOTS>
 static int launch_loop_spw_t(const LoopArgs &a, const LoopParams &P, int mode, hipStream_t stream) {
     dim3 grid((a.S + SPW - 1) / SPW), block(256);
-    const bool syms = a.syms != nullptr;
+    // the symbol-carrying instantiation: symbol rows, link statistics or both
+    const bool syms = a.syms != nullptr || a.link() != nullptr;
     const bool diff = P.differential != 0;
     if (mode == kModeConstellation)
         hipLaunchKernelGGL((loop_kernel<kModeConstellation, false, true, SPW, CAP, KB, TRIG, ACT, SLOTS>), grid, block, 0, stream, a, P);

@@ -33,6 +33,7 @@
 //   state   [S]                     StreamState
 //   bits    [S][words]              uint32  MSB-first packed bits
 //   syms    [S][syms_cap]           float2  rotated symbols (on request)
+//   link    [S]                     LinkAcc link statistics' running sums (once enabled)
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -84,6 +85,9 @@ static_assert(QPSK_FMT_CF32 == kFmtCf32 && QPSK_FMT_CS16 == kFmtCs16 && QPSK_FMT
                   QPSK_FMT_CU8 == kFmtCu8,
               "the ABI's format tags are the kernels'");
 constexpr int kFmts = 4;
+static_assert(sizeof(qpsk_link_stats) == 64 && offsetof(qpsk_link_stats, fll_freq) == 56 &&
+                  offsetof(qpsk_link_stats, error) == 60,
+              "qpsk_link_stats is 64 bytes without padding");
 
 struct Call : CallArgs {
     // internal chunk of a longer call: outputs appended to dst_* at the running
@@ -170,6 +174,12 @@ struct qpsk_demod {
     size_t xbits_bytes = 0;
     float *d_xsyms = nullptr;
     size_t xsyms_bytes = 0;
+    // link statistics (qpsk_demod_link_stats): the per-stream running sums the
+    // loop kernel's decode wave continues while link_on, and the rows a
+    // host-memory read is gathered into (both made by the first enable)
+    bool link_on = false;
+    LinkAcc *d_link = nullptr;
+    qpsk_link_stats *d_link_rows = nullptr;
     bool timing = false;
     // launch timestamps of the timed calls ([call][kKtPerCall] wall-clock ticks,
     // written by the kernels themselves: qpsk_kernels.h kt_start / kt_end)
@@ -486,6 +496,7 @@ int run_loop(qpsk_demod *h, const Call &c, const int64_t *d_len, float *mf, hipS
     la.syms_stride = h->syms_cap;
     la.syms_cap = h->syms_cap;
     la.n_syms = h->d_counts + S;
+    la.set_link(h->link_on ? h->d_link : nullptr);
     // device-memory outputs whose rows the kernel can address as its own (4-B
     // aligned word rows holding every word a row can take; float2-aligned
     // symbol rows): written in place, no staging copy behind the kernel
@@ -834,6 +845,8 @@ int qpsk_demod_destroy(qpsk_demod *h) {
     hipFree(h->d_acc);
     hipFree(h->d_xbits);
     hipFree(h->d_xsyms);
+    hipFree(h->d_link);
+    hipFree(h->d_link_rows);
     if (h->e_in) hipEventDestroy(h->e_in);
     if (h->e_fll) hipEventDestroy(h->e_fll);
     if (h->s_front) hipStreamDestroy(h->s_front);
@@ -1361,6 +1374,52 @@ int qpsk_demod_status(qpsk_demod *h, uint32_t *flags) {
     QPSK_HIP_TRY(hipMemset(h->d_flags, 0, sizeof(uint32_t)));
     *flags = *h->h_flags | h->status_host;
     h->status_host = 0;
+    return QPSK_OK;
+}
+
+int qpsk_link_stats_size(void) { return static_cast<int>(sizeof(qpsk_link_stats)); }
+
+int qpsk_demod_enable_link_stats(qpsk_demod *h, int32_t on) {
+    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    int rc;
+    if ((rc = handle_sync(h))) return rc;
+    if (on) {
+        const size_t S = static_cast<size_t>(h->S);
+        if (!h->d_link && (rc = dev_alloc(&h->d_link, S))) return rc;
+        if (!h->d_link_rows && (rc = dev_alloc(&h->d_link_rows, S))) return rc;
+        // +0.0, +0.0, 0; on the handle's stream, which every later call and
+        // read is ordered behind (a null-stream memset is not: the handle's
+        // streams do not synchronise with it)
+        QPSK_HIP_TRY(hipMemsetAsync(h->d_link, 0, S * sizeof(LinkAcc), h->stream));
+    }
+    h->link_on = on != 0;
+    return QPSK_OK;
+}
+
+int qpsk_demod_link_stats(qpsk_demod *h, qpsk_link_stats *out, int32_t mem, int32_t reset) {
+    if (!h || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
+    if (mem == QPSK_MEM_DEVICE && (reinterpret_cast<uintptr_t>(out) & 7))
+        return fail(QPSK_ERR_ARGUMENT, "device link-statistics rows must be 8-byte aligned");
+    if (!h->link_on) return fail(QPSK_ERR_STATE, "link statistics are not enabled (qpsk_demod_enable_link_stats)");
+    int rc;
+    // every queued call has run: the loop kernels of pipelined calls add to the
+    // sums on the back stream, the gather reads them on the handle's
+    if ((rc = handle_sync(h))) return rc;
+    LinkGatherArgs ga{};
+    ga.state = h->d_state;
+    ga.acc = h->d_link;
+    ga.out = mem == QPSK_MEM_HOST ? h->d_link_rows : out;
+    ga.S = h->S;
+    ga.fll = h->p.enable_fll ? 1 : 0;
+    ga.reset = reset ? 1 : 0;
+    launch_link_gather(ga, h->stream);
+    QPSK_HIP_TRY(hipGetLastError());
+    if (mem == QPSK_MEM_HOST) {
+        QPSK_HIP_TRY(hipMemcpyAsync(out, h->d_link_rows, static_cast<size_t>(h->S) * sizeof(qpsk_link_stats),
+                                    hipMemcpyDeviceToHost, h->stream));
+        QPSK_HIP_TRY(hipStreamSynchronize(h->stream));
+    }
     return QPSK_OK;
 }
 

@@ -312,6 +312,11 @@ def lib():
     L.qpsk_demod_group_state_bytes.restype = C.c_int64
     L.qpsk_demod_group_get_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
     L.qpsk_demod_group_set_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_link_stats_size.restype = C.c_int
+    L.qpsk_demod_enable_link_stats.argtypes = [C.c_void_p, C.c_int32]
+    L.qpsk_demod_link_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+    L.qpsk_demod_group_enable_link_stats.argtypes = [C.c_void_p, C.c_int32]
+    L.qpsk_demod_group_link_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     _lib = real
     return real
 
@@ -344,6 +349,8 @@ EXPORTED_SYMBOLS = [
     "qpsk_demod_set_input_scale", "qpsk_demod_get_input_scale", "qpsk_rx_create_fmt", "qpsk_rx_next_slot_fmt",
     "qpsk_rx_submit_fmt", "qpsk_demod_group_process_fmt",
     "qpsk_state_blob_check",
+    "qpsk_link_stats_size", "qpsk_demod_enable_link_stats", "qpsk_demod_link_stats",
+    "qpsk_demod_group_enable_link_stats", "qpsk_demod_group_link_stats",
 ]
 
 _EXC = {
@@ -413,6 +420,24 @@ STREAM_STATE_DTYPE = np.dtype([("mu", "f8"), ("integ", "f8"), ("theta", "f8"), (
                                ("iqb_re", "f4"), ("iqb_im", "f4"), ("_pad", "V8")])   # alignas(16): 112 B
 STATE_CARRY_MAX = 256   # kCarryMax
 STATE_FLL_TAPS = 40     # kFllTaps
+
+
+# qpsk_link_stats (include/qpsk_demod.h): one 64-byte row per stream
+LINK_STATS_DTYPE = np.dtype([("n_symbols", "i8"), ("sum_dist2", "f8"), ("sum_power", "f8"),
+                             ("costas_freq", "f8"), ("costas_theta", "f8"), ("mm_mu", "f8"),
+                             ("mm_rate", "f8"), ("fll_freq", "f4"), ("error", "i4")])
+
+
+class LinkStats(C.Structure):
+    """qpsk_link_stats as a ctypes structure (LINK_STATS_DTYPE is the same layout)."""
+    _fields_ = [("n_symbols", C.c_int64), ("sum_dist2", C.c_double), ("sum_power", C.c_double),
+                ("costas_freq", C.c_double), ("costas_theta", C.c_double), ("mm_mu", C.c_double),
+                ("mm_rate", C.c_double), ("fll_freq", C.c_float), ("error", C.c_int32)]
+
+
+def link_stats_size() -> int:
+    """sizeof(qpsk_link_stats) as the library was built (needs no device)."""
+    return int(lib().qpsk_link_stats_size())
 
 
 def state_blob_check(p: DemodParams, n_streams: int, blob: bytes):
@@ -546,6 +571,32 @@ class BatchDemodulator:
         f = C.c_uint32()
         _check(lib().qpsk_demod_status(self._h, C.byref(f)))
         return int(f.value)
+
+    def enable_link_stats(self, on=True):
+        """Per-stream link statistics on or off (qpsk_demod_enable_link_stats):
+        waits for every queued call; turning them on zeroes every stream's sums."""
+        _check(lib().qpsk_demod_enable_link_stats(self._h, 1 if on else 0))
+
+    def link_stats(self, reset=False) -> np.ndarray:
+        """[S] LINK_STATS_DTYPE: every stream's symbol count, sums of dist2 and
+        power since the last reset, and its loop state now (waits for every
+        queued call; qpsk_demod_link_stats).  reset zeroes the sums behind the
+        read.  QPSKError (QPSK_ERR_STATE) while statistics are not enabled."""
+        out = np.zeros(self.S, dtype=LINK_STATS_DTYPE)
+        _check(lib().qpsk_demod_link_stats(self._h, out.ctypes.data, MEM_HOST, 1 if reset else 0))
+        return out
+
+    def link_stats_device(self, out_tensor, reset=False):
+        """link_stats() into device memory: out_tensor holds at least 64 * S
+        contiguous bytes on the handle's device, 8-byte aligned; the rows are
+        written in order on the handle's stream.  Returns out_tensor."""
+        if not out_tensor.is_cuda or not out_tensor.is_contiguous():
+            raise ValueError("out_tensor must be a contiguous device tensor")
+        if out_tensor.numel() * out_tensor.element_size() < self.S * LINK_STATS_DTYPE.itemsize:
+            raise ValueError("out_tensor holds fewer than 64 bytes a stream")
+        self._after_torch(out_tensor)
+        _check(lib().qpsk_demod_link_stats(self._h, out_tensor.data_ptr(), MEM_DEVICE, 1 if reset else 0))
+        return out_tensor
 
     def last_mf(self, n: int) -> np.ndarray:
         """[S, 2n] float32: the matched-filter output of the last synchronous call."""
@@ -785,6 +836,17 @@ class DemodGroup:
     def set_state(self, k: int, blob: bytes):
         buf = C.create_string_buffer(bytes(blob), len(blob))
         _check(lib().qpsk_demod_group_set_state(self._g, int(k), buf, len(blob)))
+
+    def enable_link_stats(self, on=True):
+        """BatchDemodulator.enable_link_stats on every shard."""
+        _check(lib().qpsk_demod_group_enable_link_stats(self._g, 1 if on else 0))
+
+    def link_stats(self, reset=False) -> np.ndarray:
+        """[S] LINK_STATS_DTYPE over the whole batch in stream order
+        (qpsk_demod_group_link_stats), as BatchDemodulator.link_stats."""
+        out = np.zeros(self.S, dtype=LINK_STATS_DTYPE)
+        _check(lib().qpsk_demod_group_link_stats(self._g, out.ctypes.data, 1 if reset else 0))
+        return out
 
     def process(self, iq: np.ndarray, mode=MODE_DEMODULATE, lengths=None, want_syms=False):
         """iq: [S, 2n] float32 host rows of the whole batch; returns (bits,
