@@ -144,6 +144,23 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     // which keeps loops bounded by it scalar (no exec-mask loop control)
     return __builtin_amdgcn_readfirstlane(v);
 }
+__device__ __forceinline__ int wave_min_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
+// Largest backlog (samples behind the round's end) a stream may carry into the
+// next round: half a round keeps its taps inside the ring slots not being
+// refilled, and a round then holds at most (KB + lag_max + 4)/(sps - 0.1) + 1
+// <= CAP symbols; <= 0 (small sps) means every round is finished
+// (two-slot ring: the backlog is read from the slot's prefix, kPre - 4)
+__host__ __device__ inline double lag_max(int KB, int CAP, int SLOTS, double sps) {
+    return fmin(SLOTS == 2 ? kPre - 4.0 : 0.5 * KB, (CAP - 1) * (sps - 0.1) - KB - 4.0);
+}
 
 // r of the lower half (lanes 0-31) and of the upper half (lanes 32-63) of the
 // wave, each into every lane: v_permlane32_swap exchanges the upper half of
@@ -324,13 +341,7 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
             const int64_t oj = readlane64(org, jj) - static_cast<int64_t>(blk_s0) * a.mf_stride;
             voff[j] = static_cast<uint32_t>((oj + 2 * lane) * 8);
         }
-        int cmin = valid ? cnt : 0x7fffffff;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int w = __shfl_xor(cmin, o, 64);
-            cmin = w < cmin ? w : cmin;
-        }
-        cmin = __builtin_amdgcn_readfirstlane(cmin);
+        const int cmin = wave_min_i32(valid ? cnt : 0x7fffffff);
         // the 32-bit offsets reach every row of the workgroup
         const bool near = static_cast<int64_t>(SPW) * a.mf_stride * 8 < (1ll << 32);
         auto issue = [&](int r) {
@@ -413,17 +424,13 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
             const int64_t oj = readlane64(org, jj) - static_cast<int64_t>(blk_s0) * a.mf_stride;
             voff[j] = static_cast<uint32_t>((oj + c2) * 8);
         }
-        // the fast path needs every stream of the workgroup to hold the whole round
-        int cmin = valid ? cnt : 0x7fffffff;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int w = __shfl_xor(cmin, o, 64);
-            cmin = w < cmin ? w : cmin;
-        }
-        cmin = __builtin_amdgcn_readfirstlane(cmin);
+        // the fast path needs every stream of the workgroup to hold the whole round,
+        // and the 32-bit offsets to reach every row of the workgroup (as above)
+        const int cmin = wave_min_i32(valid ? cnt : 0x7fffffff);
+        const bool near = static_cast<int64_t>(SPW) * a.mf_stride * 8 < (1ll << 32);
         auto issue = [&](int r) {
             const int roff = (r & 3) * KB;
-            if ((r + 1) * KB <= cmin) {
+            if (near && (r + 1) * KB <= cmin) {
                 const char *rb = reinterpret_cast<const char *>(wg_mf + static_cast<int64_t>(r) * KB);
 #pragma unroll
                 for (int j = 0; j < SPW; ++j)
@@ -549,12 +556,7 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
         const double step_max = sps + 0.1;
         const double thr0 = (kguar - 1) * step_max, thr1 = kguar * step_max;
         const double thr2 = (kguar + 1) * step_max, thr3 = (kguar + 2) * step_max;
-        // largest backlog (samples behind rend) a stream may carry into the next
-        // round: half a round keeps its taps inside the ring slots not being
-        // refilled, and a round then holds at most (KB + lag_max + 4)/(sps - 0.1) + 1
-        // <= CAP symbols; <= 0 (small sps) means every round is finished
-        // (two-slot ring: the backlog is read from the slot's prefix, kPre - 4)
-        const double lag_max = fmin(TWO ? kPre - 4.0 : 0.5 * KB, (CAP - 1) * (sps - 0.1) - KB - 4.0);
+        const double lag = lag_max(KB, CAP, SLOTS, sps);   // backlog bound of the per-lane catch-up below
         // logical time baseIndex + mu.  After baseIndex = floor(t), mu = t - baseIndex
         // (exact, Sterbenz), (double)baseIndex + mu == t exactly, so the reference's
         // next time baseIndex + mu + advance (MuellerMuller.cs:113) is simply t + advance
@@ -739,7 +741,7 @@ __global__ __launch_bounds__(256) void loop_kernel(LoopArgs a, LoopParams P) {
                 const bool last = cnt <= (r + 1) * KB;
                 auto more = [&]() {
                     return (base + 2 < rend) & (k < kmax) &
-                           (last | (static_cast<double>(rend - dP - 3) - nt >= lag_max));
+                           (last | (static_cast<double>(rend - dP - 3) - nt >= lag));
                 };
                 if (__builtin_amdgcn_ballot_w64(more()) != 0) {   // one vote skips the loop in steady state
                     reload();                   // the uniform loop ended on a tap-less step
@@ -1298,9 +1300,7 @@ void loop_shape_info(int variant, int S, double sps, int cus, int taps, int trig
         o->slots = T::SLOTS;
         o->prefix = T::SLOTS == 2 ? kPre : 0;
         o->cap = T::CAP;
-        // as the M&M wave computes it
-        const double lag = std::fmin(T::SLOTS == 2 ? kPre - 4.0 : 0.5 * T::KB, (T::CAP - 1) * (sps - 0.1) - T::KB - 4.0);
-        o->lag_max = lag;
+        o->lag_max = lag_max(T::KB, T::CAP, T::SLOTS, sps);
         o->lds_bytes = T::lds(trig, syms != 0);
         o->fir_beside = syms ? 0 : T::FIRS;
         o->fir_taps = syms ? 0 : T::FIRT;

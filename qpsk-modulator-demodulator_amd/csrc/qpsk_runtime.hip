@@ -642,6 +642,9 @@ int pipe_setup(qpsk_demod *h) {
             QPSK_HIP_TRY(hipMemset(h->d_mf[1], 0, 2 * S * h->mf_stride * sizeof(float)));
         }
     }
+    // as at creation: the memsets above (counter, gate, MF rows) ran on the null
+    // stream and are done before any pipelined call uses what they cleared
+    QPSK_HIP_TRY(hipStreamSynchronize(nullptr));
     h->pipe_bufs = h->d_mf[1] ? 2 : 1;
     h->pipe_ready = true;
     return QPSK_OK;
@@ -805,7 +808,12 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
         (H > 0 && hipMemset(h->d_hist[0], 0, 2 * S * H * sizeof(float)) != hipSuccess) ||
         hipMemset(h->d_carry, 0, 2 * S * kCarryMax * sizeof(float)) != hipSuccess ||
         hipMemset(h->d_fll_delay, 0, 2 * S * 2 * kFllTaps * sizeof(float)) != hipSuccess ||
-        hipMemset(h->d_mf[0], 0, static_cast<size_t>(2 * S * h->mf_stride) * sizeof(float)) != hipSuccess)
+        hipMemset(h->d_mf[0], 0, static_cast<size_t>(2 * S * h->mf_stride) * sizeof(float)) != hipSuccess ||
+        // a device memset returns before it is done, and it runs on the null
+        // stream, which the handle's non-blocking stream does not wait for:
+        // without this the first call's kernels race a multi-GB clear of the
+        // MF rows (seen as 4 KB of zero MF samples in the middle of a row)
+        hipStreamSynchronize(nullptr) != hipSuccess)
         return cleanup_fail(fail(QPSK_ERR_DEVICE, "device init failed"));
     *out = h;
     return QPSK_OK;
