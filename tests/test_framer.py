@@ -16,6 +16,7 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
+from gpu_harness import dev
 from refmodel import RefFramer
 
 
@@ -136,14 +137,6 @@ def test_string_model_matches_oracle_framer(tsc, chunks):
 # ---------------------------------------------------------------------------
 # device framer / TSC (HIP)
 
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    return torch
-
-
 RING = 1 << 20   # per-stream ring for the synthetic cases (no frame comes near it)
 
 
@@ -179,12 +172,12 @@ def _run_device(torch, fr, calls, payload_cap, marker_schedule):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("start,end", MARKERS)
-def test_device_framer_matches_string_model(torch_gpu, start, end):
+def test_device_framer_matches_string_model(dev, start, end):
     rng = np.random.default_rng(21)
     S = 40
     streams = [make_stream(rng, start, end, 6, payload=(0, 300)) for _ in range(S)]
     calls = make_calls(rng, streams, 19)
-    outs, _ = run_device(torch_gpu, calls, start, end)
+    outs, _ = run_device(dev, calls, start, end)
     refs = [RefFramer(RING) for _ in range(S)]
     n_frames = 0
     for ci, rows in enumerate(calls):
@@ -197,7 +190,7 @@ def test_device_framer_matches_string_model(torch_gpu, start, end):
 
 
 @pytest.mark.gpu
-def test_device_framer_long_rows_and_offsets(torch_gpu):
+def test_device_framer_long_rows_and_offsets(dev):
     """Rows of ~260k bits (one C2 call's worth) with frames of every lock
     offset and a payload longer than the caller's payload buffer."""
     rng = np.random.default_rng(22)
@@ -206,7 +199,7 @@ def test_device_framer_long_rows_and_offsets(torch_gpu):
     streams = [make_stream(rng, start, end, 8, noise_bits=(0, 60000), payload=(0, 3000))
                for _ in range(S)]
     calls = make_calls(rng, streams, 4, tsc_fail=0.0, max_prefix=64)
-    outs, _ = run_device(torch_gpu, calls, start, end, payload_cap=1024)
+    outs, _ = run_device(dev, calls, start, end, payload_cap=1024)
     refs = [RefFramer(RING) for _ in range(S)]
     for ci, rows in enumerate(calls):
         for s in range(S):
@@ -216,7 +209,7 @@ def test_device_framer_long_rows_and_offsets(torch_gpu):
 
 
 @pytest.mark.gpu
-def test_device_framer_overflow_and_marker_change(torch_gpu):
+def test_device_framer_overflow_and_marker_change(dev):
     rng = np.random.default_rng(23)
     S = 16
     m1, m2 = (b"\x02", b"\x03"), (b"\xA5\x5A", b"\xFF")
@@ -224,7 +217,7 @@ def test_device_framer_overflow_and_marker_change(torch_gpu):
                make_stream(rng, m2[0], m2[1], 4, payload=(0, 60)) for _ in range(S)]
     calls = make_calls(rng, streams, 12)
     sched = [m1] * 6 + [m2] * 6
-    outs, fr = run_device(torch_gpu, calls, *m1, ring_capacity=24, marker_schedule=sched)
+    outs, fr = run_device(dev, calls, *m1, ring_capacity=24, marker_schedule=sched)
     refs = [RefFramer(ring_capacity=24) for _ in range(S)]
     for ci, rows in enumerate(calls):
         for s in range(S):
@@ -239,8 +232,8 @@ def test_device_framer_overflow_and_marker_change(torch_gpu):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("tsc", [K.TSC, "1011001", "1" * 33, K.TSC * 3, "01" * 2100, "   ", "10x1"])
-def test_tsc_find_device_matches_str_find(torch_gpu, tsc):
-    torch = torch_gpu
+def test_tsc_find_device_matches_str_find(dev, tsc):
+    torch = dev
     rng = np.random.default_rng(24)
     S = 33
     rows = []
@@ -268,11 +261,11 @@ def test_tsc_find_device_matches_str_find(torch_gpu, tsc):
 
 
 @pytest.mark.gpu
-def test_device_bytes_chain_matches_oracle(torch_gpu):
+def test_device_bytes_chain_matches_oracle(dev):
     """DeModulateBytes end to end on the device: process_device -> TSC search
     -> device framer, per stream against the oracle's DeModulateBytes on the
     testAtDataLevel frames (TSC + MESSAGE_START/STOP) with per-stream LOs."""
-    torch = torch_gpu
+    torch = dev
     fs, sps, span = K.FS, 8, 8
     rs = fs // sps
     S = 4
@@ -455,13 +448,13 @@ def tsc_device(torch, rows, tsc):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("m", TSC_LENGTHS)
-def test_tsc_find_device_at_chunk_edges(torch_gpu, m):
+def test_tsc_find_device_at_chunk_edges(dev, m):
     """One launch, one row per case: the first occurrence on either side of
     every chunk edge and across it, a later copy in the same or the next
     chunk (which a search that leaves early, or late, would report)."""
     pat, rows = tsc_edge_rows(m)
     want = [tsc_expect(r, pat) for r in rows]
-    bits, got = tsc_device(torch_gpu, rows, pat)
+    bits, got = tsc_device(dev, rows, pat)
     for s, r in enumerate(rows):
         assert got[s] == want[s], (m, s, len(r), r.find(pat))
         assert Q.tsc_find(bits[s], len(r), pat) == want[s]
@@ -469,8 +462,8 @@ def test_tsc_find_device_at_chunk_edges(torch_gpu, m):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("tsc,rows", PERIODIC, ids=["ones", "ones-broken", "01", "01-broken"])
-def test_tsc_find_device_periodic_rows(torch_gpu, tsc, rows):
-    bits, got = tsc_device(torch_gpu, rows, tsc)
+def test_tsc_find_device_periodic_rows(dev, tsc, rows):
+    bits, got = tsc_device(dev, rows, tsc)
     for s, r in enumerate(rows):
         assert got[s] == tsc_expect(r, tsc), (s, len(r))
         assert Q.tsc_find(bits[s], len(r), tsc) == tsc_expect(r, tsc)
@@ -607,9 +600,9 @@ def test_host_framer_end_search_at_chunk_edges(start, end):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("start,end", EDGE_MARKERS)
-def test_device_framer_end_search_at_chunk_edges(torch_gpu, start, end):
+def test_device_framer_end_search_at_chunk_edges(dev, start, end):
     calls, sched, want = end_edge_case(start, end)
-    device_matches(torch_gpu, calls, sched, RING, want, payload_cap=8192)
+    device_matches(dev, calls, sched, RING, want, payload_cap=8192)
 
 
 def test_end_marker_in_front_of_the_search_start_is_not_found():
@@ -648,9 +641,9 @@ def marker_change_case():
 
 
 @pytest.mark.gpu
-def test_device_framer_end_marker_in_front_of_the_search_start(torch_gpu):
+def test_device_framer_end_marker_in_front_of_the_search_start(dev):
     calls, sched, want = marker_change_case()
-    device_matches(torch_gpu, calls, sched, RING, want)
+    device_matches(dev, calls, sched, RING, want)
 
 
 _hunt_cases = {}
@@ -724,9 +717,9 @@ def test_host_framer_start_hunt_at_chunk_edges(start, end, ks):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("start,end,ks", HUNT)
-def test_device_framer_start_hunt_at_chunk_edges(torch_gpu, start, end, ks):
+def test_device_framer_start_hunt_at_chunk_edges(dev, start, end, ks):
     calls, sched, want = hunt_edge_case(start, end, ks)
-    device_matches(torch_gpu, calls, sched, RING, want)
+    device_matches(dev, calls, sched, RING, want)
 
 
 # ---------------------------------------------------------------------------
@@ -785,9 +778,9 @@ def test_host_framer_low_entropy_streams():
 @pytest.mark.gpu
 @pytest.mark.parametrize("cap", LOW_RINGS)
 @pytest.mark.parametrize("pair", range(len(LOW_ENTROPY)), ids=[f"{s.hex()}-{e.hex()}" for s, e in LOW_ENTROPY])
-def test_device_framer_low_entropy_streams(torch_gpu, pair, cap):
+def test_device_framer_low_entropy_streams(dev, pair, cap):
     """status() after every call: a frame that closes with an empty payload
     returns the same as "no frame", so only the state shows such a close."""
     calls, sched, want, frames = low_entropy_case(pair, cap)
     assert frames >= 20
-    device_matches(torch_gpu, calls, sched, cap, want)
+    device_matches(dev, calls, sched, cap, want)

@@ -16,6 +16,7 @@ import pytest
 import common as K
 import oracle as O
 import refmodel as RM
+from gpu_harness import Q, call_rows
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 START, STOP = "MESSAGE_START", "MESSAGE_STOP"
@@ -108,15 +109,6 @@ def test_oracle_reproduces_impaired():
 
 # ---------------------------------------------------------------- GPU
 
-@pytest.fixture(scope="module")
-def Q():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    import qpsk_amd
-    return qpsk_amd
-
-
 @pytest.mark.gpu
 def test_gpu_tad_literal_mirror(Q):
     """testAtDataLevel.cs:15-58 through the single-stream mirror class."""
@@ -175,11 +167,7 @@ def test_gpu_impaired_ragged(Q, tag, fll):
                                        max_samples_per_call=n))
     for call in range(2):
         lens = cut if call == 0 else n - cut
-        m = int(lens.max())
-        x = np.zeros((S, 2 * m), np.float32)
-        for s in range(S):
-            a = 0 if call == 0 else cut[s]
-            x[s, : 2 * lens[s]] = iq[s, 2 * a: 2 * (a + lens[s])]
+        x = call_rows(iq, lens, np.zeros_like(cut) if call == 0 else cut)
         gb, nb, gs, ns = b.process(x, lengths=lens, want_syms=True)
         for s in range(S):
             i = 2 * s + call

@@ -20,6 +20,7 @@ import pytest
 
 import common as K
 import qpsk_amd as Q
+from gpu_harness import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -155,7 +156,7 @@ class Env:
 
 
 @pytest.fixture(scope="module")
-def env():
+def env(dev):
     e = Env()
     yield e
     e.close()

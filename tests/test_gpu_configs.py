@@ -27,7 +27,7 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
-from test_gpu_parity import SYM_TOL
+from gpu_harness import SYM_TOL, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -44,12 +44,9 @@ CASES = {
 
 
 @pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
+def _gpu(dev):
     yield
-    torch.cuda.empty_cache()
+    dev.cuda.empty_cache()
 
 
 def _rows(t, idx):

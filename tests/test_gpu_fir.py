@@ -23,73 +23,15 @@ import pytest
 
 import common as K
 import oracle as O
+from gpu_harness import (SPECIALISED, TILE, Q, _ids, assert_rows, assert_same, fir_ref, host_calls, make, oracle_run,
+                         ragged_calls, rrc)
 
 gpu = pytest.mark.gpu
-
-# (sps, span) -> T = sps * span + 1: one pair per tile-kernel instantiation of
-# launch_fir (qpsk_kernels.hip); test_every_specialised_tap_count_has_a_case
-# keeps the two lists equal
-SPECIALISED = [(2, 6), (2, 8), (2, 10), (4, 8), (4, 10), (4, 12), (8, 8), (8, 12), (4, 32)]
-TILE = 2048   # outputs per workgroup of fir_tile_kernel (256 threads x 8)
-
-
-def _ids(pairs):
-    return [f"T{s * p + 1}" for s, p in pairs]
-
-
-@pytest.fixture(scope="module")
-def Q():
-    """The binding and a device (GPU tests only)."""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    import qpsk_amd
-    return qpsk_amd
-
-
-@functools.lru_cache(maxsize=None)
-def rrc(sps, span):
-    """The reference's float32 RRC taps for (K.FS, K.FS // sps, K.ALPHA, span)."""
-    h = K.oracle_for(sps, span).rrc_f32()
-    h.setflags(write=False)
-    return h
-
-
-def fir_ref(h, row, lanes=8):
-    """One streaming reference filter over a whole interleaved row."""
-    tiq = np.zeros(2 * h.size, np.float32)
-    tiq[0::2] = h
-    return O.oracle_fir(tiq, row, lanes=lanes)
-
-
-def is_neg_zero(v):
-    return np.signbit(v) & (v == 0)
 
 
 # ---------------------------------------------------------------------------
 # call sequences and inputs
 # ---------------------------------------------------------------------------
-def ragged_calls(T, S=6):
-    """Per-call [S] lengths: stream s takes 1, T-2, T-1, T, 2047, 2048, 2049, 0,
-    4097 samples in that order, started s places in (so stream 0 builds its
-    history from calls shorter than T-1, and every stream reaches and crosses
-    the 2048-output tile edge with both parities of n).  A call in which the
-    rotation leaves no stream empty gets one: stream (call % S) sits that call
-    out and takes its length in the next one."""
-    base = [1, T - 2, T - 1, T, TILE - 1, TILE, TILE + 1, 0, 2 * TILE + 1]
-    todo = [base[s:] + base[:s] for s in range(S)]
-    calls = []
-    while any(todo):
-        lens = [q[0] if q else 0 for q in todo]
-        if 0 not in lens:
-            lens[len(calls) % S] = 0
-        for s in range(S):
-            if todo[s] and lens[s] == todo[s][0]:
-                todo[s].pop(0)
-        calls.append(lens)
-    return calls
-
-
 def normal_rows(S, n, seed):
     return np.random.default_rng(seed).standard_normal((S, 2 * n)).astype(np.float32)
 
@@ -209,44 +151,16 @@ def test_every_specialised_tap_count_has_a_case():
 # ---------------------------------------------------------------------------
 # GPU runs
 # ---------------------------------------------------------------------------
-def run_calls(Q, iq, calls, sps, span, n_max, mode=None, **kw):
-    """The host process path with per-stream lengths; per call the decoded rows
-    [(bits, symbols)] and last_mf(max(lens))."""
-    S = iq.shape[0]
-    b = Q.BatchDemodulator(S, Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=n_max, **kw))
+def run_calls(iq, calls, sps, span, n_max, mode=None, **kw):
+    """The host process path with per-stream lengths in every call; per call
+    the decoded rows [(bits, symbols)] and last_mf(max(lens))."""
+    b = make(iq.shape[0], sps, span, n_max, **kw)
     assert K.bitwise_equal(b.rrc_taps(), rrc(sps, span))
-    pos = np.zeros(S, np.int64)
-    out, mfs = [], []
-    for ci, lens in enumerate(calls):
-        m = mode[ci] if mode else Q.MODE_DEMODULATE
-        n = int(max(lens))
-        x = np.zeros((S, 2 * n), np.float32)
-        for s in range(S):
-            x[s, : 2 * lens[s]] = iq[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-        bits, nb, syms, ns = b.process(x, mode=m, lengths=np.array(lens, np.int64), want_syms=True)
-        out.append([(Q.unpack_bits(bits[s], int(nb[s])) if m == Q.MODE_DEMODULATE else "",
-                     syms[s, : 2 * int(ns[s])].copy()) for s in range(S)])
-        mf = b.last_mf(n)
-        assert mf.shape == (S, 2 * n)
-        mfs.append(mf.copy())
-        pos += np.array(lens)
+    out, mfs = host_calls(b, iq, calls, mode=mode, always_lengths=True)
+    assert all(mf.shape == (iq.shape[0], 2 * max(lens)) for mf, lens in zip(mfs, calls))
     assert b.status() == 0
     b.close()
     return out, mfs
-
-
-def assert_rows(mfs, calls, refs):
-    """refs[s]: the reference filter's output over stream s's whole input."""
-    pos = np.zeros(len(refs), np.int64)
-    for ci, (mf, lens) in enumerate(zip(mfs, calls)):
-        for s, n in enumerate(lens):
-            got, want = mf[s, : 2 * n], refs[s][2 * pos[s]: 2 * (pos[s] + n)]
-            if not K.bitwise_equal(got, want):
-                bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
-                pytest.fail(f"call {ci} stream {s} (n = {n}): {bad.size} floats differ, first at output "
-                            f"{bad[0] // 2}: {got[bad[0]]!r} vs {want[bad[0]]!r}")
-            assert not is_neg_zero(got).any(), f"call {ci} stream {s}: -0 in the matched filter"
-            pos[s] += n
 
 
 def stage_case(Q, sps, span, n_max, lanes=8, seed=0):
@@ -255,7 +169,7 @@ def stage_case(Q, sps, span, n_max, lanes=8, seed=0):
     total = sum(c[0] for c in calls)
     assert all(sum(c[s] for c in calls) == total for s in range(6))
     iq = normal_rows(6, total, seed=seed + T)
-    _, mfs = run_calls(Q, iq, calls, sps, span, n_max, vector_lanes=lanes)
+    _, mfs = run_calls(iq, calls, sps, span, n_max, vector_lanes=lanes)
     assert_rows(mfs, calls, [fir_ref(rrc(sps, span), iq[s], lanes) for s in range(6)])
 
 
@@ -320,7 +234,7 @@ def test_signed_zero_windows_and_subnormals(Q, sps, span):
     iq, _ = signed_zero_case(sps, span)
     assert np.count_nonzero(np.abs(iq[5]) < np.float32(2.0 ** -126)) > iq.shape[1] // 2
     calls = [[n] * 6 for n in SZ_CALLS]
-    _, mfs = run_calls(Q, iq, calls, sps, span, max(SZ_CALLS) + 1)
+    _, mfs = run_calls(iq, calls, sps, span, max(SZ_CALLS) + 1)
     assert_rows(mfs, calls, [fir_ref(h, iq[s]) for s in range(6)])
 
 
@@ -330,7 +244,6 @@ def test_signed_zero_tail_through_the_chain(Q, sps, span):
     """A5.  Ordinary signal, then >= 64 symbols of the all-(-0)-products pattern
     back to back (stream 1: of -0), split over two calls inside that tail:
     bits and symbols of DeModulate and of deModulateConstellation."""
-    from test_gpu_parity import assert_same, oracle_run
     h = rrc(sps, span)
     T = h.size
     sig = K.batch_signals(2, seed0=810, sps=sps, span=span, n_bits=800, snr_db=18)
@@ -343,8 +256,8 @@ def test_signed_zero_tail_through_the_chain(Q, sps, span):
     n1 = sig.shape[1] // 2 + tail.size // 4 + 3
     calls = [[n1] * 2, [n - n1] * 2]
     for modes in ([Q.MODE_DEMODULATE] * 2, [Q.MODE_CONSTELLATION] * 2):
-        got, mfs = run_calls(Q, iq, calls, sps, span, n, mode=modes)
-        assert_same(got, oracle_run(iq, calls, sps, span, mode=modes))
+        got, mfs = run_calls(iq, calls, sps, span, n, mode=modes)
+        assert_same(got, oracle_run(iq, calls, K.FS // sps, span, mode=modes))
         assert_rows(mfs, calls, [fir_ref(h, iq[s]) for s in range(2)])
 
 
@@ -355,7 +268,6 @@ def test_fll_then_matched_filter_on_degenerate_streams(Q):
     an 8-sample block and than the 40-tap window, empty ones): bits and symbols
     against the reference chain, and each call's matched-filter rows against
     the reference filter over the reference FLL's output."""
-    from test_gpu_parity import assert_same, oracle_run
     sps, span, S = 8, 8, 5
     iq = K.batch_signals(S, seed0=830, sps=sps, span=span, n_bits=900, cfo_hz=-3000.0, snr_db=22)
     iq[0] = np.float32(0.0)
@@ -372,8 +284,8 @@ def test_fll_then_matched_filter_on_degenerate_streams(Q):
         calls.append([int(v) for v in lens])
         used += lens
     calls.append([int(n - u) for u in used])
-    got, mfs = run_calls(Q, iq, calls, sps, span, n, enable_fll=True)
-    assert_same(got, oracle_run(iq, calls, sps, span, enable_fll=True))
+    got, mfs = run_calls(iq, calls, sps, span, n, enable_fll=True)
+    assert_same(got, oracle_run(iq, calls, K.FS // sps, span, enable_fll=True))
     # the FLL as OracleDemod builds it (QPSKDeModulator.cs:35): integer fs / rs,
     # 40 taps, the default CFO loop bandwidth (float 1e-4), portable trig
     refs = []

@@ -46,7 +46,7 @@ import pytest
 
 import common as K
 import oracle as O
-from test_gpu_fir import fir_ref, is_neg_zero, rrc
+from gpu_harness import Q, call_rows, fir_ref, is_neg_zero, oracle_run, rrc
 
 gpu = pytest.mark.gpu
 
@@ -70,16 +70,6 @@ ORDER = [0, 4, 2, 1, 9, 8, 6, 3,
          4, 0, 1, 9, 0, 1, 9, 0,
          1, 5, 9, 0, 1, 9, 0, 1,
          5, 7]
-
-
-@pytest.fixture(scope="module")
-def Q():
-    """The binding and a device (GPU tests only)."""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    import qpsk_amd
-    return qpsk_amd
 
 
 def u32(v):
@@ -257,14 +247,6 @@ def ladder_calls(sps, span, lanes):
     return c, calls
 
 
-def call_rows(rows, lens, pos):
-    S, n = rows.shape[0], int(max(lens))
-    x = np.zeros((S, 2 * n), rows.dtype)
-    for s in range(S):
-        x[s, : 2 * lens[s]] = rows[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-    return x, n
-
-
 def same_floats(got, want, nan_ok):
     return K.bitwise_equal(np.asarray(got, np.float32), np.asarray(want, np.float32), nan_any_payload=nan_ok)
 
@@ -280,7 +262,8 @@ def drive(Q, b, case, calls, process, chain=None, nan_rows=(), may_raise=False):
     pos = np.zeros(S, np.int64)
     raised = 0
     for ci, lens in enumerate(calls):
-        x, n = call_rows(case.rows, lens, pos)
+        x = call_rows(case.rows, lens, pos)
+        n = x.shape[1] // 2
         res = None
         try:
             res = process(x, np.array(lens, np.int64))
@@ -342,10 +325,9 @@ def test_stored_state_cases_in_the_oracle():
 @pytest.mark.parametrize("lanes", [8, 4], ids=["systolic", "one-lane"])
 @pytest.mark.parametrize("sps,span", CONFIGS)
 def test_amplitude_ladder_through_wrap_and_clamp(Q, sps, span, lanes):
-    from test_gpu_parity import oracle_run
     c, calls = ladder_calls(sps, span, lanes)
     S, n = c.rows.shape[0], c.rows.shape[1] // 2
-    chain = oracle_run(c.rows, calls, sps, span, enable_fll=True, cfo_loop_bw=BW, lanes=lanes)
+    chain = oracle_run(c.rows, calls, K.FS // sps, span, enable_fll=True, cfo_loop_bw=BW, lanes=lanes)
     b = Q.BatchDemodulator(S, Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=n, enable_fll=True,
                                        cfo_loop_bandwidth=BW, vector_lanes=lanes))
     drive(Q, b, c, calls, lambda x, lens: b.process(x, lengths=lens, want_syms=True), chain=chain)
@@ -369,12 +351,11 @@ def cs8_case(sps, span):
 
 @gpu
 def test_cs8_at_scale_one_lives_in_the_redo_path(Q):
-    from test_gpu_parity import oracle_run
     sps, span = 8, 8
     c = cs8_case(sps, span)
     S, n = c.rows.shape[0], c.rows.shape[1] // 2
     calls = ragged(S, n, seed=21)
-    chain = oracle_run(c.feed, calls, sps, span, enable_fll=True, cfo_loop_bw=BW)
+    chain = oracle_run(c.feed, calls, K.FS // sps, span, enable_fll=True, cfo_loop_bw=BW)
     b = Q.BatchDemodulator(S, Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=n, enable_fll=True,
                                        cfo_loop_bandwidth=BW))
     b.set_input_scale("cs8", 1.0)

@@ -15,27 +15,19 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
-from test_gpu_parity import assert_same, async_run, gpu_run, oracle_run
+from gpu_harness import assert_same, async_run, dev, gpu_run, oracle_run
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("dev")]
 
 LIBM = dict(trig=O.TRIG_LIBM)
 GL = dict(costas_trig=1)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    yield
 
 
 @pytest.mark.parametrize("sps,span", K.CONFIGS)
 def test_glibc_trig_single_call_bit_exact(sps, span):
     iq = K.batch_signals(5, seed0=900, sps=sps, span=span, n_bits=3000, snr_db=16)
     calls = [[iq.shape[1] // 2] * 5]
-    assert_same(gpu_run(iq, calls, sps, span, **GL), oracle_run(iq, calls, sps, span, **LIBM))
+    assert_same(gpu_run(iq, calls, K.FS // sps, span, **GL), oracle_run(iq, calls, K.FS // sps, span, **LIBM))
 
 
 @pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 6, 7])
@@ -50,8 +42,8 @@ def test_glibc_trig_ragged_chunks_every_loop_shape(variant):
         calls.append([int(v) for v in lens])
         used += lens
     calls.append([int(n - u) for u in used])
-    got = gpu_run(iq, calls, sps, span, loop_variant=variant, **GL)
-    assert_same(got, oracle_run(iq, calls, sps, span, **LIBM))
+    got = gpu_run(iq, calls, K.FS // sps, span, loop_variant=variant, **GL)
+    assert_same(got, oracle_run(iq, calls, K.FS // sps, span, **LIBM))
 
 
 @pytest.mark.parametrize("fll", [False, True])
@@ -63,7 +55,7 @@ def test_glibc_trig_pipelined_bit_exact(fll):
     n = iq.shape[1] // 2
     calls = [[n // 4] * 5, [n // 3] * 5, [n - n // 4 - n // 3] * 5]
     got, _ = async_run(iq, calls, 8, 8, **GL, **kw)
-    assert_same(got, oracle_run(iq, calls, 8, 8, **LIBM, **okw))
+    assert_same(got, oracle_run(iq, calls, K.FS // 8, 8, **LIBM, **okw))
 
 
 def test_glibc_trig_constellation_and_nondifferential():
@@ -71,11 +63,12 @@ def test_glibc_trig_constellation_and_nondifferential():
     n = iq.shape[1] // 2
     calls = [[n // 2] * 3, [n - n // 2] * 3]
     mode = [Q.MODE_CONSTELLATION, Q.MODE_DEMODULATE]
-    assert_same(gpu_run(iq, calls, 4, 32, mode=mode, **GL), oracle_run(iq, calls, 4, 32, mode=mode, **LIBM))
+    assert_same(gpu_run(iq, calls, K.FS // 4, 32, mode=mode, **GL),
+                oracle_run(iq, calls, K.FS // 4, 32, mode=mode, **LIBM))
     iq = K.batch_signals(3, seed0=931, sps=8, span=8, n_bits=2000, snr_db=16, differential=False)
     calls = [[iq.shape[1] // 2] * 3]
-    assert_same(gpu_run(iq, calls, 8, 8, differential=False, **GL),
-                oracle_run(iq, calls, 8, 8, differential=False, **LIBM))
+    assert_same(gpu_run(iq, calls, K.FS // 8, 8, differential=False, **GL),
+                oracle_run(iq, calls, K.FS // 8, 8, differential=False, **LIBM))
 
 
 def test_glibc_trig_huge_theta_payne_hanek():
@@ -85,7 +78,7 @@ def test_glibc_trig_huge_theta_payne_hanek():
     iq = K.batch_signals(3, seed0=940, sps=8, span=8, n_bits=800, snr_db=20) * np.float32(1e12)
     n = iq.shape[1] // 2
     calls = [[n // 3] * 3, [n - n // 3] * 3]
-    got, ref = gpu_run(iq, calls, 8, 8, **GL), oracle_run(iq, calls, 8, 8, **LIBM)
+    got, ref = gpu_run(iq, calls, K.FS // 8, 8, **GL), oracle_run(iq, calls, K.FS // 8, 8, **LIBM)
     for ci, (ra, rb) in enumerate(zip(got, ref)):
         for s, ((ba, sa), (bb, sb)) in enumerate(zip(ra, rb)):
             assert ba == bb, f"call {ci} stream {s}: bits differ"

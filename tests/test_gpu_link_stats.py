@@ -32,8 +32,9 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
+from gpu_harness import call_rows, dev, oracle_run, quantised, widened
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("dev")]
 
 SMAX = 70
 SHAPES = [(8, 8), (4, 32), (2, 10)]
@@ -51,15 +52,6 @@ CFGS = {
 f4, f8 = np.float32, np.float64
 
 
-@pytest.fixture(scope="module", autouse=True)
-def dev():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    torch.cuda.init()
-    return torch
-
-
 # ---------------------------------------------------------------------------
 # signals, calls, the oracle
 # ---------------------------------------------------------------------------
@@ -67,7 +59,7 @@ def dev():
 def signal_i8(sps, span):
     base = K.batch_signals(SMAX, seed0=5200 + sps, sps=sps, span=span, n_bits=2 * 6800 // sps, snr_db=14,
                            cfo_hz=1500.0)
-    q = np.round(base * (64.0 / np.abs(base).max())).astype(np.int8)
+    q = quantised(base, "cs8")
     q.setflags(write=False)
     return q
 
@@ -77,7 +69,7 @@ def signal(sps, span, kind="base"):
     """[70, 2n] float32 rows of at least 6500 samples, noisy and 1.5 kHz off
     tune; "q8": the same rows on the int8 grid, as a CS8 call widens them."""
     if kind == "q8":
-        x = signal_i8(sps, span).astype(f4) * f4(1.0 / 128.0)
+        x = widened(signal_i8(sps, span), "cs8")
     else:
         x = K.batch_signals(SMAX, seed0=5200 + sps, sps=sps, span=span, n_bits=2 * 6800 // sps, snr_db=14,
                             cfo_hz=1500.0)
@@ -131,23 +123,15 @@ def sums_of(syms):
 def trace(sps, span, cfg, calls, kind="base"):
     """The oracle over calls on all the streams the calls name: outs[ci][s] =
     (bits, symbols) of call ci, states[s] = read_state() after the last call."""
-    iq = signal(sps, span, kind)
-    S = len(calls[0])
-    modes = call_modes(cfg, len(calls))
-    outs = [[None] * S for _ in calls]
+    iq = signal(sps, span, kind)[: len(calls[0])]
     states = []
-    for s in range(S):
-        dm = K.oracle_for(sps, span, **CFGS[cfg][1])
-        pos = 0
-        for ci, lens in enumerate(calls):
-            x = iq[s, 2 * pos: 2 * (pos + lens[s])]
-            if modes[ci] == Q.MODE_DEMODULATE:
-                bits, syms, _ = dm.demodulate_ex(x)
-                outs[ci][s] = (bits, syms)
-            else:
-                outs[ci][s] = ("", dm.deModulateConstellation(x))
-            pos += lens[s]
-        states.append(dm.read_state())
+
+    def after_call(ci, dms):
+        if ci == len(calls) - 1:
+            states.extend(dm.read_state() for dm in dms)
+
+    outs = oracle_run(iq, calls, K.FS // sps, span, mode=call_modes(cfg, len(calls)), after_call=after_call,
+                      **CFGS[cfg][1])
     return outs, states
 
 
@@ -165,21 +149,13 @@ def make(sps, span, S, cfg="plain", msc=2560, **knobs):
     return Q.BatchDemodulator(S, Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=msc, **kw))
 
 
-def rows_of_call(iq, pos, lens):
-    S, n = len(lens), int(max(lens))
-    x = np.zeros((S, 2 * max(n, 1)), iq.dtype)
-    for s in range(S):
-        x[s, : 2 * lens[s]] = iq[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-    return x[:, : 2 * n]
-
-
 def host_call(b, iq, calls, ci, mode=Q.MODE_DEMODULATE, want_syms=False, fmt=None):
     """Call ci of calls on b (which has run calls 0 .. ci - 1): uniform calls
     pass n_samples, ragged ones per-stream lengths."""
     S = len(calls[ci])
     lens = np.array(calls[ci], np.int64)
     pos = np.sum(np.array(calls[:ci], np.int64).reshape(-1, S), axis=0)
-    x = rows_of_call(iq, pos, lens)
+    x = call_rows(iq[:S], lens, pos)
     lengths = None if len(set(calls[ci])) == 1 and lens[0] > 0 else lens
     if fmt is None:
         bits, nb, syms, ns = b.process(x, mode=mode, lengths=lengths, want_syms=want_syms)
@@ -497,7 +473,7 @@ def test_nan_sample_stays_in_its_stream(variant, bad):
         with contextlib.suppress(Q.QPSKError):              # non-finite timing: reported, rows still written
             host_call(b, iq, calls, ci)
         lens = np.array(calls[ci], np.int64)
-        x = rows_of_call(iq, np.sum(np.array(calls[:ci], np.int64).reshape(-1, SMAX), axis=0), lens)
+        x = call_rows(iq, lens, np.sum(np.array(calls[:ci], np.int64).reshape(-1, SMAX), axis=0))
         n_syms = np.zeros(SMAX, np.int64)
         nb = np.zeros(SMAX, np.int64)
         ms = max(twin.max_symbols(int(lens.max())), 1)

@@ -18,24 +18,15 @@ import pytest
 
 import common as K
 import qpsk_amd as Q
-from test_gpu_loop_two_slot import gpu_calls, oracle_calls
-from test_gpu_parity import assert_same
+from gpu_harness import assert_same, dev, gpu_run, oracle_run
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("dev")]
 
 SPS, SPAN = 4, 32
 SMAX = 64
 # (streams, loop_variant, max_samples_per_call): streams x row bytes > 2^32
 FOUR_SLOT = (32, 2, 18_000_000)
 TWO_SLOT = (64, 5, 9_000_000)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    yield
 
 
 def calls_for(S):
@@ -50,7 +41,7 @@ def case():
     iq.setflags(write=False)
     calls = calls_for(SMAX)
     assert iq.shape[1] // 2 >= sum(max(c) for c in calls)
-    return iq, oracle_calls(iq, calls, K.FS // SPS, SPAN)
+    return iq, oracle_run(iq, calls, K.FS // SPS, SPAN)
 
 
 @pytest.mark.parametrize("want_syms", [True, False])
@@ -61,6 +52,6 @@ def test_far_rows_bit_exact(S, variant, n_max, want_syms):
     assert (g["streams"], g["slots"]) == (S, 2 if variant == 5 else 4)
     assert (S - 1) * n_max * 8 >= 1 << 32
     iq, ref = case()
-    got = gpu_calls(iq[:S], calls_for(S), K.FS // SPS, SPAN, want_syms=want_syms, max_samples=n_max,
-                    loop_variant=variant)
+    got = gpu_run(iq[:S], calls_for(S), K.FS // SPS, SPAN, want_syms=want_syms, max_samples=n_max,
+                  loop_variant=variant)
     assert_same(got, [res[:S] for res in ref])

@@ -18,20 +18,12 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
-from test_gpu_parity import assert_same
+from gpu_harness import assert_same, dev, gpu_run, oracle_run
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("dev")]
 
 S = 70
 VARIANTS = [5, 0]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    yield
 
 
 @functools.lru_cache(maxsize=None)
@@ -39,54 +31,6 @@ def signals(sps, span, differential=True, seed0=3000):
     iq = K.batch_signals(S, seed0=seed0, sps=sps, span=span, n_bits=2400, snr_db=14, differential=differential)
     iq.setflags(write=False)
     return iq
-
-
-def oracle_calls(iq, calls, rs, span, mode=None, **kw):
-    """test_gpu_parity.oracle_run with the demodulator's symbol rate given in Hz."""
-    dms = [O.OracleDemod(K.FS, rs, K.ALPHA, span, **kw) for _ in range(iq.shape[0])]
-    pos = np.zeros(iq.shape[0], dtype=np.int64)
-    out = []
-    for ci, lens in enumerate(calls):
-        m = mode[ci] if mode else Q.MODE_DEMODULATE
-        res = []
-        for s, dm in enumerate(dms):
-            x = iq[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-            if m == Q.MODE_DEMODULATE:
-                bits, syms, _ = dm.demodulate_ex(x)
-                res.append((bits, syms))
-            else:
-                res.append(("", dm.deModulateConstellation(x)))
-            pos[s] += lens[s]
-        out.append(res)
-    return out
-
-
-def gpu_calls(iq, calls, rs, span, mode=None, want_syms=True, max_samples=None, **kw):
-    """test_gpu_parity.gpu_run with the symbol rate in Hz and the internal chunk size."""
-    n_streams = iq.shape[0]
-    chunk = max_samples or max(max(c) for c in calls) + 8
-    b = Q.BatchDemodulator(n_streams, Q.params(K.FS, rs, K.ALPHA, span, max_samples_per_call=chunk, **kw))
-    pos = np.zeros(n_streams, dtype=np.int64)
-    out = []
-    try:
-        for ci, lens in enumerate(calls):
-            m = mode[ci] if mode else Q.MODE_DEMODULATE
-            n = int(max(lens))
-            x = np.zeros((n_streams, 2 * max(n, 1)), np.float32)
-            for s in range(n_streams):
-                x[s, : 2 * lens[s]] = iq[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-            uniform = all(l == lens[0] for l in lens)
-            bits, nb, syms, ns = b.process(x[:, : 2 * n] if n else x[:, :0], mode=m,
-                                           lengths=None if uniform else np.array(lens), want_syms=want_syms)
-            res = []
-            for s in range(n_streams):
-                bs = Q.unpack_bits(bits[s], int(nb[s])) if m == Q.MODE_DEMODULATE else ""
-                res.append((bs, syms[s, : 2 * int(ns[s])].copy() if want_syms else None))
-            pos += np.array(lens)
-            out.append(res)
-    finally:
-        b.close()
-    return out
 
 
 def ragged_calls(n, seed):
@@ -109,7 +53,7 @@ def ragged_calls(n, seed):
 def ragged_case(sps, span):
     iq = signals(sps, span)
     calls = ragged_calls(iq.shape[1] // 2, sps)
-    return iq, calls, oracle_calls(iq, calls, K.FS // sps, span)
+    return iq, calls, oracle_run(iq, calls, K.FS // sps, span)
 
 
 @pytest.mark.parametrize("want_syms", [True, False])
@@ -117,14 +61,14 @@ def ragged_case(sps, span):
 @pytest.mark.parametrize("sps,span", [(4, 32), (8, 8)])
 def test_ragged_calls_bit_exact(sps, span, variant, want_syms):
     iq, calls, ref = ragged_case(sps, span)
-    assert_same(gpu_calls(iq, calls, K.FS // sps, span, loop_variant=variant, want_syms=want_syms), ref)
+    assert_same(gpu_run(iq, calls, K.FS // sps, span, loop_variant=variant, want_syms=want_syms), ref)
 
 
 @functools.lru_cache(maxsize=None)
 def single_call_ref(sps, span, rs):
     iq = signals(sps, span)
     calls = [[iq.shape[1] // 2] * S]
-    return iq, calls, oracle_calls(iq, calls, rs, span)
+    return iq, calls, oracle_run(iq, calls, rs, span)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -133,9 +77,9 @@ def test_internal_chunks_bit_exact(sps, span, variant):
     """One call run as internal chunks of about 1000 samples: the timing runs on
     in the call's coordinates (StreamState.tofs != 0)."""
     iq, calls, ref = single_call_ref(sps, span, K.FS // sps)
-    assert_same(gpu_calls(iq, calls, K.FS // sps, span, loop_variant=variant, max_samples=1000), ref)
-    assert_same(gpu_calls(iq, calls, K.FS // sps, span, loop_variant=variant, max_samples=1000,
-                          want_syms=False), ref)
+    assert_same(gpu_run(iq, calls, K.FS // sps, span, loop_variant=variant, max_samples=1000), ref)
+    assert_same(gpu_run(iq, calls, K.FS // sps, span, loop_variant=variant, max_samples=1000,
+                        want_syms=False), ref)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -147,8 +91,8 @@ def test_backlog_at_its_bound_bit_exact(sps, span, off, variant):
     end and run the per-lane catch-up loop."""
     rs = int(round(K.FS / sps * off))
     iq, calls, ref = single_call_ref(sps, span, rs)
-    assert_same(gpu_calls(iq, calls, rs, span, loop_variant=variant), ref)
-    assert_same(gpu_calls(iq, calls, rs, span, loop_variant=variant, want_syms=False), ref)
+    assert_same(gpu_run(iq, calls, rs, span, loop_variant=variant), ref)
+    assert_same(gpu_run(iq, calls, rs, span, loop_variant=variant, want_syms=False), ref)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -159,14 +103,14 @@ def test_non_integer_sps_bit_exact(variant):
     n = iq.shape[1] // 2
     calls = [[n // 3] * S, [n - n // 3] * S]
     ref = _non_integer_ref(rs, span)
-    assert_same(gpu_calls(iq, calls, rs, span, loop_variant=variant), ref)
+    assert_same(gpu_run(iq, calls, rs, span, loop_variant=variant), ref)
 
 
 @functools.lru_cache(maxsize=None)
 def _non_integer_ref(rs, span):
     iq = signals(4, 32)
     n = iq.shape[1] // 2
-    return oracle_calls(iq, [[n // 3] * S, [n - n // 3] * S], rs, span)
+    return oracle_run(iq, [[n // 3] * S, [n - n // 3] * S], rs, span)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -175,9 +119,9 @@ def test_constellation_and_non_differential_bit_exact(variant):
     n = iq.shape[1] // 2
     calls = [[n // 2] * S, [n - n // 2] * S]
     mode = [Q.MODE_CONSTELLATION, Q.MODE_DEMODULATE]
-    assert_same(gpu_calls(iq, calls, K.FS // 4, 32, mode=mode, loop_variant=variant), _modes_ref()[0])
+    assert_same(gpu_run(iq, calls, K.FS // 4, 32, mode=mode, loop_variant=variant), _modes_ref()[0])
     nd = signals(4, 32, differential=False)
-    assert_same(gpu_calls(nd, [[nd.shape[1] // 2] * S], K.FS // 4, 32, differential=False, loop_variant=variant),
+    assert_same(gpu_run(nd, [[nd.shape[1] // 2] * S], K.FS // 4, 32, differential=False, loop_variant=variant),
                 _modes_ref()[1])
 
 
@@ -186,9 +130,9 @@ def _modes_ref():
     iq = signals(4, 32)
     n = iq.shape[1] // 2
     calls = [[n // 2] * S, [n - n // 2] * S]
-    a = oracle_calls(iq, calls, K.FS // 4, 32, mode=[Q.MODE_CONSTELLATION, Q.MODE_DEMODULATE])
+    a = oracle_run(iq, calls, K.FS // 4, 32, mode=[Q.MODE_CONSTELLATION, Q.MODE_DEMODULATE])
     nd = signals(4, 32, differential=False)
-    b = oracle_calls(nd, [[nd.shape[1] // 2] * S], K.FS // 4, 32, differential=False)
+    b = oracle_run(nd, [[nd.shape[1] // 2] * S], K.FS // 4, 32, differential=False)
     return a, b
 
 
@@ -198,13 +142,13 @@ def test_glibc_trig_bit_exact(variant):
     32-stream shape whatever loop_variant asks for; bit-exact with the libm
     oracle either way."""
     iq, calls, _ = ragged_case(4, 32)
-    assert_same(gpu_calls(iq, calls, K.FS // 4, 32, loop_variant=variant, costas_trig=1), _glibc_ref())
+    assert_same(gpu_run(iq, calls, K.FS // 4, 32, loop_variant=variant, costas_trig=1), _glibc_ref())
 
 
 @functools.lru_cache(maxsize=None)
 def _glibc_ref():
     iq, calls, _ = ragged_case(4, 32)
-    return oracle_calls(iq, calls, K.FS // 4, 32, trig=O.TRIG_LIBM)
+    return oracle_run(iq, calls, K.FS // 4, 32, trig=O.TRIG_LIBM)
 
 
 def test_small_sps_falls_back_to_auto():
@@ -212,6 +156,6 @@ def test_small_sps_falls_back_to_auto():
     automatic shape and stays bit-exact."""
     iq = signals(2, 10)
     calls = ragged_calls(iq.shape[1] // 2, 2)
-    ref = oracle_calls(iq, calls, K.FS // 2, 10)
-    assert_same(gpu_calls(iq, calls, K.FS // 2, 10, loop_variant=5), ref)
-    assert_same(gpu_calls(iq, calls, K.FS // 2, 10, loop_variant=5, want_syms=False), ref)
+    ref = oracle_run(iq, calls, K.FS // 2, 10)
+    assert_same(gpu_run(iq, calls, K.FS // 2, 10, loop_variant=5), ref)
+    assert_same(gpu_run(iq, calls, K.FS // 2, 10, loop_variant=5, want_syms=False), ref)

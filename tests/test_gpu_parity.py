@@ -11,87 +11,17 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
+from gpu_harness import (assert_same, async_run, call_rows, decoded, dev, gpu_run, lengths_of, oracle_run,
+                         out_rows)
 
-pytestmark = pytest.mark.gpu
-
-SYM_TOL = 1e-5   # constellation tolerance vs the libm-trig oracle
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    yield
-
-
-def oracle_run(iq2d, calls, sps, span, mode=None, **kw):
-    """Per-stream oracle instances fed the same call sequence.
-    calls: list of per-call [S] lengths (complex samples); mode per call."""
-    S = iq2d.shape[0]
-    dms = [K.oracle_for(sps, span, **kw) for _ in range(S)]
-    pos = np.zeros(S, dtype=np.int64)
-    out = []
-    for ci, lens in enumerate(calls):
-        m = mode[ci] if mode else Q.MODE_DEMODULATE
-        res = []
-        for s in range(S):
-            x = iq2d[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-            if m == Q.MODE_DEMODULATE:
-                bits, syms, _ = dms[s].demodulate_ex(x)
-                res.append((bits, syms))
-            else:
-                res.append(("", dms[s].deModulateConstellation(x)))
-            pos[s] += lens[s]
-        out.append(res)
-    return out
-
-
-def gpu_run(iq2d, calls, sps, span, mode=None, want_syms=True, **kw):
-    """want_syms=False runs the bits-only kernel (decisions-only Costas ->
-    decode slots); its rows carry bits and None for the symbols."""
-    S = iq2d.shape[0]
-    p = Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=max(max(c) for c in calls) + 8, **kw)
-    b = Q.BatchDemodulator(S, p)
-    pos = np.zeros(S, dtype=np.int64)
-    out = []
-    for ci, lens in enumerate(calls):
-        m = mode[ci] if mode else Q.MODE_DEMODULATE
-        n = int(max(lens))
-        x = np.zeros((S, 2 * max(n, 1)), np.float32)
-        for s in range(S):
-            x[s, : 2 * lens[s]] = iq2d[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-        uniform = all(l == lens[0] for l in lens)
-        bits, nb, syms, ns = b.process(x[:, : 2 * n] if n else x[:, :0], mode=m,
-                                       lengths=None if uniform else np.array(lens), want_syms=want_syms)
-        res = []
-        for s in range(S):
-            bs = Q.unpack_bits(bits[s], int(nb[s])) if m == Q.MODE_DEMODULATE else ""
-            res.append((bs, syms[s, : 2 * int(ns[s])].copy() if want_syms else None))
-        pos += np.array(lens)
-        out.append(res)
-    b.close()
-    return out
-
-
-def assert_same(a, b, exact=True):
-    for ci, (ra, rb) in enumerate(zip(a, b)):
-        for s, ((ba, sa), (bb, sb)) in enumerate(zip(ra, rb)):
-            assert ba == bb, f"call {ci} stream {s}: bits differ ({len(ba)} vs {len(bb)})"
-            if sa is None or sb is None:
-                continue
-            assert sa.shape == sb.shape, f"call {ci} stream {s}: symbol count"
-            if exact:
-                assert K.bitwise_equal(sa, sb), f"call {ci} stream {s}: symbols differ (bitwise)"
-            else:
-                assert np.max(np.abs(sa - sb), initial=0) <= SYM_TOL
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("dev")]
 
 
 @pytest.mark.parametrize("sps,span", K.CONFIGS)
 def test_single_call_bit_exact(sps, span):
     iq = K.batch_signals(5, seed0=10, sps=sps, span=span, n_bits=3000, snr_db=16)
     calls = [[iq.shape[1] // 2] * 5]
-    assert_same(gpu_run(iq, calls, sps, span), oracle_run(iq, calls, sps, span))
+    assert_same(gpu_run(iq, calls, K.FS // sps, span), oracle_run(iq, calls, K.FS // sps, span))
 
 
 @pytest.mark.parametrize("sps,span", K.CONFIGS)
@@ -115,10 +45,10 @@ def test_chunked_ragged_calls_bit_exact(sps, span, variant):
         calls.append(c)
         left -= np.array(c)
         k += 1
-    ref = oracle_run(iq, calls, sps, span)
-    assert_same(gpu_run(iq, calls, sps, span, loop_variant=variant), ref)
+    ref = oracle_run(iq, calls, K.FS // sps, span)
+    assert_same(gpu_run(iq, calls, K.FS // sps, span, loop_variant=variant), ref)
     # the production bits-only kernel on the same ragged calls
-    assert_same(gpu_run(iq, calls, sps, span, loop_variant=variant, want_syms=False), ref)
+    assert_same(gpu_run(iq, calls, K.FS // sps, span, loop_variant=variant, want_syms=False), ref)
 
 
 @pytest.mark.parametrize("variant", [4, 6, 7])
@@ -136,9 +66,9 @@ def test_long_round_shapes_many_streams_bit_exact(variant):
         calls.append([int(v) for v in lens])
         used += lens
     calls.append([int(n - u) for u in used])
-    ref = oracle_run(iq, calls, sps, span)
-    assert_same(gpu_run(iq, calls, sps, span, loop_variant=variant), ref)
-    assert_same(gpu_run(iq, calls, sps, span, loop_variant=variant, want_syms=False), ref)
+    ref = oracle_run(iq, calls, K.FS // sps, span)
+    assert_same(gpu_run(iq, calls, K.FS // sps, span, loop_variant=variant), ref)
+    assert_same(gpu_run(iq, calls, K.FS // sps, span, loop_variant=variant, want_syms=False), ref)
 
 
 @pytest.mark.parametrize("sps,span", [(30, 6), (100, 4), (200, 2), (300, 2), (1000, 1)])
@@ -158,21 +88,21 @@ def test_large_sps_multi_call_bit_exact(sps, span):
         calls.append(c)
         left -= np.array(c)
         k += 1
-    assert_same(gpu_run(iq, calls, sps, span), oracle_run(iq, calls, sps, span))
+    assert_same(gpu_run(iq, calls, K.FS // sps, span), oracle_run(iq, calls, K.FS // sps, span))
 
 
 def test_empty_call_keeps_state():
     iq = K.batch_signals(2, seed0=30, n_bits=1200)
     n = iq.shape[1] // 2
     calls = [[n // 2] * 2, [0, 0], [n - n // 2] * 2]
-    assert_same(gpu_run(iq, calls, 8, 8), oracle_run(iq, calls, 8, 8))
+    assert_same(gpu_run(iq, calls, K.FS // 8, 8), oracle_run(iq, calls, K.FS // 8, 8))
 
 
 def test_nondifferential_bit_exact():
     iq = K.batch_signals(3, seed0=40, sps=4, span=32, n_bits=2000, snr_db=20, differential=False)
     calls = [[iq.shape[1] // 2] * 3]
-    assert_same(gpu_run(iq, calls, 4, 32, differential=False),
-                oracle_run(iq, calls, 4, 32, differential=False))
+    assert_same(gpu_run(iq, calls, K.FS // 4, 32, differential=False),
+                oracle_run(iq, calls, K.FS // 4, 32, differential=False))
 
 
 def test_constellation_mode_shares_state():
@@ -180,14 +110,14 @@ def test_constellation_mode_shares_state():
     n = iq.shape[1] // 2
     calls = [[n // 3] * 3, [n // 3] * 3, [n - 2 * (n // 3)] * 3]
     modes = [Q.MODE_DEMODULATE, Q.MODE_CONSTELLATION, Q.MODE_DEMODULATE]
-    assert_same(gpu_run(iq, calls, 8, 8, mode=modes), oracle_run(iq, calls, 8, 8, mode=modes))
+    assert_same(gpu_run(iq, calls, K.FS // 8, 8, mode=modes), oracle_run(iq, calls, K.FS // 8, 8, mode=modes))
 
 
 @pytest.mark.parametrize("lanes", [4, 1, 16])
 def test_other_vector_widths_bit_exact(lanes):
     iq = K.batch_signals(3, seed0=60, sps=8, span=8, n_bits=1500, snr_db=15)
     calls = [[5000] * 3, [iq.shape[1] // 2 - 5000] * 3]
-    assert_same(gpu_run(iq, calls, 8, 8, vector_lanes=lanes), oracle_run(iq, calls, 8, 8, lanes=lanes))
+    assert_same(gpu_run(iq, calls, K.FS // 8, 8, vector_lanes=lanes), oracle_run(iq, calls, K.FS // 8, 8, lanes=lanes))
 
 
 def test_even_tap_count_generic_path():
@@ -195,13 +125,13 @@ def test_even_tap_count_generic_path():
     for sps, span in [(3, 6), (3, 5)]:
         iq = K.batch_signals(2, seed0=70, sps=sps, span=span, n_bits=1500, snr_db=20)
         calls = [[iq.shape[1] // 2] * 2]
-        assert_same(gpu_run(iq, calls, sps, span), oracle_run(iq, calls, sps, span))
+        assert_same(gpu_run(iq, calls, K.FS // sps, span), oracle_run(iq, calls, K.FS // sps, span))
 
 
 def test_libm_oracle_bits_equal_symbols_close():
     iq = K.batch_signals(4, seed0=80, n_bits=4000, snr_db=14)
     calls = [[iq.shape[1] // 2] * 4]
-    assert_same(gpu_run(iq, calls, 8, 8), oracle_run(iq, calls, 8, 8, trig=O.TRIG_LIBM), exact=False)
+    assert_same(gpu_run(iq, calls, K.FS // 8, 8), oracle_run(iq, calls, K.FS // 8, 8, trig=O.TRIG_LIBM), exact=False)
 
 
 @pytest.mark.parametrize("lanes", [8, 4])
@@ -210,8 +140,8 @@ def test_fll_mode_bit_exact(lanes):
     iq = K.batch_signals(3, seed0=90, sps=8, span=8, n_bits=1200, cfo_hz=4000.0, snr_db=25)
     n = iq.shape[1] // 2
     calls = [[n // 2] * 3, [n - n // 2] * 3]
-    assert_same(gpu_run(iq, calls, 8, 8, enable_fll=True, cfo_loop_bandwidth=1e-3, vector_lanes=lanes),
-                oracle_run(iq, calls, 8, 8, enable_fll=True, cfo_loop_bw=1e-3, lanes=lanes))
+    assert_same(gpu_run(iq, calls, K.FS // 8, 8, enable_fll=True, cfo_loop_bandwidth=1e-3, vector_lanes=lanes),
+                oracle_run(iq, calls, K.FS // 8, 8, enable_fll=True, cfo_loop_bw=1e-3, lanes=lanes))
 
 
 def test_fll_ragged_chunks_bit_exact():
@@ -229,8 +159,8 @@ def test_fll_ragged_chunks_bit_exact():
         calls.append([int(v) for v in lens])
         used += lens
     calls.append([int(n - u) for u in used])
-    assert_same(gpu_run(iq, calls, 8, 8, enable_fll=True, cfo_loop_bandwidth=1e-3),
-                oracle_run(iq, calls, 8, 8, enable_fll=True, cfo_loop_bw=1e-3))
+    assert_same(gpu_run(iq, calls, K.FS // 8, 8, enable_fll=True, cfo_loop_bandwidth=1e-3),
+                oracle_run(iq, calls, K.FS // 8, 8, enable_fll=True, cfo_loop_bw=1e-3))
 
 
 def test_state_checkpoint_roundtrip():
@@ -244,7 +174,7 @@ def test_state_checkpoint_roundtrip():
     b = Q.BatchDemodulator(2, p)
     b.set_state(blob)
     bb, nb, _, _ = b.process(iq[:, 2 * h:])
-    ref = oracle_run(iq, [[h, h], [n - h, n - h]], 8, 8)
+    ref = oracle_run(iq, [[h, h], [n - h, n - h]], K.FS // 8, 8)
     for s in range(2):
         assert Q.unpack_bits(ba[s], int(na[s])) == ref[0][s][0]
         assert Q.unpack_bits(bb[s], int(nb[s])) == ref[1][s][0]
@@ -301,8 +231,8 @@ def test_synth_generated_batch_parity_and_ber():
     S, n = 8, 1 << 16
     iq, tx = Q.synth_generate(S, n, K.FS, K.FS // 8, rrc_span=8, seed=123)
     host = iq.cpu().numpy()
-    ref = oracle_run(host, [[n] * S], 8, 8)
-    got = gpu_run(host, [[n] * S], 8, 8)
+    ref = oracle_run(host, [[n] * S], K.FS // 8, 8)
+    got = gpu_run(host, [[n] * S], K.FS // 8, 8)
     assert_same(got, ref)
     txb = tx.cpu().numpy()
     clean = 0
@@ -320,72 +250,6 @@ def test_synth_generated_batch_parity_and_ber():
     assert clean >= S // 2
 
 
-def out_rows(S, ms, layout):
-    """Device output rows.  "direct": word-aligned rows the loop kernel writes
-    in place; "staged": a 1-byte-offset bit row of odd stride and an odd
-    symbol stride, which take the staging buffers and the 2-D copies."""
-    import torch
-    if layout == "staged":
-        bw = (2 * ms + 7) // 8 + 9
-        bw += 1 - bw % 2
-        bits = torch.zeros((S, bw + 1), dtype=torch.uint8, device="cuda")[:, 1:]
-        sy = torch.zeros((S, 2 * ms + 1), dtype=torch.float32, device="cuda")
-    else:
-        bits = torch.zeros((S, ((2 * ms + 7) // 8 + 63) // 64 * 64), dtype=torch.uint8, device="cuda")
-        sy = torch.zeros((S, 2 * ms), dtype=torch.float32, device="cuda")
-    return bits, sy
-
-
-def async_run(iq2d, calls, sps, span, sync_every=0, layout=None, **kw):
-    """The same call sequence through qpsk_demod_process_async (front stage of
-    call k+1 overlapping the back stage of call k), every call's outputs in
-    their own device rows, one pipeline_wait at the end.  sync_every > 0 makes
-    every sync_every-th call a synchronous process() (mixed ordering).
-    layout: None (rows as a caller would size them), or out_rows' layouts."""
-    import torch
-    S = iq2d.shape[0]
-    nmax = max(max(c) for c in calls)
-    p = Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=nmax + 8, **kw)
-    b = Q.BatchDemodulator(S, p)
-    stream = torch.cuda.Stream()
-    b.set_stream(stream.cuda_stream)
-    ms = max(b.max_symbols(nmax), 1)
-    pos = np.zeros(S, dtype=np.int64)
-    outs = []
-    with torch.cuda.stream(stream):
-        for ci, lens in enumerate(calls):
-            n = int(max(lens))
-            x = np.zeros((S, 2 * max(n, 1)), np.float32)
-            for s in range(S):
-                x[s, : 2 * lens[s]] = iq2d[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-            xd = torch.from_numpy(x).to("cuda", non_blocking=False)
-            if layout:
-                bits, sy = out_rows(S, ms, layout)
-            else:
-                bits = torch.zeros((S, (2 * ms + 7) // 8 + 8), dtype=torch.uint8, device="cuda")
-                sy = torch.zeros((S, 2 * ms), dtype=torch.float32, device="cuda")
-            nb = torch.zeros(S, dtype=torch.int64, device="cuda")
-            ns = torch.zeros(S, dtype=torch.int64, device="cuda")
-            uniform = all(l == lens[0] for l in lens)
-            if sync_every and ci % sync_every == sync_every - 1:
-                assert uniform
-                b.process_device(xd, n, bits, nb, syms_dev=sy, n_syms_dev=ns)
-            else:
-                b.process_device_async(xd, n, bits, nb, syms_dev=sy, n_syms_dev=ns,
-                                       lengths=None if uniform else np.array(lens))
-            outs.append((xd, bits, nb, sy, ns))
-            pos += np.array(lens)
-    depth = b.pipeline_depth()
-    b.pipeline_wait()
-    torch.cuda.synchronize()
-    res = []
-    for _, bits, nb, sy, ns in outs:
-        bits, nb, sy, ns = bits.cpu().numpy(), nb.cpu().numpy(), sy.cpu().numpy(), ns.cpu().numpy()
-        res.append([(Q.unpack_bits(bits[s], int(nb[s])), sy[s, : 2 * int(ns[s])].copy()) for s in range(S)])
-    b.close()
-    return res, depth
-
-
 @pytest.mark.parametrize("layout", ["direct", "staged"])
 @pytest.mark.parametrize("sync_every,fll", [(0, False), (2, False), (0, True)])
 def test_device_output_rows_in_place_or_staged(layout, sync_every, fll):
@@ -399,7 +263,7 @@ def test_device_output_rows_in_place_or_staged(layout, sync_every, fll):
     n = iq.shape[1] // 2
     calls = [[n // 4] * 4, [n // 3] * 4, [n // 5] * 4, [n - n // 4 - n // 3 - n // 5] * 4]
     got, _ = async_run(iq, calls, 8, 8, sync_every=sync_every, layout=layout, **kw)
-    assert_same(got, oracle_run(iq, calls, 8, 8, **okw))
+    assert_same(got, oracle_run(iq, calls, K.FS // 8, 8, **okw))
 
 
 @pytest.mark.parametrize("fll", [False, True])
@@ -422,7 +286,7 @@ def test_pipelined_calls_bit_exact(fll):
     calls.append([int(n - u) for u in used])
     got, depth = async_run(iq, calls, 8, 8, **kw)
     assert depth == 2
-    assert_same(got, oracle_run(iq, calls, 8, 8, **okw))
+    assert_same(got, oracle_run(iq, calls, K.FS // 8, 8, **okw))
 
 
 def test_pipelined_mixed_with_sync_calls():
@@ -432,7 +296,7 @@ def test_pipelined_mixed_with_sync_calls():
     k = n // 6
     calls = [[k] * 3 for _ in range(5)] + [[n - 5 * k] * 3]
     got, _ = async_run(iq, calls, 4, 32, sync_every=2)
-    assert_same(got, oracle_run(iq, calls, 4, 32))
+    assert_same(got, oracle_run(iq, calls, K.FS // 4, 32))
 
 
 def test_huge_amplitude_takes_the_costas_rollback_path():
@@ -442,7 +306,7 @@ def test_huge_amplitude_takes_the_costas_rollback_path():
     iq = K.batch_signals(3, seed0=300, sps=8, span=8, n_bits=800, snr_db=20) * np.float32(1e12)
     n = iq.shape[1] // 2
     calls = [[n // 3] * 3, [n - n // 3] * 3]
-    got, ref = gpu_run(iq, calls, 8, 8), oracle_run(iq, calls, 8, 8)
+    got, ref = gpu_run(iq, calls, K.FS // 8, 8), oracle_run(iq, calls, K.FS // 8, 8)
     for ci, (ra, rb) in enumerate(zip(got, ref)):
         for s, ((ba, sa), (bb, sb)) in enumerate(zip(ra, rb)):
             assert ba == bb, f"call {ci} stream {s}: bits differ"
@@ -468,7 +332,7 @@ def test_degenerate_streams_bit_exact(sps, span):
     calls = [[n // 3 + 100] * 6, [0, 5, 17, 1, 300, 2], [n - n // 3 - 100, n - n // 3 - 105,
                                                         n - n // 3 - 117, n - n // 3 - 101,
                                                         n - n // 3 - 400, n - n // 3 - 102]]
-    got, ref = gpu_run(iq, calls, sps, span), oracle_run(iq, calls, sps, span)
+    got, ref = gpu_run(iq, calls, K.FS // sps, span), oracle_run(iq, calls, K.FS // sps, span)
     for ci, (ra, rb) in enumerate(zip(got, ref)):
         for s, ((ba, sa), (bb, sb)) in enumerate(zip(ra, rb)):
             assert ba == bb, f"call {ci} stream {s}: bits differ"
@@ -487,11 +351,10 @@ def ring_run(iq2d, calls, sps, span, depth=2, zero_copy=False, **kw):
 
     def collect():
         bits, nb, _ = ring.collect()
-        out.append([(Q.unpack_bits(bits[s], int(nb[s])), None) for s in range(S)])
+        out.append(decoded(Q.MODE_DEMODULATE, bits, nb, None, None))
 
     for lens in calls:
         n = int(max(lens))
-        uniform = all(l == lens[0] for l in lens)
         if pending == depth:
             collect()
             pending -= 1
@@ -499,12 +362,11 @@ def ring_run(iq2d, calls, sps, span, depth=2, zero_copy=False, **kw):
             slot = ring.next_slot()
             for s in range(S):
                 slot[s, : 2 * lens[s]] = iq2d[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-            ring.submit(None, n, None if uniform else np.array(lens))
+            ring.submit(None, n, lengths_of(lens))
         else:
             x = np.zeros((S, 2 * max(n, 1)), np.float32)
-            for s in range(S):
-                x[s, : 2 * lens[s]] = iq2d[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-            ring.submit(x, n, None if uniform else np.array(lens))
+            x[:, : 2 * n] = call_rows(iq2d, lens, pos)
+            ring.submit(x, n, lengths_of(lens))
         pending += 1
         pos += np.array(lens)
     while pending:
@@ -540,7 +402,7 @@ def test_host_ring_bit_exact(depth, zero_copy, fll):
         used += lens
     calls.append([int(n - u) for u in used])
     got = ring_run(iq, calls, 8, 8, depth=depth, zero_copy=zero_copy, **kw)
-    assert_same_bits(got, oracle_run(iq, calls, 8, 8, **okw))
+    assert_same_bits(got, oracle_run(iq, calls, K.FS // 8, 8, **okw))
 
 
 def test_host_ring_errors():
@@ -611,10 +473,7 @@ def test_device_constellation_rows_in_place_or_staged(layout, pipelined):
             pos += k
     b.pipeline_wait()
     torch.cuda.synchronize()
-    got = []
-    for _, bits, nb, sy, ns, m in outs:
-        bits, nb, sy, ns = bits.cpu().numpy(), nb.cpu().numpy(), sy.cpu().numpy(), ns.cpu().numpy()
-        got.append([(Q.unpack_bits(bits[s], int(nb[s])) if m == Q.MODE_DEMODULATE else "",
-                     sy[s, : 2 * int(ns[s])].copy()) for s in range(S)])
+    got = [decoded(m, bits.cpu().numpy(), nb.cpu().numpy(), sy.cpu().numpy(), ns.cpu().numpy())
+           for _, bits, nb, sy, ns, m in outs]
     b.close()
-    assert_same(got, oracle_run(iq, calls, 8, 8, mode=modes))
+    assert_same(got, oracle_run(iq, calls, K.FS // 8, 8, mode=modes))

@@ -10,17 +10,9 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
-from test_gpu_parity import SYM_TOL, assert_same, gpu_run, oracle_run
+from gpu_harness import assert_same, async_run, dev, gpu_run, oracle_run
 
-pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    yield
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("dev")]
 
 
 def _rows(t, idx):
@@ -65,8 +57,8 @@ def test_fll_mode_vs_libm_oracle(seed):
                          snr_db=20)
     n = iq.shape[1] // 2
     calls = [[n // 3] * 4, [n - n // 3] * 4]
-    got = gpu_run(iq, calls, 8, 8, enable_fll=True, cfo_loop_bandwidth=1e-3)
-    ref = oracle_run(iq, calls, 8, 8, enable_fll=True, cfo_loop_bw=1e-3, trig=O.TRIG_LIBM)
+    got = gpu_run(iq, calls, K.FS // 8, 8, enable_fll=True, cfo_loop_bandwidth=1e-3)
+    ref = oracle_run(iq, calls, K.FS // 8, 8, enable_fll=True, cfo_loop_bw=1e-3, trig=O.TRIG_LIBM)
     assert_same(got, ref, exact=False)
 
 
@@ -75,8 +67,8 @@ def test_fll_mode_default_bandwidth_vs_libm_oracle():
     iq = K.batch_signals(2, seed0=530, sps=8, span=8, n_bits=20000, cfo_hz=5000.0, multipath=True,
                          snr_db=20)
     calls = [[iq.shape[1] // 2] * 2]
-    got = gpu_run(iq, calls, 8, 8, enable_fll=True)
-    ref = oracle_run(iq, calls, 8, 8, enable_fll=True, trig=O.TRIG_LIBM)
+    got = gpu_run(iq, calls, K.FS // 8, 8, enable_fll=True)
+    ref = oracle_run(iq, calls, K.FS // 8, 8, enable_fll=True, trig=O.TRIG_LIBM)
     assert_same(got, ref, exact=False)
 
 
@@ -109,7 +101,7 @@ def test_chunked_device_and_pipelined_calls():
     n = iq.shape[1] // 2
     half = n // 2
     cap = half // 2 - 7
-    ref = oracle_run(iq, [[half] * S, [n - half] * S], 8, 8)
+    ref = oracle_run(iq, [[half] * S, [n - half] * S], K.FS // 8, 8)
     for pipelined in (False, True):
         b = Q.BatchDemodulator(S, Q.params(K.FS, K.FS // 8, K.ALPHA, 8, max_samples_per_call=cap))
         ms = b.max_symbols(n)
@@ -279,10 +271,9 @@ def test_iq_balance_prestage_bit_exact(fll):
     calls = [[n // 3, n // 2, 100], [n - n // 3, n - n // 2, n - 100]]
     kw = dict(enable_fll=fll, cfo_loop_bandwidth=1e-3) if fll else {}
     okw = dict(enable_fll=fll, cfo_loop_bw=1e-3) if fll else {}
-    got = gpu_run(iq, calls, 8, 8, iq_balance=True, **kw)
-    ref = oracle_run(iq, calls, 8, 8, iq_balance=True, **okw)
+    got = gpu_run(iq, calls, K.FS // 8, 8, iq_balance=True, **kw)
+    ref = oracle_run(iq, calls, K.FS // 8, 8, iq_balance=True, **okw)
     assert_same(got, ref)
-    from test_gpu_parity import async_run
     got_async, _ = async_run(iq, calls, 8, 8, iq_balance=True, **kw)
     assert_same(got_async, ref)
 

@@ -36,9 +36,9 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
-from test_gpu_parity import oracle_run
-from test_group import _rows_of_call
-from test_state_blob import bad_blob
+import gpu_harness as H
+from gpu_harness import as_fmt, call_rows, decoded, dev, oracle_run, quantised, widened
+from state_blobs import bad_blob
 
 gpu = pytest.mark.gpu
 
@@ -70,14 +70,6 @@ def taps_of(sps, span):
     return sps * span + 1
 
 
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need an MI355X")
-    return torch
-
-
 # ---------------------------------------------------------------------------
 # signals, the call sequence, the oracle
 # ---------------------------------------------------------------------------
@@ -85,7 +77,7 @@ def dev():
 def signal_i8(sps, span):
     base = K.batch_signals(S, seed0=3100 + sps, sps=sps, span=span, n_bits=16000 // sps, snr_db=16,
                            cfo_hz=2000.0)
-    q = np.round(base * (64.0 / np.abs(base).max())).astype(np.int8)
+    q = quantised(base, "cs8")
     q.setflags(write=False)
     return q
 
@@ -94,7 +86,7 @@ def signal_i8(sps, span):
 def signal(sps, span, kind):
     """[S, 2n] float32 rows, about 8 000 samples each, 2 kHz off tune."""
     if kind == "q8":
-        x = signal_i8(sps, span).astype(np.float32) * np.float32(1.0 / 128.0)
+        x = widened(signal_i8(sps, span), "cs8")
     else:
         x = K.batch_signals(S, seed0=3100 + sps, sps=sps, span=span, n_bits=16000 // sps, snr_db=16,
                             cfo_hz=2000.0)
@@ -151,25 +143,16 @@ def oracle_trace(cfg, sps, span, lanes=8, lanes_after=None):
     instance moves to Vector width w after call k."""
     _, okw, kind, _ = CFGS[cfg]
     iq, calls = signal(sps, span, kind), sequence(sps, span)
-    modes = call_modes(cfg, len(calls))
-    dms = [K.oracle_for(sps, span, lanes=lanes, **okw) for _ in range(S)]
-    pos = np.zeros(S, np.int64)
-    outs, states = [], []
-    for ci, lens in enumerate(calls):
-        res = []
-        for s in range(S):
-            x = iq[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-            if modes[ci] == Q.MODE_DEMODULATE:
-                bits, syms, _ = dms[s].demodulate_ex(x)
-                res.append((bits, syms))
-            else:
-                res.append(("", dms[s].deModulateConstellation(x)))
-            pos[s] += lens[s]
-        outs.append(res)
+    states = []
+
+    def after_call(ci, dms):
         states.append([d.read_state() for d in dms])
         if lanes_after and lanes_after[0] == ci:
             for d in dms:
                 d.set_lanes(lanes_after[1])
+
+    outs = oracle_run(iq, calls, K.FS // sps, span, mode=call_modes(cfg, len(calls)), after_call=after_call,
+                      lanes=lanes, **okw)
     return outs, states
 
 
@@ -182,11 +165,6 @@ def make_handle(cfg, sps, span, n_streams=S, msc=None, **knobs):
     n = signal(sps, span, "base").shape[1] // 2
     return Q.BatchDemodulator(n_streams, Q.params(K.FS, K.FS // sps, K.ALPHA, span,
                                                   max_samples_per_call=msc or n, **gkw))
-
-
-def decoded(mode, bits, nb, syms, ns, rows=range(S)):
-    return [(Q.unpack_bits(bits[s], int(nb[s])) if mode == Q.MODE_DEMODULATE else "",
-             syms[s, : 2 * int(ns[s])].copy()) for s in rows]
 
 
 def assert_out(got, want, what):
@@ -202,15 +180,7 @@ def host_call(b, cfg, sps, span, ci, rows=None, fmt=None):
     lens = np.array(calls[ci], np.int64)
     mode = call_modes(cfg, len(calls))[ci]
     pos = positions(calls, ci - 1)
-    if fmt is None:
-        res = b.process(_rows_of_call(rows, pos, lens), mode=mode, lengths=lens, want_syms=True)
-    else:
-        n = int(lens.max())
-        x = np.zeros((S, 2 * n), rows.dtype)
-        for s in range(S):
-            x[s, : 2 * lens[s]] = rows[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-        res = b.process_fmt(x, fmt, mode=mode, lengths=lens, want_syms=True)
-    return decoded(mode, *res)
+    return H.host_call(b, call_rows(rows, lens, pos), lens, mode, fmt or "cf32", family="fmt")
 
 
 def run_rest(b, cfg, sps, span, first, want, what, **kw):
@@ -286,7 +256,7 @@ def test_sequence_reaches_its_edges(sps, span):
     assert sum(calls[ALL_EMPTY]) == 0 and len(calls) == 12
     assert sum(0 in c for c in ragged) >= 5, "an empty call for one stream only"
     outs, states = oracle_trace("fll", sps, span)
-    ref = oracle_run(signal(sps, span, "base"), [list(c) for c in calls], sps, span, **OFLL)
+    ref = oracle_run(signal(sps, span, "base"), [list(c) for c in calls], K.FS // sps, span, **OFLL)
     for ci in range(len(calls)):   # the trace is oracle_run with the fields read in between
         assert_out(outs[ci], ref[ci], f"call {ci}")
     assert sum(len(b) for b, _ in outs[-1]) > 2 * 4000 // sps * S
@@ -455,7 +425,7 @@ def async_calls(torch, b, cfg, sps, span, first, last, peek=()):
             lens = np.array(calls[ci], np.int64)
             n = int(lens.max())
             x = np.zeros((S, 2 * max(n, 1)), np.float32)
-            x[:, : 2 * n] = _rows_of_call(rows, positions(calls, ci - 1), lens)
+            x[:, : 2 * n] = call_rows(rows, lens, positions(calls, ci - 1))
             xd = torch.from_numpy(x).to("cuda")
             bits = torch.zeros((S, (2 * ms + 7) // 8 + 8), dtype=torch.uint8, device="cuda")
             sy = torch.zeros((S, 2 * ms), dtype=torch.float32, device="cuda")
@@ -499,10 +469,8 @@ def test_blob_moves_to_a_taker_fed_integer_rows(dev, fmt, sps, span):
     """A runs on the floats the integer rows widen to (the signal quantised to
     int8 steps first, as the format tests do); the taker gets the rows."""
     v = signal_i8(sps, span)
-    rows = {"cs8": v, "cu8": (v.astype(np.int16) + 128).astype(np.uint8), "cs16": v.astype(np.int16) * 256}[fmt]
-    scale = {"cs8": 1.0 / 128.0, "cu8": 1.0 / 128.0, "cs16": 1.0 / 32768.0}[fmt]
-    wide = (v if fmt != "cs16" else rows).astype(np.float32) * np.float32(scale)
-    assert K.bitwise_equal(wide, signal(sps, span, "q8"))
+    rows = as_fmt(v, fmt)
+    assert K.bitwise_equal(widened(rows, fmt), signal(sps, span, "q8"))
     want, _ = oracle_trace("fll-q8", sps, span)
     _, blobs = run_a("fll-q8", sps, span)
     k = 4
@@ -533,7 +501,7 @@ def test_blob_moves_into_a_group_shard_and_back(dev, sps, span):
     assert grp.get_state(1) == blobs[k] and grp.get_state(0) == fresh
     lens = np.concatenate([np.zeros(S, np.int64), np.array(calls[k + 1], np.int64)])
     pos = np.concatenate([np.zeros(S, np.int64), positions(calls, k)])
-    res = grp.process(_rows_of_call(np.concatenate([rows, rows]), pos, lens), lengths=lens, want_syms=True)
+    res = grp.process(call_rows(np.concatenate([rows, rows]), lens, pos), lengths=lens, want_syms=True)
     assert_out(decoded(Q.MODE_DEMODULATE, *res, rows=range(S, 2 * S)), want[k + 1], f"group shard 1, call {k + 1}")
     assert int(res[1][:S].sum()) == 0 and grp.get_state(0) == fresh
     back = grp.get_state(1)

@@ -21,6 +21,7 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
+from gpu_harness import call_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.argv = sys.argv[:1]
@@ -78,15 +79,6 @@ def _ragged_calls(S, n, rng):
     return calls
 
 
-def _rows_of_call(iq, pos, lens):
-    S = iq.shape[0]
-    n = int(lens.max())
-    x = np.zeros((S, 2 * max(n, 1)), np.float32)
-    for s in range(S):
-        x[s, : 2 * lens[s]] = iq[s, 2 * pos[s]: 2 * (pos[s] + lens[s])]
-    return x[:, : 2 * n]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("sps,span,S", [(8, 8, 7), (4, 32, 6)])
 def test_group_two_shards_equal_one_handle_host_memory(sps, span, S):
@@ -103,7 +95,7 @@ def test_group_two_shards_equal_one_handle_host_memory(sps, span, S):
     last = S - 1          # the second shard's last stream
     rows_last = []
     for ci, lens in enumerate(calls):
-        x = _rows_of_call(iq, pos, lens)
+        x = call_rows(iq, lens, pos)
         a = one.process(x, lengths=lens, want_syms=True)
         b = grp.process(x, lengths=lens, want_syms=True)
         rows_last.append((Q.unpack_bits(b[0][last], int(b[1][last])), b[2][last, : 2 * int(b[3][last])].copy()))

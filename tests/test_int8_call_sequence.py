@@ -1,8 +1,7 @@
-"""The call sequence of tests/test_gpu_int8.py is what its cases need (no GPU):
+"""The 8-bit call sequence of tests/gpu_format_cases.py is what its cases need (no GPU):
 with 8-sample loads every residue of a row's length mod 8 must end a row past
 the first tile."""
-from test_gpu_fir import SPECIALISED, TILE
-from test_gpu_int8 import calls_for
+from gpu_harness import SPECIALISED, TILE, calls_for
 
 
 def test_call_sequence_ends_rows_at_every_residue_mod_8():

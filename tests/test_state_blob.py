@@ -26,9 +26,8 @@ import pytest
 
 import common as K
 import qpsk_amd as Q
+from state_blobs import CARRY_MAX, FLL_TAPS, fresh_records, make_blob
 
-MAGIC, FORMAT = 0x4B535051, 2
-CARRY_MAX, FLL_TAPS = 256, 40
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 # (sps, span): the two shapes of the GPU tests, and a fractional sps
 SHAPES = [(8, 8), (4, 32)]
@@ -47,37 +46,10 @@ def base_hi(sps):
     return 1 + math.ceil(sps + 0.1)
 
 
-def fresh_records(n):
-    """A new handle's records: base = 1, everything else zero."""
-    rec = np.zeros(n, dtype=Q.STREAM_STATE_DTYPE)
-    rec["base"] = 1
-    return rec
-
-
-def make_blob(rec, taps, carry=None, hist=None, delay=None, magic=MAGIC, fmt=FORMAT, streams=None,
-              hdr_taps=None):
-    n = rec.size
-    hd = np.array([0, 0, streams if streams is not None else n, hdr_taps if hdr_taps is not None else taps,
-                   CARRY_MAX, FLL_TAPS, Q.STREAM_STATE_DTYPE.itemsize, 0], dtype=np.int32)
-    hd.view(np.uint32)[:2] = (magic, fmt)
-    carry = np.zeros((n, CARRY_MAX, 2), np.float32) if carry is None else carry
-    hist = np.zeros((n, taps - 1, 2), np.float32) if hist is None else hist
-    delay = np.zeros((n, 2 * FLL_TAPS, 2), np.float32) if delay is None else delay
-    return b"".join(a.tobytes() for a in (hd, rec, carry, hist, delay))
-
-
 def edited(sps, span, stream, **fields):
     rec = fresh_records(S)
     for k, v in fields.items():
         rec[k][stream] = v
-    return make_blob(rec, taps_of(sps, span))
-
-
-def bad_blob(sps, span, n_streams, stream, field, value):
-    """One valid blob of n_streams fresh records with one field of one stream
-    set to value (tests/test_gpu_state.py feeds these to live handles)."""
-    rec = fresh_records(n_streams)
-    rec[field][stream] = value
     return make_blob(rec, taps_of(sps, span))
 
 
