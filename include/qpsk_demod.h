@@ -424,6 +424,71 @@ int qpsk_demod_enable_link_stats(qpsk_demod *h, int32_t on);
 int qpsk_demod_link_stats(qpsk_demod *h, qpsk_link_stats *out, int32_t mem, int32_t reset);
 
 /* ---------------------------------------------------------------------------
+ * Selected streams: reset, read and write the state of the rows a caller
+ * names, and of no other.  (Added within ABI version 3: no existing entry
+ * point or the blob layout changed.)
+ *
+ * The reference constructs and drops each receiver on its own
+ * (QPSKDeModulator.cs:11-56); a handle makes all of its rows at once, and
+ * qpsk_demod_get_state / set_state move all of them.  These calls give one row
+ * the lifetime of one instance: a new receiver on row s (a stream in a Costas
+ * false lock, a client that reconnects), and a stream moved to another handle
+ * or another GPU, at the cost of the rows moved.
+ *
+ * A stream list is n indices into the batch: 1 <= n <= n_streams, every index
+ * in [0, n_streams), none twice, in any order; else QPSK_ERR_ARGUMENT, and
+ * qpsk_last_error names the position and the value.
+ *
+ * The rows of n listed streams, laid out as header (streams = n), records,
+ * carries, histories and delay lines in list order, are themselves a state
+ * blob of an n-stream handle with the same tap count: a "sub-blob" is no new
+ * format.  qpsk_state_blob_check(p, n, sub, bytes) and qpsk_demod_set_state of
+ * an n-stream handle take it as it is.
+ */
+/* The three below need no device and no handle (p as in qpsk_state_blob_check). */
+int qpsk_stream_list_check(int32_t n_streams, const int32_t *streams, int32_t n);
+/* sub <- the sub-blob of rows streams[0..n) of blob, in list order.  First
+ * qpsk_state_blob_check on blob for (p, n_streams); blob_bytes and sub_bytes
+ * are exact.  A rejected call writes nothing. */
+int qpsk_state_blob_select(const qpsk_demod_params *p, int32_t n_streams, const void *blob, int64_t blob_bytes,
+                           const int32_t *streams, int32_t n, void *sub, int64_t sub_bytes);
+/* Row streams[i] of blob <- row i of sub, and no other byte of blob.  First
+ * qpsk_state_blob_check on sub for (p, n) and on blob for (p, n_streams).  A
+ * rejected call changes nothing. */
+int qpsk_state_blob_merge(const qpsk_demod_params *p, int32_t n_streams, void *blob, int64_t blob_bytes,
+                          const int32_t *streams, int32_t n, const void *sub, int64_t sub_bytes);
+/* On a handle.  Each call checks its arguments on the host first (a rejected
+ * call neither waits nor changes anything), then waits for every queued call,
+ * pipelined ones included, as qpsk_demod_set_state and qpsk_demod_link_stats
+ * do: a stream's record holds fields of both pipeline stages, so no row is
+ * written between queued calls (DESIGN.md 3.12 has the cost).  It then runs on
+ * the handle's stream and returns when done.  Like qpsk_demod_link_stats they
+ * may be called on a handle that feeds a qpsk_rx ring, between submits.
+ * Handle-wide things stay as they are: status flags, input scales, timing
+ * records.
+ *
+ * reset_streams is `new QPSKDeModulator(...)` on those rows: the symbol-sync
+ * and Costas loops, the matched filter's history, the FLL and IQ-balancer
+ * state, the differential decoder (the fields of QPSKDeModulator.cs:20-73) and
+ * the sticky `error` go back to construction, and the rows' three link sums
+ * are zeroed (a new receiver has seen no symbol).  n = 0 is QPSK_OK and does
+ * nothing.
+ *
+ * streams_state_bytes: the bytes of a blob of n streams; 0 for a null handle
+ * or n outside [1, n_streams].  get_streams_state writes the sub-blob of the
+ * listed rows as they are (buf_bytes exactly streams_state_bytes; a row with a
+ * carry-overflow record is returned, and a later set refuses it).
+ * set_streams_state runs qpsk_state_blob_check on the sub-blob for n streams,
+ * then overwrites the listed rows; it leaves the link sums alone, as
+ * qpsk_demod_set_state does.  For both n = 0 is QPSK_ERR_ARGUMENT: there is no
+ * blob of zero streams. */
+int qpsk_demod_reset_streams(qpsk_demod *h, const int32_t *streams, int32_t n);
+int64_t qpsk_demod_streams_state_bytes(const qpsk_demod *h, int32_t n);
+int qpsk_demod_get_streams_state(qpsk_demod *h, const int32_t *streams, int32_t n, void *host_buf, int64_t buf_bytes);
+int qpsk_demod_set_streams_state(qpsk_demod *h, const int32_t *streams, int32_t n, const void *host_buf,
+                                 int64_t buf_bytes);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU group: one batch of n_streams over several GPUs,
  * for a host (the C# shim, a C++ driver) that wants the whole node behind one
  * object.  Every reference instance owns its loop state (QPSKDeModulator.cs:20-73),
@@ -474,6 +539,16 @@ int qpsk_demod_group_set_state(qpsk_demod_group *g, int32_t k, const void *host_
  * rows of all n_streams streams in stream order, in host memory. */
 int qpsk_demod_group_enable_link_stats(qpsk_demod_group *g, int32_t on);
 int qpsk_demod_group_link_stats(qpsk_demod_group *g, qpsk_link_stats *out_host, int32_t reset);
+/* Selected streams of the group by global stream id (0 .. n_streams - 1 over
+ * the whole batch).  The list, and for set the whole sub-blob, is checked
+ * before any shard runs; each shard then works on its own rows on its worker.
+ * A stream moves between GPUs in two calls: get on one id, set on another. */
+int qpsk_demod_group_reset_streams(qpsk_demod_group *g, const int32_t *streams, int32_t n);
+int64_t qpsk_demod_group_streams_state_bytes(const qpsk_demod_group *g, int32_t n);
+int qpsk_demod_group_get_streams_state(qpsk_demod_group *g, const int32_t *streams, int32_t n, void *host_buf,
+                                       int64_t buf_bytes);
+int qpsk_demod_group_set_streams_state(qpsk_demod_group *g, const int32_t *streams, int32_t n,
+                                       const void *host_buf, int64_t buf_bytes);
 
 /* ---------------------------------------------------------------------------
  * Host-fed streaming front-end: the deployment shape of

@@ -27,6 +27,7 @@
 
 #include "qpsk_demod.h"
 #include "qpsk_internal.h"
+#include "qpsk_state_blob.h"
 
 namespace {
 using qpsk::fail;
@@ -39,6 +40,7 @@ struct Shard {
 
 struct qpsk_demod_group {
     int32_t S = 0;
+    qpsk_demod_params p{};   // as given to create (every shard's, but for the device)
     std::vector<Shard> shards;
     // worker pool: worker k runs job(k) for every generation, then counts down
     std::vector<std::thread> threads;
@@ -137,6 +139,7 @@ int qpsk_demod_group_create(const qpsk_demod_params *p, const int32_t *devices, 
         if (devices[k] < 0) return fail(QPSK_ERR_ARGUMENT, "negative device ordinal");
     auto *g = new qpsk_demod_group();
     g->S = n_streams;
+    g->p = *p;
     g->shards.resize(n_dev);
     g->rc.assign(n_dev, QPSK_OK);
     g->err.assign(n_dev, std::string());
@@ -257,6 +260,107 @@ int qpsk_demod_group_set_state(qpsk_demod_group *g, int32_t k, const void *host_
     if (!g) return fail(QPSK_ERR_ARGUMENT_NULL, "null group");
     if (k < 0 || k >= static_cast<int32_t>(g->shards.size())) return fail(QPSK_ERR_ARGUMENT, "no such shard");
     return qpsk_demod_set_state(g->shards[k].h, host_buf, buf_bytes);
+}
+
+}  // extern "C"
+
+namespace {
+
+// A list of global stream ids cut by shard: each shard's local ids, and the
+// positions in the caller's list they came from (a shard off the list has none).
+struct ShardLists {
+    std::vector<std::vector<int32_t>> local, pos;
+};
+
+ShardLists split_list(const qpsk_demod_group *g, const int32_t *streams, int32_t n) {
+    ShardLists l;
+    l.local.resize(g->shards.size());
+    l.pos.resize(g->shards.size());
+    for (int32_t i = 0; i < n; ++i) {
+        size_t k = 0;
+        while (streams[i] >= g->shards[k].first + g->shards[k].count) ++k;   // the list is checked: it ends
+        l.local[k].push_back(streams[i] - g->shards[k].first);
+        l.pos[k].push_back(i);
+    }
+    return l;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Selected streams by global id (qpsk_stream_state.hip): the list is checked
+// on the whole batch before any shard runs, each shard then works on its
+// local list, and a sub-blob is cut and put together on the host.
+int qpsk_demod_group_reset_streams(qpsk_demod_group *g, const int32_t *streams, int32_t n) {
+    if (!g) return fail(QPSK_ERR_ARGUMENT_NULL, "null group");
+    if (n == 0) return QPSK_OK;
+    int rc;
+    if ((rc = qpsk::stream_list_check(g->S, streams, n))) return rc;
+    const ShardLists l = split_list(g, streams, n);
+    return fan_out(g, [g, &l](int k) {
+        const std::vector<int32_t> &ids = l.local[k];
+        return ids.empty() ? QPSK_OK : qpsk_demod_reset_streams(g->shards[k].h, ids.data(), static_cast<int32_t>(ids.size()));
+    });
+}
+
+int64_t qpsk_demod_group_streams_state_bytes(const qpsk_demod_group *g, int32_t n) {
+    if (!g || n < 1 || n > g->S) return 0;
+    return qpsk::state_blob_bytes(n, qpsk::handle_taps(g->shards[0].h));
+}
+
+int qpsk_demod_group_get_streams_state(qpsk_demod_group *g, const int32_t *streams, int32_t n, void *host_buf,
+                                       int64_t buf_bytes) {
+    if (!g || !streams || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    int rc;
+    if ((rc = qpsk::stream_list_check(g->S, streams, n))) return rc;
+    const int32_t T = qpsk::handle_taps(g->shards[0].h);
+    if (buf_bytes != qpsk::state_blob_bytes(n, T))
+        return fail(QPSK_ERR_ARGUMENT, "the state buffer holds " + std::to_string(buf_bytes) + " bytes, " +
+                                           std::to_string(n) + " streams take " +
+                                           std::to_string(qpsk::state_blob_bytes(n, T)));
+    const ShardLists l = split_list(g, streams, n);
+    std::vector<std::vector<char>> part(g->shards.size());
+    if ((rc = fan_out(g, [g, &l, &part, T](int k) {
+            const int32_t m = static_cast<int32_t>(l.local[k].size());
+            if (!m) return QPSK_OK;
+            part[k].resize(static_cast<size_t>(qpsk::state_blob_bytes(m, T)));
+            return qpsk_demod_get_streams_state(g->shards[k].h, l.local[k].data(), m, part[k].data(),
+                                                static_cast<int64_t>(part[k].size()));
+        })))
+        return rc;
+    // shard k's row i is the caller's row pos[k][i]
+    const qpsk::StateHeader hd = qpsk::state_header(n, T);
+    std::memcpy(host_buf, &hd, sizeof(hd));
+    for (size_t k = 0; k < part.size(); ++k)
+        if (!l.pos[k].empty())
+            qpsk::state_blob_scatter_rows(n, T, host_buf, l.pos[k].data(), static_cast<int32_t>(l.pos[k].size()),
+                                          part[k].data());
+    return QPSK_OK;
+}
+
+int qpsk_demod_group_set_streams_state(qpsk_demod_group *g, const int32_t *streams, int32_t n, const void *host_buf,
+                                       int64_t buf_bytes) {
+    if (!g || !streams || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    int rc;
+    // the whole list and the whole sub-blob first: a rejected call moves no shard's state
+    if ((rc = qpsk::stream_list_check(g->S, streams, n)) || (rc = qpsk_state_blob_check(&g->p, n, host_buf, buf_bytes)))
+        return rc;
+    const int32_t T = qpsk::handle_taps(g->shards[0].h);
+    const ShardLists l = split_list(g, streams, n);
+    std::vector<std::vector<char>> part(g->shards.size());
+    for (size_t k = 0; k < part.size(); ++k) {
+        const int32_t m = static_cast<int32_t>(l.pos[k].size());
+        if (!m) continue;
+        part[k].resize(static_cast<size_t>(qpsk::state_blob_bytes(m, T)));
+        qpsk::state_blob_gather_rows(n, T, host_buf, l.pos[k].data(), m, part[k].data());
+    }
+    return fan_out(g, [g, &l, &part](int k) {
+        const int32_t m = static_cast<int32_t>(l.local[k].size());
+        return m ? qpsk_demod_set_streams_state(g->shards[k].h, l.local[k].data(), m, part[k].data(),
+                                                static_cast<int64_t>(part[k].size()))
+                 : QPSK_OK;
+    });
 }
 
 int qpsk_demod_group_enable_link_stats(qpsk_demod_group *g, int32_t on) {

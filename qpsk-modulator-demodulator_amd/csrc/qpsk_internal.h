@@ -46,6 +46,7 @@ int check_call(const qpsk_demod *h, int S, CallArgs &c);
 int handle_streams(const qpsk_demod *h);
 int64_t handle_max_samples(const qpsk_demod *h);
 int handle_device(const qpsk_demod *h);
+int handle_taps(const qpsk_demod *h);   // of the matched filter
 // the host waits for every call queued on the handle, pipelined or stream-ordered
 int handle_sync(qpsk_demod *h);
 
@@ -58,6 +59,25 @@ namespace qpsk {
 // the pipelined path's front-stage stream (qpsk_rx.hip records "input consumed"
 // on it); nullptr before the first pipelined call
 hipStream_t pipe_front_stream(const qpsk_demod *h);
+
+// What the rows of selected streams (qpsk_stream_state.hip) need from a handle:
+// its shape and stream, the four per-stream arrays of a state blob (hist: the
+// current one of the ping-pong pair, good until the next call is issued), the
+// link sums (nullptr until first enabled) and the staging buffer it keeps for
+// them, which qpsk_demod_destroy frees.
+struct StreamState;
+struct LinkAcc;
+struct StreamRows {
+    const qpsk_demod_params *p;
+    int S, T;
+    hipStream_t stream;
+    StreamState *state;
+    float *carry, *hist, *fll_delay;
+    LinkAcc *link;
+    void **staging;
+    size_t *staging_bytes;
+};
+StreamRows handle_rows(qpsk_demod *h);
 }  // namespace qpsk
 
 #define QPSK_HIP_TRY(expr)                                                                    \

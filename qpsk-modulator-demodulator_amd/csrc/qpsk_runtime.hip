@@ -34,6 +34,7 @@
 //   bits    [S][words]              uint32  MSB-first packed bits
 //   syms    [S][syms_cap]           float2  rotated symbols (on request)
 //   link    [S]                     LinkAcc link statistics' running sums (once enabled)
+//   rows    blob of n streams + [n] int32   staging of selected streams' rows (qpsk_stream_state.hip)
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -180,6 +181,10 @@ struct qpsk_demod {
     bool link_on = false;
     LinkAcc *d_link = nullptr;
     qpsk_link_stats *d_link_rows = nullptr;
+    // rows of selected streams (qpsk_stream_state.hip): the packed sub-blob and
+    // the index list behind it, grown on demand
+    void *d_rows = nullptr;
+    size_t rows_bytes = 0;
     bool timing = false;
     // launch timestamps of the timed calls ([call][kKtPerCall] wall-clock ticks,
     // written by the kernels themselves: qpsk_kernels.h kt_start / kt_end)
@@ -238,6 +243,11 @@ hipStream_t pipe_front_stream(const qpsk_demod *h) { return h->s_front; }
 int handle_streams(const qpsk_demod *h) { return h->S; }
 int64_t handle_max_samples(const qpsk_demod *h) { return h->n_max; }
 int handle_device(const qpsk_demod *h) { return h->p.device; }
+int handle_taps(const qpsk_demod *h) { return h->T; }
+StreamRows handle_rows(qpsk_demod *h) {
+    return StreamRows{&h->p,      h->S,       h->T,      h->stream,  h->d_state, h->d_carry, h->d_hist[h->hist_cur],
+                      h->d_fll_delay, h->d_link, &h->d_rows, &h->rows_bytes};
+}
 }  // namespace qpsk
 
 namespace {
@@ -855,6 +865,7 @@ int qpsk_demod_destroy(qpsk_demod *h) {
     hipFree(h->d_xsyms);
     hipFree(h->d_link);
     hipFree(h->d_link_rows);
+    hipFree(h->d_rows);
     if (h->e_in) hipEventDestroy(h->e_in);
     if (h->e_fll) hipEventDestroy(h->e_fll);
     if (h->s_front) hipStreamDestroy(h->s_front);

@@ -1,7 +1,10 @@
 // qpsk_state_blob.cpp -- qpsk_state_blob_check: what a state blob must satisfy
-// before qpsk_demod_set_state copies it to the device.  Host-only (no HIP): a
+// before qpsk_demod_set_state copies it to the device; and the rows of
+// selected streams as a blob of their own (qpsk_stream_list_check,
+// qpsk_state_blob_select, qpsk_state_blob_merge).  Host-only (no HIP): a
 // stand-alone CPU program links this file, qpsk_error.cpp and qpsk_design.cpp
-// (tools/state_blob_check_main.cpp runs it under the sanitizers).
+// (tools/state_blob_check_main.cpp and tools/state_blob_rows_main.cpp run it
+// under the sanitizers).
 //
 // A blob is external input.  The kernels take a record's integers, and the
 // timing phase, as addresses without looking at them, so each such field is
@@ -14,6 +17,7 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <vector>
 
 #include "qpsk_demod.h"
 #include "qpsk_design.h"
@@ -107,7 +111,114 @@ int state_blob_check(int32_t S, int32_t T, double sps, const void *buf, int64_t 
     return QPSK_OK;
 }
 
+int stream_list_check(int32_t S, const int32_t *streams, int32_t n) {
+    if (!streams) return fail(QPSK_ERR_ARGUMENT_NULL, "stream list is null");
+    if (S <= 0 || n < 1 || n > S)
+        return fail(QPSK_ERR_ARGUMENT, "stream list: n = " + std::to_string(n) + " outside [1, " + std::to_string(S) +
+                                           "] (the streams of the batch)");
+    std::vector<int32_t> first(static_cast<size_t>(S), -1);   // position an index was first seen at
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t v = streams[i];
+        if (v < 0 || v >= S)
+            return fail(QPSK_ERR_ARGUMENT, "stream list position " + std::to_string(i) + ": index " + std::to_string(v) +
+                                               " outside [0, " + std::to_string(S) + ")");
+        if (first[v] >= 0)
+            return fail(QPSK_ERR_ARGUMENT, "stream list position " + std::to_string(i) + ": index " + std::to_string(v) +
+                                               " repeated (first at position " + std::to_string(first[v]) + ")");
+        first[v] = i;
+    }
+    return QPSK_OK;
+}
+
+namespace {
+
+// One section after the other: row src_row(i) of the section in `from` (a
+// blob of S_from streams) to row dst_row(i) of the section in `to`.
+template <typename SrcRow, typename DstRow>
+void copy_rows(int32_t T, const char *from, int64_t S_from, char *to, int64_t S_to, int32_t n, SrcRow src_row,
+               DstRow dst_row) {
+    int64_t words[kStateSections];
+    state_row_words(T, words);
+    from += sizeof(StateHeader);
+    to += sizeof(StateHeader);
+    for (int k = 0; k < kStateSections; ++k) {
+        const int64_t row = 8 * words[k];
+        for (int32_t i = 0; i < n; ++i) std::memcpy(to + dst_row(i) * row, from + src_row(i) * row, row);
+        from += S_from * row;
+        to += S_to * row;
+    }
+}
+
+}  // namespace
+
+void state_blob_gather_rows(int32_t S, int32_t T, const void *blob, const int32_t *streams, int32_t n, void *sub) {
+    const StateHeader hd = state_header(n, T);
+    std::memcpy(sub, &hd, sizeof(hd));
+    copy_rows(T, static_cast<const char *>(blob), S, static_cast<char *>(sub), n, n,
+              [&](int32_t i) { return static_cast<int64_t>(streams[i]); }, [](int32_t i) { return static_cast<int64_t>(i); });
+}
+
+void state_blob_scatter_rows(int32_t S, int32_t T, void *blob, const int32_t *streams, int32_t n, const void *sub) {
+    copy_rows(T, static_cast<const char *>(sub), n, static_cast<char *>(blob), S, n,
+              [](int32_t i) { return static_cast<int64_t>(i); }, [&](int32_t i) { return static_cast<int64_t>(streams[i]); });
+}
+
+namespace {
+
+// the tap count and the M&M samples per symbol of p, as qpsk_demod_design
+int shape_of(const qpsk_demod_params *p, const char *who, int32_t *T, double *sps) {
+    LoopDesign d;
+    std::string err;
+    if (design_loops(p->sample_rate, p->symbol_rate, p->rrc_alpha, p->rrc_span, p->symbol_sync_bandwidth,
+                     p->costas_loop_bandwidth, p->cfo_loop_bandwidth, &d, &err) != QPSK_OK)
+        return fail(QPSK_ERR_ARGUMENT, std::string(who) + ": " + err);
+    *T = static_cast<int32_t>(d.rrc_f32.size());
+    *sps = d.mm_sps;
+    return QPSK_OK;
+}
+
+}  // namespace
+
 }  // namespace qpsk
+
+extern "C" int qpsk_stream_list_check(int32_t n_streams, const int32_t *streams, int32_t n) {
+    return qpsk::stream_list_check(n_streams, streams, n);
+}
+
+extern "C" int qpsk_state_blob_select(const qpsk_demod_params *p, int32_t n_streams, const void *blob,
+                                      int64_t blob_bytes, const int32_t *streams, int32_t n, void *sub,
+                                      int64_t sub_bytes) {
+    using namespace qpsk;
+    if (!p || !blob || !streams || !sub) return fail(QPSK_ERR_ARGUMENT_NULL, "state blob select: null argument");
+    int rc;
+    int32_t T;
+    double sps;
+    if ((rc = stream_list_check(n_streams, streams, n)) || (rc = shape_of(p, "state blob select", &T, &sps)) ||
+        (rc = state_blob_check(n_streams, T, sps, blob, blob_bytes)))
+        return rc;
+    if (sub_bytes != state_blob_bytes(n, T))
+        return fail(QPSK_ERR_ARGUMENT, "state blob select: the sub-blob buffer holds " + std::to_string(sub_bytes) +
+                                           " bytes, " + std::to_string(n) + " streams take " +
+                                           std::to_string(state_blob_bytes(n, T)));
+    state_blob_gather_rows(n_streams, T, blob, streams, n, sub);
+    return QPSK_OK;
+}
+
+extern "C" int qpsk_state_blob_merge(const qpsk_demod_params *p, int32_t n_streams, void *blob, int64_t blob_bytes,
+                                     const int32_t *streams, int32_t n, const void *sub, int64_t sub_bytes) {
+    using namespace qpsk;
+    if (!p || !blob || !streams || !sub) return fail(QPSK_ERR_ARGUMENT_NULL, "state blob merge: null argument");
+    int rc;
+    int32_t T;
+    double sps;
+    // every check before the first byte moves: a rejected call changes nothing
+    if ((rc = stream_list_check(n_streams, streams, n)) || (rc = shape_of(p, "state blob merge", &T, &sps)) ||
+        (rc = state_blob_check(n, T, sps, sub, sub_bytes)) ||
+        (rc = state_blob_check(n_streams, T, sps, blob, blob_bytes)))
+        return rc;
+    state_blob_scatter_rows(n_streams, T, blob, streams, n, sub);
+    return QPSK_OK;
+}
 
 extern "C" int qpsk_state_blob_check(const qpsk_demod_params *p, int32_t n_streams, const void *buf,
                                      int64_t buf_bytes) {

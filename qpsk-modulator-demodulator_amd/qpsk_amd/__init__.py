@@ -317,6 +317,17 @@ def lib():
     L.qpsk_demod_link_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     L.qpsk_demod_group_enable_link_stats.argtypes = [C.c_void_p, C.c_int32]
     L.qpsk_demod_group_link_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    _i32p = C.POINTER(C.c_int32)
+    L.qpsk_stream_list_check.argtypes = [C.c_int32, _i32p, C.c_int32]
+    rows = [C.POINTER(DemodParams), C.c_int32, C.c_void_p, C.c_int64, _i32p, C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_state_blob_select.argtypes = rows
+    L.qpsk_state_blob_merge.argtypes = rows
+    for owner in ("qpsk_demod", "qpsk_demod_group"):
+        getattr(L, owner + "_reset_streams").argtypes = [C.c_void_p, _i32p, C.c_int32]
+        getattr(L, owner + "_streams_state_bytes").argtypes = [C.c_void_p, C.c_int32]
+        getattr(L, owner + "_streams_state_bytes").restype = C.c_int64
+        getattr(L, owner + "_get_streams_state").argtypes = [C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_int64]
+        getattr(L, owner + "_set_streams_state").argtypes = [C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_int64]
     _lib = real
     return real
 
@@ -351,6 +362,10 @@ EXPORTED_SYMBOLS = [
     "qpsk_state_blob_check",
     "qpsk_link_stats_size", "qpsk_demod_enable_link_stats", "qpsk_demod_link_stats",
     "qpsk_demod_group_enable_link_stats", "qpsk_demod_group_link_stats",
+    "qpsk_stream_list_check", "qpsk_state_blob_select", "qpsk_state_blob_merge",
+    "qpsk_demod_reset_streams", "qpsk_demod_streams_state_bytes", "qpsk_demod_get_streams_state",
+    "qpsk_demod_set_streams_state", "qpsk_demod_group_reset_streams", "qpsk_demod_group_streams_state_bytes",
+    "qpsk_demod_group_get_streams_state", "qpsk_demod_group_set_streams_state",
 ]
 
 _EXC = {
@@ -467,8 +482,88 @@ def state_blob_parts(blob: bytes, n_streams: int, taps: int):
             dl.reshape(S, 2 * STATE_FLL_TAPS, 2).copy())
 
 
-class BatchDemodulator:
+def _stream_list(streams):
+    """A stream list as (ctypes int32 array, n); indices are passed on as they
+    are, for the library to check."""
+    ids = [int(v) for v in streams]
+    return (C.c_int32 * max(len(ids), 1))(*ids), len(ids)
+
+
+def stream_list_check(n_streams: int, streams):
+    """qpsk_stream_list_check: 1 <= len(streams) <= n_streams, every index in
+    [0, n_streams), none twice (needs no device).  Raises ValueError naming
+    the position and the value."""
+    ids, n = _stream_list(streams)
+    _check(lib().qpsk_stream_list_check(int(n_streams), ids, n))
+
+
+def state_blob_select(p: DemodParams, n_streams: int, blob: bytes, streams) -> bytes:
+    """qpsk_state_blob_select: the rows `streams` of an n_streams blob, in
+    list order, as a blob of len(streams) streams (needs no device)."""
+    ids, n = _stream_list(streams)
+    taps = design(p)[0].size
+    src = C.create_string_buffer(bytes(blob), max(len(blob), 1))
+    sub = C.create_string_buffer(state_blob_bytes(max(n, 1), taps))
+    _check(lib().qpsk_state_blob_select(C.byref(p), int(n_streams), src, len(blob), ids, n, sub, len(sub)))
+    return sub.raw
+
+
+def state_blob_merge(p: DemodParams, n_streams: int, blob: bytes, streams, sub: bytes) -> bytes:
+    """qpsk_state_blob_merge: a copy of blob whose rows `streams` are the rows
+    of sub, a blob of len(streams) streams (needs no device)."""
+    ids, n = _stream_list(streams)
+    dst = C.create_string_buffer(bytes(blob), max(len(blob), 1))
+    src = C.create_string_buffer(bytes(sub), max(len(sub), 1))
+    _check(lib().qpsk_state_blob_merge(C.byref(p), int(n_streams), dst, len(blob), ids, n, src, len(sub)))
+    return dst.raw[:len(blob)]
+
+
+def state_blob_bytes(n_streams: int, taps: int) -> int:
+    """Bytes of a state blob of n_streams streams of a taps-tap matched filter."""
+    return STATE_HEADER_BYTES + int(n_streams) * (STREAM_STATE_DTYPE.itemsize + 8 * STATE_CARRY_MAX +
+                                                  8 * (int(taps) - 1) + 8 * 2 * STATE_FLL_TAPS)
+
+
+class _StreamRows:
+    """reset_streams / get_streams_state / set_streams_state over a handle or a
+    group: _rows_owner() gives the entry points' prefix and the C object."""
+
+    def reset_streams(self, streams):
+        """`new QPSKDeModulator(...)` on the listed rows: loops, filter history,
+        FLL and IQ-balancer state, differential decoder, sticky error and the
+        rows' link sums go back to construction.  Waits for every queued call.
+        An empty list does nothing."""
+        prefix, obj = self._rows_owner()
+        ids, n = _stream_list(streams)
+        _check(getattr(lib(), prefix + "_reset_streams")(obj, ids, n))
+
+    def get_streams_state(self, streams) -> bytes:
+        """The listed rows, in list order, as a state blob of len(streams)
+        streams (what state_blob_select cuts from get_state()).  Waits for
+        every queued call."""
+        prefix, obj = self._rows_owner()
+        ids, n = _stream_list(streams)
+        size = getattr(lib(), prefix + "_streams_state_bytes")(obj, n)
+        buf = C.create_string_buffer(max(size, 1))
+        _check(getattr(lib(), prefix + "_get_streams_state")(obj, ids, n, buf, size))
+        return buf.raw[:size]
+
+    def set_streams_state(self, streams, sub: bytes):
+        """Overwrite the listed rows with the rows of sub, a blob of
+        len(streams) streams.  A bad list or a sub-blob that fails
+        state_blob_check raises ValueError and changes nothing.  The link
+        sums stay as they are."""
+        prefix, obj = self._rows_owner()
+        ids, n = _stream_list(streams)
+        buf = C.create_string_buffer(bytes(sub), max(len(sub), 1))
+        _check(getattr(lib(), prefix + "_set_streams_state")(obj, ids, n, buf, len(sub)))
+
+
+class BatchDemodulator(_StreamRows):
     """A batch of S independent reference demodulators on one MI355X."""
+
+    def _rows_owner(self):
+        return "qpsk_demod", self._h
 
     def __init__(self, n_streams: int, p: DemodParams):
         self.S = int(n_streams)
@@ -788,11 +883,15 @@ def shard_streams(n_streams: int, n_parts: int, k: int):
     return f.value, c.value
 
 
-class DemodGroup:
+class DemodGroup(_StreamRows):
     """One batch of streams over several GPUs (qpsk_demod_group_*): shard k =
     contiguous streams on devices[k], one handle each, fanned out per call on
     worker threads and joined.  process() takes the same host rows as
-    BatchDemodulator.process over all n_streams and returns the same arrays."""
+    BatchDemodulator.process over all n_streams and returns the same arrays.
+    reset_streams / get_streams_state / set_streams_state take global ids."""
+
+    def _rows_owner(self):
+        return "qpsk_demod_group", self._g
 
     def __init__(self, n_streams: int, p: DemodParams, devices):
         self.S = int(n_streams)
