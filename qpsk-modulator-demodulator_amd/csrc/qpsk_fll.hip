@@ -43,11 +43,18 @@
 //   Main loop (blocks of 8 samples, 4 per iteration): the 32-sample window of
 //   mixed samples the partial sums read lives in registers, four 8-sample groups
 //   that rotate with the block position, and a block's outputs overwrite the
-//   oldest group in place (sample u of it is dead once step u starts).  The LDS
-//   ring serves only the first and the last blocks of a call.  The NCO's
+//   oldest group in place (sample u of it is dead once step u starts).  The NCO's
 //   sinf/cosf is the lane-split form of qpsk_sincosf.h: the stream's even lanes
 //   run glibc's sin polynomial, its odd lanes the cos polynomial, one DPP swap
 //   hands each the other's value.
+//
+//   Every other block in which all 8 streams of the wave have 8 samples (the
+//   call's first, those behind the main loop, all of a short call) is the same
+//   register-window block, with its window fetched from the LDS ring before it
+//   and its outputs put back after it.  The ring is also what the ragged rest
+//   (streams of different length, partly filled waves, the last < 8 samples)
+//   advances on sample by sample, what carries the window into and out of the
+//   main loop, and what the delay line is written back from.
 //
 // Every float op is the reference's op in the reference's order
 // (-ffp-contract=off), so the output equals the one-lane fll_kernel bit for bit.
@@ -131,18 +138,11 @@ __device__ __forceinline__ void sincosf_split(float y, const qpsk_sincosf_lane &
     cs = __uint_as_float(co);
 }
 
-// Band-edge products of complex tap (a, b) [packed A = {a, a}, B = {b, b}] with
-// sample x, in the layout the lane sum and the powers want:
+// Band-edge products of complex tap T = {a, b} with sample x, in the layout the
+// lane sum and the powers want:
 //   R = {upper re, lower re} = {a xr + b xi, a xr - b xi}
 //   I = {upper im, lower im} = {a xi - b xr, a xi + b xr}
-__device__ __forceinline__ void band_prod(f2 A, f2 B, f2 x, f2 &R, f2 &I) {
-    const f2 p = A * x;   // {a xr, a xi}
-    const f2 q = B * x;   // {b xr, b xi}
-    R = add_xy_neghi(p, q);
-    I = add_yx_neglo(p, q);
-}
-// the same with the tap as one register pair T = {a, b}: the broadcasts are
-// op_sel / op_sel_hi modifiers of the two v_pk_mul_f32 (half the tap VGPRs)
+// The tap's broadcasts are op_sel / op_sel_hi modifiers of the two v_pk_mul_f32.
 __device__ __forceinline__ void band_prod(f2 T, f2 x, f2 &R, f2 &I) {
     const f2 p = T.xx * x;   // {a xr, a xi}
     const f2 q = T.yy * x;   // {b xr, b xi}
@@ -214,15 +214,10 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
     }
     __syncthreads();
 
-    // taps of this lane: reversed index l + 8j, as {a, a} and {b, b} pairs
-    f2 TA[5], TB[5], TT[5];
+    // taps of this lane: reversed index l + 8j, as {a, b} pairs
+    f2 TT[5];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const float ta = L.taps[2 * (l + 8 * j)], tb = L.taps[2 * (l + 8 * j) + 1];
-        TA[j] = f2{ta, ta};
-        TB[j] = f2{tb, tb};
-        TT[j] = f2{ta, tb};
-    }
+    for (int j = 0; j < 5; ++j) TT[j] = f2{L.taps[2 * (l + 8 * j)], L.taps[2 * (l + 8 * j) + 1]};
 
     // pipeline state as after step -1: lane l (< 7) holds the lane sum over
     // lanes 0..l for output 6 - l (reference order: +0, then lanes in order)
@@ -231,9 +226,9 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
         for (int k = 0; k <= l; ++k) {
             f2 ar = f2{0.f, 0.f}, ai = f2{0.f, 0.f};
             for (int j = 0; j < 5; ++j) {
-                const float ta = L.taps[2 * (k + 8 * j)], tb = L.taps[2 * (k + 8 * j) + 1];
+                const f2 T = f2{L.taps[2 * (k + 8 * j)], L.taps[2 * (k + 8 * j) + 1]};
                 f2 R, I;
-                band_prod(f2{ta, ta}, f2{tb, tb}, ring[(-33 + 8 * j + k - l) & (kRingLen - 1)], R, I);
+                band_prod(T, ring[(-33 + 8 * j + k - l) & (kRingLen - 1)], R, I);
                 ar = ar + R;
                 ai = ai + I;
             }
@@ -241,32 +236,28 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
             SI = SI + ai;
         }
     }
-    // partial accumulators of the step at time t (inputs x[t-32], x[t-24],
-    // x[t-16], x[t-8]); fetch(k) = x[(t - off) - 32 + k], off <= 8: from the ring
-    // (rb = ring + ((t - off - 32) & 63), static offsets, the mirror covers the
-    // wrap) or from a block's register window
+    // partial accumulators of the step at time t = t0 + off, off <= 8 (inputs
+    // x[t-32], x[t-24], x[t-16], x[t-8]) from the ring: rb = ring + ((t0 - 32) &
+    // 63), static offsets, the mirror covers the wrap
     f2 PR, PI;
-    auto partial = [&](auto fetch, int off) __attribute__((always_inline)) {
+    auto partial = [&](int64_t t0, int off) __attribute__((always_inline)) {
+        const lds_f2 *rb = ring + ((t0 - 32) & (kRingLen - 1));
         // the reference starts each lane accumulator at +0 (Vector<float>.Zero);
         // 0 + v differs from v only in the sign of a zero, and the filter
         // outputs are only ever squared (the band powers), so the start is dropped
         f2 ar, ai;
-        band_prod(TA[0], TB[0], fetch(off), ar, ai);
+        band_prod(TT[0], rb[off], ar, ai);
 #pragma unroll
         for (int j = 1; j < 4; ++j) {
             f2 R, I;
-            band_prod(TA[j], TB[j], fetch(off + 8 * j), R, I);
+            band_prod(TT[j], rb[off + 8 * j], R, I);
             ar = ar + R;
             ai = ai + I;
         }
         PR = ar;
         PI = ai;
     };
-    auto ring_at = [&](int64_t t0) __attribute__((always_inline)) {
-        const lds_f2 *rb = ring + ((t0 - 32) & (kRingLen - 1));
-        return [rb](int k) -> f2 { return rb[k]; };
-    };
-    partial(ring_at(0), 0);
+    partial(0, 0);
 
     const float two_pi = 2.0f * 3.14159274101257324219f;
     // the partial sums' sign vectors, pinned (as SGPR pairs the compiler
@@ -283,46 +274,27 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
     const qpsk_sincosf_lane K = qpsk_sincosf_lane_init((l & 1) == 0);
     const float zy = (l & 1) == 0 ? 0.0f : __builtin_nanf("");
 
-    // one sample (Band-Edge Filter.cs:102-129) at t = t0 + u, t0 a multiple of 8.
-    // FIRST: the call's first sample (the stored phase may be anything set_state
-    // put there).  EXACT: the IEEERemainder wrap (:185-189) behind a vote and the
-    // frequency clamp (:191-195).  Without EXACT the step tracks max |phase| and
-    // max |freq| instead, and the block is redone exactly if either left its
+    // (inI*c - inQ*s, inI*s + inQ*c) from p = in*c = {inI*c, inQ*c} and
+    // q = in*s = {inI*s, inQ*s}: {p.x - q.y, p.y + q.x}.  The broadcasts are
+    // op_sel_hi modifiers of one v_pk_mul_f32 each (plain vector code: no
+    // inline asm, whose hazards the compiler pads with s_nop)
+    auto mix = [](f2 in, float sn, float cs) __attribute__((always_inline)) -> f2 {
+        return add_swap_neglo(in * f2{cs, cs}, in * f2{sn, sn});
+    };
+    // One sample's update behind the NCO mix (Band-Edge Filter.cs:112-129): xm is
+    // the mixed sample, pr / pi its step's partial sums.  EXACT: the
+    // IEEERemainder wrap (:185-189) behind a vote and the frequency clamp
+    // (:191-195).  Without EXACT the update tracks max |phase| and max |freq|
+    // in amax / fmx instead, and the block is redone exactly if either left its
     // range (the phase every ~2pi/|freq| samples; the clamp never on a
     // unit-amplitude signal, at most samples from amplitude ~1e3 on: DESIGN
     // "Which inputs live in the redo"), so a block is branch-free straight-line
     // code.
-    // REG: a uniform block's step -- the partial sums read the block's register
-    // window X (x[t0-32 .. t0-1]; x[t0] is this block's first output, xmv[0])
-    // and the outputs stay in xmv until the block writes them to the ring at its
-    // end (16-B LDS accesses instead of a read per tap and a write pair per
-    // sample); otherwise the ring is read and written per sample
-    auto step = [&](f2 in, int64_t t0, int u, auto first, auto exact, float &amax, float &fmx,
-                    auto reg, const f2 *X, f2 *xmv) __attribute__((always_inline)) {
-        // MathF.Cos / MathF.Sin (Band-Edge Filter.cs:108-109) = glibc cosf / sinf
-        float sn, cs;
-        if constexpr (decltype(first)::value) {
-            qpsk_sincosf_glibc(phase, &sn, &cs);
-        } else {
-            // a kept result has |phase| <= 2pi (or NaN): the branch-free form
-            qpsk_sincosf_glibc_fast_k(phase, &sn, &cs, sign_v);
-        }
-        // (inI*c - inQ*s, inI*s + inQ*c) from p = in*c = {inI*c, inQ*c} and
-        // q = in*s = {inI*s, inQ*s}: {p.x - q.y, p.y + q.x}.  The broadcasts are
-        // op_sel_hi modifiers of one v_pk_mul_f32 each (plain vector code: no
-        // inline asm, whose hazards the compiler pads with s_nop)
-        const f2 xm = add_swap_neglo(in * f2{cs, cs}, in * f2{sn, sn});
-        if constexpr (decltype(reg)::value) {
-            xmv[u] = xm;
-        } else {
-            lds_f2 *wb = ring + (t0 & (kRingLen - 1));
-            wb[u] = xm;
-            wb[u + kRingLen] = xm;
-        }
-        y[t0 + u] = xm;
+    float amax = 0.f, fmx = 0.f;
+    auto update = [&](f2 xm, f2 pr, f2 pi, auto exact) __attribute__((always_inline)) {
         f2 R4, I4;
-        band_prod(TA[4], TB[4], xm, R4, I4);
-        const f2 ar = PR + R4, ai = PI + I4;
+        band_prod(TT[4], xm, R4, I4);
+        const f2 ar = pr + R4, ai = pi + I4;
         SR = f2{shr2(SR.x) + ar.x, shr2(SR.y) + ar.y};
         SI = f2{shr2(SI.x) + ai.x, shr2(SI.y) + ai.y};
         // lane 7 holds the filter outputs of sample t: {pow upper, pow lower}
@@ -338,49 +310,26 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
             amax = fmaxf(amax, fabsf(phase));   // NaN never wraps or clamps: ignored
             fmx = fmaxf(fmx, fabsf(freq));
         }
-        if constexpr (decltype(reg)::value)
-            partial([&](int k) -> f2 { return k == 32 ? xmv[0] : X[k]; }, u + 1);
-        else
-            partial(ring_at(t0), u + 1);
     };
-    // 8 samples of every stream of the wave, no masks
-    typedef __attribute__((address_space(3))) f4 lds_f4;
-    auto block = [&](const f2 *in, int64_t t0, auto first) __attribute__((always_inline)) {
-        const float ph0 = phase, fr0 = freq;
-        const f2 sr0 = SR, si0 = SI, pr0 = PR, pi0 = PI;
-        float amax = 0.f, fmx = 0.f;
-        // the window x[t0-32 .. t0-1]: (t0 - 32) & 63 is a multiple of 8 samples,
-        // so 16 aligned 16-B reads (the mirror keeps it contiguous)
-        f2 X[32], xmv[8];
-        const lds_f4 *wr = reinterpret_cast<const lds_f4 *>(ring + ((t0 - 32) & (kRingLen - 1)));
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const f4 v = wr[k];
-            X[2 * k] = f2{v.x, v.y};
-            X[2 * k + 1] = f2{v.z, v.w};
+    // The ring step, for everything ragged: one exact sample at t = t0 + u (t0 a
+    // multiple of 8), the ring read per tap and written per sample.  FIRST: the
+    // call's first sample (the stored phase may be anything set_state put there).
+    auto step = [&](f2 in, int64_t t0, int u, auto first) __attribute__((always_inline)) {
+        // MathF.Cos / MathF.Sin (Band-Edge Filter.cs:108-109) = glibc cosf / sinf
+        float sn, cs;
+        if constexpr (decltype(first)::value) {
+            qpsk_sincosf_glibc(phase, &sn, &cs);
+        } else {
+            // a kept result has |phase| <= 2pi (or NaN): the branch-free form
+            qpsk_sincosf_glibc_fast_k(phase, &sn, &cs, sign_v);
         }
-        step(in[0], t0, 0, first, std::false_type{}, amax, fmx, std::true_type{}, X, xmv);
-#pragma unroll
-        for (int u = 1; u < 8; ++u)
-            step(in[u], t0, u, std::false_type{}, std::false_type{}, amax, fmx, std::true_type{}, X, xmv);
-        if (__builtin_expect(__ballot((amax > two_pi) | (fmx > fmax_)) != 0, 0)) {
-            // some stream's phase needed a wrap or its frequency a clamp: redo
-            // from the block start (its outputs are rewritten)
-            phase = ph0; freq = fr0; SR = sr0; SI = si0; PR = pr0; PI = pi0;
-            step(in[0], t0, 0, first, std::true_type{}, amax, fmx, std::true_type{}, X, xmv);
-#pragma unroll
-            for (int u = 1; u < 8; ++u)
-                step(in[u], t0, u, std::false_type{}, std::true_type{}, amax, fmx, std::true_type{}, X, xmv);
-        }
-        // the block's outputs into the ring and its mirror: x[t0 .. t0+7] at
-        // t0 & 63, a multiple of 8 samples (64-B aligned)
-        lds_f4 *ww = reinterpret_cast<lds_f4 *>(ring + (t0 & (kRingLen - 1)));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const f4 v = f4{xmv[2 * k].x, xmv[2 * k].y, xmv[2 * k + 1].x, xmv[2 * k + 1].y};
-            ww[k] = v;
-            ww[k + kRingLen / 2] = v;
-        }
+        const f2 xm = mix(in, sn, cs);
+        lds_f2 *wb = ring + (t0 & (kRingLen - 1));
+        wb[u] = xm;
+        wb[u + kRingLen] = xm;
+        y[t0 + u] = xm;
+        update(xm, PR, PI, std::true_type{});
+        partial(t0, u + 1);
     };
 
     // wave-uniform block counts (8 streams per wave); rows past the batch count
@@ -401,18 +350,26 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
         for (int u = 0; u < 8; ++u) buf[u] = x[t0 + u];
     };
 
-    // ---- register-window blocks ------------------------------------------
-    // G[(p + i) & 3] holds x[t0 - 32 + 8i .. t0 - 25 + 8i] at block position p;
-    // step u overwrites G[p][u] with the block's output x[t0 + u].  The partial
-    // sums of steps 1..7 depend on the old window only (their newest input is
-    // x[t0 + u - 7]), so they are kept for a redo; step 8's (the next block's
-    // step 0) reads x[t0] = G[p][0], the block's first output.
+    // ---- the register-window block: 8 samples of every stream of the wave, no
+    // masks.  G[(p + i) & 3] holds x[t0 - 32 + 8i .. t0 - 25 + 8i] at block
+    // position p; step u overwrites G[p][u] with the block's output x[t0 + u].
+    // The partial sums of steps 1..7 depend on the old window only (their newest
+    // input is x[t0 + u - 7]), so they are kept for a redo; step 8's (the next
+    // block's step 0) reads x[t0] = G[p][0], the block's first output.
+    // FIRST: the block is the call's first, and its first sample takes the
+    // full-range sinf/cosf in both passes (the stored phase may be anything
+    // set_state put there).  As in every block, a phase the fast pass takes
+    // past 2pi goes on into sincosf_split (here |phase| may be >= 120); amax
+    // has seen it, and the redo discards the pass.
     f2 G[4][8];
     // lanes whose block-start phase is -0 (sincosf_split<false> excludes it),
     // as a ballot mask: the per-block redo test below is then two compares
     // into SGPR masks, scalar ors and one branch on SCC
     uint64_t need_exact = 0;
-    auto rblock = [&](auto pc, const f2 *in, int64_t t0) __attribute__((always_inline)) {
+    auto minus0_phase = [&]() __attribute__((always_inline)) {
+        return __builtin_amdgcn_ballot_w64(__float_as_uint(phase) == 0x80000000u);
+    };
+    auto rblock = [&](auto pc, auto first, const f2 *in) __attribute__((always_inline)) {
         constexpr int p = decltype(pc)::value;
         auto X = [&](int k) __attribute__((always_inline)) -> f2 { return G[(p + (k >> 3)) & 3][k & 7]; };
         const float ph0 = phase, fr0 = freq;
@@ -433,33 +390,21 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
             QR[u + 1] = ar;
             QI[u + 1] = ai;
         };
-        float amax = 0.f, fmx = 0.f;
-        auto core = [&](f2 inu, int u, auto exact) __attribute__((always_inline)) {
+        amax = 0.f;
+        fmx = 0.f;
+        auto core = [&](int u, auto exact) __attribute__((always_inline)) {
             float sn, cs;
-            sincosf_split<decltype(exact)::value>(phase, K, sign_v, zy, sn, cs);
-            const f2 xm = add_swap_neglo(inu * f2{cs, cs}, inu * f2{sn, sn});
+            if (decltype(first)::value && u == 0)
+                qpsk_sincosf_glibc(phase, &sn, &cs);
+            else
+                sincosf_split<decltype(exact)::value>(phase, K, sign_v, zy, sn, cs);
+            const f2 xm = mix(in[u], sn, cs);
             G[p][u] = xm;
-            f2 R4, I4;
-            band_prod(TT[4], xm, R4, I4);
-            const f2 ar = QR[u] + R4, ai = QI[u] + I4;
-            SR = f2{shr2(SR.x) + ar.x, shr2(SR.y) + ar.y};
-            SI = f2{shr2(SI.x) + ai.x, shr2(SI.y) + ai.y};
-            const f2 pw = SR * SR + SI * SI;
-            const float err = bcast7(pw.y - pw.x, odd);
-            freq = freq + beta * err;
-            phase = phase + freq;   // alpha == 0 (file comment)
-            if constexpr (decltype(exact)::value) {
-                if (__builtin_expect(__ballot(fabsf(phase) > two_pi) != 0, 0))
-                    if (fabsf(phase) > two_pi) phase = remainderf(phase, two_pi);
-                freq = freq > fmax_ ? fmax_ : (freq < fmin_ ? fmin_ : freq);
-            } else {
-                amax = fmaxf(amax, fabsf(phase));   // NaN never wraps or clamps: ignored
-                fmx = fmaxf(fmx, fabsf(freq));
-            }
+            update(xm, QR[u], QI[u], exact);
         };
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            core(in[u], u, std::false_type{});
+            core(u, std::false_type{});
             part(u);
         }
         const uint64_t redo = __builtin_amdgcn_ballot_w64(amax > two_pi) | __builtin_amdgcn_ballot_w64(fmx > fmax_);
@@ -467,11 +412,11 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
             // a wrap, a clamp or a -0 phase: redo the block exactly from its start
             phase = ph0; freq = fr0; SR = sr0; SI = si0;
 #pragma unroll
-            for (int u = 0; u < 8; ++u) core(in[u], u, std::true_type{});
+            for (int u = 0; u < 8; ++u) core(u, std::true_type{});
             part(7);
             // IEEERemainder can return -0 (an exact multiple of 2pi); a fast
             // block never creates -0 (x + y == -0 needs x == -0)
-            need_exact = __builtin_amdgcn_ballot_w64(__float_as_uint(phase) == 0x80000000u);
+            need_exact = minus0_phase();
         }
         PR = QR[8];
         PI = QI[8];
@@ -487,15 +432,11 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
         for (int u = 0; u < 8; ++u) y[t0 + u] = G[p][u];
     };
 
-    int64_t t0 = 0;
-    if (nmin >= 56) {
-        {   // the call's first block (the full sinf/cosf on its first sample) from the ring
-            f2 cur[8];
-            load8(cur, 0);
-            block(cur, 0, std::true_type{});
-        }
-        t0 = 8;
-        // window x[t0-32 .. t0-1] from the ring: 16 aligned 16-B reads
+    // G <- the window x[t0-32 .. t0-1] from the ring, for a block at p = 0:
+    // (t0 - 32) & 63 is a multiple of 8 samples, so 16 aligned 16-B reads (the
+    // mirror keeps it contiguous)
+    typedef __attribute__((address_space(3))) f4 lds_f4;
+    auto window_from_ring = [&](int64_t t0) __attribute__((always_inline)) {
         const lds_f4 *wr = reinterpret_cast<const lds_f4 *>(ring + ((t0 - 32) & (kRingLen - 1)));
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
@@ -503,7 +444,45 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
             G[k >> 2][(2 * k) & 7] = f2{v.x, v.y};
             G[k >> 2][(2 * k + 1) & 7] = f2{v.z, v.w};
         }
-        need_exact = __builtin_amdgcn_ballot_w64(__float_as_uint(phase) == 0x80000000u);
+    };
+    // group G[p] = x[t .. t+7] into the ring and its mirror at t & 63, a
+    // multiple of 8 samples (64-B aligned)
+    auto group_to_ring = [&](auto pc, int64_t t) __attribute__((always_inline)) {
+        constexpr int p = decltype(pc)::value;
+        lds_f4 *ww = reinterpret_cast<lds_f4 *>(ring + (t & (kRingLen - 1)));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const f4 v = f4{G[p][2 * k].x, G[p][2 * k].y, G[p][2 * k + 1].x, G[p][2 * k + 1].y};
+            ww[k] = v;
+            ww[k + kRingLen / 2] = v;
+        }
+    };
+    // a block outside the main loop: ring -> window, the block, its outputs to
+    // y and back into the ring.  need_exact comes from the phase in front of it:
+    // ahead of a call's first block nothing has kept the mask (a -0 may be
+    // stored, or left by IEEERemainder in the call before, ragged steps included)
+    constexpr std::integral_constant<int, 0> p0{};
+    auto ring_block = [&](auto first, const f2 *in, int64_t t0) __attribute__((always_inline)) {
+        window_from_ring(t0);
+        need_exact = minus0_phase();
+        rblock(p0, first, in);
+        store8(p0, t0);
+        group_to_ring(p0, t0);
+    };
+
+    int64_t t0 = 0;
+    if (nmin >= 8) {   // the call's first block: the full sinf/cosf on its first sample
+        f2 cur[8];
+        load8(cur, 0);
+        ring_block(std::true_type{}, cur, 0);
+        t0 = 8;
+    }
+    if (nmin >= 56) {
+        // the first block is behind us; as a constant, t0 keeps the loop's
+        // address arithmetic in scalar registers
+        t0 = 8;
+        window_from_ring(t0);
+        need_exact = minus0_phase();
         f2 A[8], B[8];
         load8(A, t0);
         load8(B, t0 + 8);
@@ -519,52 +498,41 @@ void fll_sys_kernel(FllArgs a, FllParams P) {
 #endif
         __builtin_amdgcn_s_waitcnt(0xF70);
         do {
-            rblock(std::integral_constant<int, 0>{}, A, t0);
+            rblock(std::integral_constant<int, 0>{}, std::false_type{}, A);
             load8(A, t0 + 16);
             store8(std::integral_constant<int, 0>{}, t0);
-            rblock(std::integral_constant<int, 1>{}, B, t0 + 8);
+            rblock(std::integral_constant<int, 1>{}, std::false_type{}, B);
             load8(B, t0 + 24);
             store8(std::integral_constant<int, 1>{}, t0 + 8);
-            rblock(std::integral_constant<int, 2>{}, A, t0 + 16);
+            rblock(std::integral_constant<int, 2>{}, std::false_type{}, A);
             load8(A, t0 + 32);
             store8(std::integral_constant<int, 2>{}, t0 + 16);
-            rblock(std::integral_constant<int, 3>{}, B, t0 + 24);
+            rblock(std::integral_constant<int, 3>{}, std::false_type{}, B);
             load8(B, t0 + 40);
             store8(std::integral_constant<int, 3>{}, t0 + 24);
             t0 += 32;
         } while (t0 + 48 <= nmin);
         // the window back into the ring (and its mirror) for the blocks that
-        // follow: group i at (t0 - 32 + 8i) & 63, a multiple of 8 samples
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            lds_f4 *ww = reinterpret_cast<lds_f4 *>(ring + ((t0 - 32 + 8 * i) & (kRingLen - 1)));
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f4 v = f4{G[i][2 * k].x, G[i][2 * k].y, G[i][2 * k + 1].x, G[i][2 * k + 1].y};
-                ww[k] = v;
-                ww[k + kRingLen / 2] = v;
-            }
-        }
+        // follow and the delay line
+        group_to_ring(std::integral_constant<int, 0>{}, t0 - 32);
+        group_to_ring(std::integral_constant<int, 1>{}, t0 - 24);
+        group_to_ring(std::integral_constant<int, 2>{}, t0 - 16);
+        group_to_ring(std::integral_constant<int, 3>{}, t0 - 8);
     }
-    // the rest (ragged streams, short calls, partly filled waves), block by block
+    // the rest (short calls, what is left behind the main loop, ragged streams,
+    // partly filled waves), block by block
     for (; t0 < nmax; t0 += 8) {
         f2 cur[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) cur[u] = t0 + u < n ? x[t0 + u] : f2{0.f, 0.f};
         if (t0 + 8 <= nmin) {
-            if (t0 == 0) block(cur, t0, std::true_type{});
-            else block(cur, t0, std::false_type{});
+            ring_block(std::false_type{}, cur, t0);
         } else {
-            float amax = 0.f, fmx = 0.f;
 #pragma unroll
             for (int u = 0; u < 8; ++u)
                 if (t0 + u < n) {
-                    if (t0 + u == 0)
-                        step(cur[u], t0, u, std::true_type{}, std::true_type{}, amax, fmx, std::false_type{},
-                             nullptr, nullptr);
-                    else
-                        step(cur[u], t0, u, std::false_type{}, std::true_type{}, amax, fmx, std::false_type{},
-                             nullptr, nullptr);
+                    if (t0 + u == 0) step(cur[u], t0, u, std::true_type{});
+                    else step(cur[u], t0, u, std::false_type{});
                 }
         }
     }

@@ -39,6 +39,7 @@ kernels use as addresses (qpsk_state_blob_check: carry_n, fll_pos, tofs, the
 flags, base, mu), never a float that is data -- so every listed phase and
 frequency, NaN and Inf included, is run.
 """
+import copy
 import functools
 
 import numpy as np
@@ -330,6 +331,97 @@ def test_amplitude_ladder_through_wrap_and_clamp(Q, sps, span, lanes):
     chain = oracle_run(c.rows, calls, K.FS // sps, span, enable_fll=True, cfo_loop_bw=BW, lanes=lanes)
     b = Q.BatchDemodulator(S, Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=n, enable_fll=True,
                                        cfo_loop_bandwidth=BW, vector_lanes=lanes))
+    drive(Q, b, c, calls, lambda x, lens: b.process(x, lengths=lens, want_syms=True), chain=chain)
+    assert b.status() == 0
+    b.close()
+
+
+# ---------------------------------------------------------------------------
+# A1b. uniform calls across the block paths
+# ---------------------------------------------------------------------------
+# The systolic kernel runs one register-window block wherever all 8 streams of
+# a wave have 8 samples: as a call's first block, in its main loop (nmin >= 56,
+# 32 samples an iteration while t0 + 48 <= nmin) and behind it.  The ladder's
+# ragged lengths reach the blocks outside the main loop only in waves where
+# nearly every block is redone, so here every call has one length for all
+# streams, and a quiet and a mixed wave stand next to the loud one.
+#   wave 0: ORDER's first wave, every block redone
+#   wave 1: quiet rows, never redone
+#   wave 2: mixed, the amplitude-64 rows 2 and 3 wrap now and then
+#   wave 3: partly filled, the ring step throughout
+EDGE_ORDER = ORDER[:8] + [0, 1, 9, 0, 1, 9, 0, 1] + [1, 2, 9, 0, 1, 9, 0, 3] + [5, 7]
+# the smallest lengths that cross each edge: 56 is the first that enters the
+# main loop, 88 and 120 its second and third iteration, and the +-1 neighbours
+# put 0 or 1 ragged samples and 2 or 5 uniform blocks behind it
+EDGE_LENS = [8, 16, 55, 56, 57, 87, 88, 89, 120, 121, 7]
+MIXED_WAVE = 2
+
+
+def block_position(n, t0):
+    """Where the kernel runs the full block at t0 of a uniform call of n samples."""
+    if t0 == 0:
+        return "first"
+    end = 8
+    if n >= 56:
+        while True:
+            end += 32
+            if end + 48 > n:
+                break
+    return "loop" if t0 < end else "tail"
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(sps, span):
+    """(case, calls, counts, mixed): the ladder's oracle rows in EDGE_ORDER, the
+    uniform calls, and the full blocks of the short calls in the three full
+    waves counted as counts[position] = [fast, redone] (redone: a stream of the
+    wave wraps or clamps in the block); mixed = that of wave 2's "loop" blocks.
+    The preconditions are asserted here, from the oracle alone."""
+    c0 = ladder_case(sps, span, 8)
+    at = [ORDER.index(r) for r in EDGE_ORDER]
+    c = copy.copy(c0)
+    c.rows = c.feed = c0.rows[at]
+    for name in ("fll_out", "states", "true_wrap", "true_clamp", "mf", "events"):
+        setattr(c, name, [getattr(c0, name)[p] for p in at])
+    S, n = c.rows.shape[0], c.rows.shape[1] // 2
+    assert n - sum(EDGE_LENS) >= 200
+    calls = [[k] * S for k in EDGE_LENS + [n - sum(EDGE_LENS)]]
+    counts = {pos: [0, 0] for pos in ("first", "loop", "tail")}
+    mixed = [0, 0]
+    start = 0
+    for k in EDGE_LENS:
+        for w in range(3):
+            for t0 in range(0, k - 7, 8):
+                a = start + t0
+                redone = any(c.true_wrap[s][a: a + 8].any() or c.true_clamp[s][a: a + 8].any()
+                             for s in range(8 * w, 8 * w + 8))
+                pos = block_position(k, t0)
+                counts[pos][redone] += 1
+                if w == MIXED_WAVE and pos == "loop":
+                    mixed[redone] += 1
+        start += k
+    for pos, (fast, redone) in counts.items():
+        assert fast >= 10 and redone >= 10, (pos, counts)
+    assert mixed[0] >= 1 and mixed[1] >= 1, mixed
+    return c, calls, counts, mixed
+
+
+@pytest.mark.parametrize("sps,span", CONFIGS)
+def test_uniform_calls_reach_every_block_path_in_the_oracle(sps, span):
+    """The oracle's [fast, redone] counts: sps 8 first [19, 11], loop [98, 58],
+    tail [46, 23], mixed wave's loop [46, 6]; sps 4 first [15, 15], loop
+    [60, 96], tail [33, 36], mixed wave's loop [8, 44]."""
+    edge_case(sps, span)
+
+
+@gpu
+@pytest.mark.parametrize("sps,span", CONFIGS)
+def test_uniform_calls_across_the_block_paths(Q, sps, span):
+    c, calls, _, _ = edge_case(sps, span)
+    S, n = c.rows.shape[0], c.rows.shape[1] // 2
+    chain = oracle_run(c.rows, calls, K.FS // sps, span, enable_fll=True, cfo_loop_bw=BW, lanes=8)
+    b = Q.BatchDemodulator(S, Q.params(K.FS, K.FS // sps, K.ALPHA, span, max_samples_per_call=n, enable_fll=True,
+                                       cfo_loop_bandwidth=BW, vector_lanes=8))
     drive(Q, b, c, calls, lambda x, lens: b.process(x, lengths=lens, want_syms=True), chain=chain)
     assert b.status() == 0
     b.close()
