@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "qpsk_demod.h"
+#include "qpsk_device.h"
 #include "qpsk_internal.h"
 
 namespace {
@@ -450,27 +451,19 @@ using qpsk::fail;
 struct qpsk_framer_dev {
     int32_t n_streams = 0;
     int32_t device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    FrState *st = nullptr;
-    uint8_t *carry = nullptr;
+    qpsk::Stream stream;             // in front of the buffers, which go first
+    qpsk::DevBuf<FrState> st;
+    qpsk::DevBuf<uint8_t> carry;
     int64_t carry_stride = 0;
-    uint8_t *scratch = nullptr;
+    qpsk::DevBuf<uint8_t> scratch;
     int64_t scr_stride = 0;
-    uint8_t *ring = nullptr;
+    qpsk::DevBuf<uint8_t> ring;
     int64_t ring_cap = kRefRing;
-    uint8_t *markers = nullptr;      // start bytes then end bytes
-    int64_t markers_cap = 0;
+    qpsk::DevBuf<uint8_t> markers;   // start bytes then end bytes
     int32_t ns = 0, ne = 0;
 
     ~qpsk_framer_dev() {
         if (stream) hipStreamSynchronize(stream);
-        hipFree(st);
-        hipFree(carry);
-        hipFree(scratch);
-        hipFree(ring);
-        hipFree(markers);
-        if (own_stream && stream) hipStreamDestroy(stream);
     }
 };
 
@@ -483,25 +476,19 @@ int load_markers(qpsk_framer_dev *f, const uint8_t *start, int32_t ns, const uin
     if (ne <= 0) return fail(QPSK_ERR_ARGUMENT, "endMarker cannot be empty.");     // :175
     QPSK_HIP_TRY(hipSetDevice(f->device));
     if (f->stream) QPSK_HIP_TRY(hipStreamSynchronize(f->stream));
-    if (static_cast<int64_t>(ns) + ne > f->markers_cap) {
-        hipFree(f->markers);
-        f->markers = nullptr;
-        f->markers_cap = static_cast<int64_t>(ns) + ne;
-        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&f->markers), f->markers_cap));
-    }
+    QPSK_HIP_TRY(f->markers.grow(static_cast<size_t>(ns) + ne));
     std::vector<uint8_t> m(start, start + ns);
     m.insert(m.end(), end, end + ne);
     QPSK_HIP_TRY(hipMemcpy(f->markers, m.data(), m.size(), hipMemcpyHostToDevice));
     const int64_t need = ((static_cast<int64_t>(ns) + 1 + 15) / 16) * 16;
     if (need > f->carry_stride) {
-        uint8_t *c = nullptr;
-        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c), need * f->n_streams));
+        qpsk::DevBuf<uint8_t> c;   // the old rows go with it, once theirs are in the new
+        QPSK_HIP_TRY(c.alloc(need * f->n_streams));
         QPSK_HIP_TRY(hipMemset(c, 0, need * f->n_streams));
         if (f->carry)
             QPSK_HIP_TRY(hipMemcpy2D(c, need, f->carry, f->carry_stride, f->carry_stride, f->n_streams,
                                      hipMemcpyDeviceToDevice));
-        hipFree(f->carry);
-        f->carry = c;
+        f->carry.swap(c);
         f->carry_stride = need;
     }
     f->ns = ns;
@@ -527,12 +514,9 @@ int qpsk_framer_dev_create(int32_t n_streams, const uint8_t *start_marker, int32
         delete f;
         return rc;
     }
-    hipError_t e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) {
-        f->own_stream = true;
-        e = hipMalloc(reinterpret_cast<void **>(&f->ring), f->ring_cap * n_streams);
-    }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&f->st), sizeof(FrState) * n_streams);
+    hipError_t e = f->stream.create(hipStreamNonBlocking);
+    if (e == hipSuccess) e = f->ring.alloc(f->ring_cap * n_streams);
+    if (e == hipSuccess) e = f->st.alloc(n_streams);
     if (e == hipSuccess) {
         std::vector<FrState> init(n_streams, FrState{0, -1, 0, 0, 0, 0});
         e = hipMemcpy(f->st, init.data(), sizeof(FrState) * n_streams, hipMemcpyHostToDevice);
@@ -554,14 +538,7 @@ int qpsk_framer_dev_set_stream(qpsk_framer_dev *f, void *hip_stream) {
     if (!f) return fail(QPSK_ERR_ARGUMENT_NULL, "null framer");
     QPSK_HIP_TRY(hipSetDevice(f->device));
     QPSK_HIP_TRY(hipStreamSynchronize(f->stream));
-    if (hip_stream) {
-        if (f->own_stream) hipStreamDestroy(f->stream);
-        f->stream = static_cast<hipStream_t>(hip_stream);
-        f->own_stream = false;
-    } else if (!f->own_stream) {
-        QPSK_HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
-        f->own_stream = true;
-    }
+    QPSK_HIP_TRY(f->stream.rebind(hip_stream));
     return QPSK_OK;
 }
 
@@ -581,10 +558,8 @@ int qpsk_framer_dev_push(qpsk_framer_dev *f, const uint8_t *bits, int64_t bits_s
     const int64_t need = ((f->carry_stride + bits_stride_bytes + 8 + 15) / 16) * 16;
     if (need > f->scr_stride) {
         QPSK_HIP_TRY(hipStreamSynchronize(f->stream));
-        hipFree(f->scratch);
-        f->scratch = nullptr;
         f->scr_stride = 0;
-        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&f->scratch), need * f->n_streams));
+        QPSK_HIP_TRY(f->scratch.grow(need * f->n_streams));
         f->scr_stride = need;
     }
     FrArgs a;

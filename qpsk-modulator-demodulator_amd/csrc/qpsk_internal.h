@@ -55,6 +55,8 @@ int handle_sync(qpsk_demod *h);
 #ifdef __HIP__   // qpsk_group.cpp is plain C++
 #include <hip/hip_runtime.h>
 
+#include "qpsk_device.h"
+
 namespace qpsk {
 // the pipelined path's front-stage stream (qpsk_rx.hip records "input consumed"
 // on it); nullptr before the first pipelined call
@@ -64,7 +66,7 @@ hipStream_t pipe_front_stream(const qpsk_demod *h);
 // its shape and stream, the four per-stream arrays of a state blob (hist: the
 // current one of the ping-pong pair, good until the next call is issued), the
 // link sums (nullptr until first enabled) and the staging buffer it keeps for
-// them, which qpsk_demod_destroy frees.
+// them, a member of the handle like its other buffers.
 struct StreamState;
 struct LinkAcc;
 struct StreamRows {
@@ -74,8 +76,7 @@ struct StreamRows {
     StreamState *state;
     float *carry, *hist, *fll_delay;
     LinkAcc *link;
-    void **staging;
-    size_t *staging_bytes;
+    DevBuf<char> *staging;
 };
 StreamRows handle_rows(qpsk_demod *h);
 }  // namespace qpsk

@@ -26,6 +26,7 @@
 
 #include "qpsk_demod.h"
 #include "qpsk_design.h"
+#include "qpsk_device.h"
 #include "qpsk_internal.h"
 
 struct qpsk_mod {
@@ -34,19 +35,14 @@ struct qpsk_mod {
     int sps = 0;
     int delay = 0;
     std::string tsc;           // "" = none (string.IsNullOrWhiteSpace)
-    float *d_taps = nullptr;   // (float) RRC taps, T
-    uint8_t *d_tsc = nullptr;  // TSC as packed bits
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    qpsk::Stream stream;           // in front of the buffers, which go first
+    qpsk::DevBuf<float> d_taps;    // (float) RRC taps, T
+    qpsk::DevBuf<uint8_t> d_tsc;   // TSC as packed bits
     // per-call device staging (grown as needed)
-    uint8_t *d_quad = nullptr;
-    size_t quad_bytes = 0;
-    uint8_t *d_bits = nullptr;
-    size_t bits_bytes = 0;
-    int64_t *d_nbits = nullptr;
-    int nbits_cap = 0;
-    float *d_out = nullptr;
-    size_t out_bytes = 0;
+    qpsk::DevBuf<uint8_t> d_quad;
+    qpsk::DevBuf<uint8_t> d_bits;
+    qpsk::DevBuf<int64_t> d_nbits;
+    qpsk::DevBuf<float> d_out;
 };
 
 namespace {
@@ -145,17 +141,8 @@ __global__ void mod_samples_kernel(ModArgs a) {
     o[1] = static_cast<float>(ai);
 }
 
-template <typename T>
-int grow(T **p, size_t *have, size_t need_bytes) {
-    if (need_bytes <= *have) return QPSK_OK;
-    hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(reinterpret_cast<void **>(p), need_bytes) != hipSuccess)
-        return fail(QPSK_ERR_DEVICE, "hipMalloc (modulator staging)");
-    *have = need_bytes;
-    return QPSK_OK;
-}
+// the status of a staging buffer's grow
+int staged(hipError_t e) { return e == hipSuccess ? QPSK_OK : fail(QPSK_ERR_DEVICE, "hipMalloc (modulator staging)"); }
 
 bool blank(const char *s) {
     if (!s) return true;
@@ -206,15 +193,13 @@ int qpsk_mod_create(const qpsk_mod_params *p, const char *tsc, qpsk_mod **out) {
     std::vector<uint8_t> tb((m->tsc.size() + 7) / 8 + 1, 0);
     for (size_t i = 0; i < m->tsc.size(); ++i)
         if (m->tsc[i] == '1') tb[i >> 3] |= static_cast<uint8_t>(0x80u >> (i & 7));
-    if (hipSetDevice(p->device) != hipSuccess || hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&m->d_taps), m->T * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&m->d_tsc), tb.size()) != hipSuccess ||
+    if (hipSetDevice(p->device) != hipSuccess || m->stream.create(hipStreamNonBlocking) != hipSuccess ||
+        m->d_taps.alloc(m->T) != hipSuccess || m->d_tsc.alloc(tb.size()) != hipSuccess ||
         hipMemcpy(m->d_taps, tf.data(), m->T * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(m->d_tsc, tb.data(), tb.size(), hipMemcpyHostToDevice) != hipSuccess) {
         qpsk_mod_destroy(m);
         return fail(QPSK_ERR_DEVICE, "modulator device set-up failed (no GPU?)");
     }
-    m->own_stream = true;
     *out = m;
     return QPSK_OK;
 }
@@ -222,13 +207,6 @@ int qpsk_mod_create(const qpsk_mod_params *p, const char *tsc, qpsk_mod **out) {
 int qpsk_mod_destroy(qpsk_mod *m) {
     if (!m) return QPSK_OK;
     if (m->stream) hipStreamSynchronize(m->stream);
-    hipFree(m->d_taps);
-    hipFree(m->d_tsc);
-    hipFree(m->d_quad);
-    hipFree(m->d_bits);
-    hipFree(m->d_nbits);
-    hipFree(m->d_out);
-    if (m->own_stream && m->stream) hipStreamDestroy(m->stream);
     delete m;
     return QPSK_OK;
 }
@@ -236,14 +214,7 @@ int qpsk_mod_destroy(qpsk_mod *m) {
 int qpsk_mod_set_stream(qpsk_mod *m, void *hip_stream) {
     if (!m) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     QPSK_HIP_TRY(hipStreamSynchronize(m->stream));
-    if (hip_stream) {
-        if (m->own_stream) hipStreamDestroy(m->stream);
-        m->stream = static_cast<hipStream_t>(hip_stream);
-        m->own_stream = false;
-    } else if (!m->own_stream) {
-        QPSK_HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        m->own_stream = true;
-    }
+    QPSK_HIP_TRY(m->stream.rebind(hip_stream));
     return QPSK_OK;
 }
 
@@ -286,28 +257,21 @@ int qpsk_mod_modulate(qpsk_mod *m, int32_t n_streams, const uint8_t *bits, int64
     a.out_stride = out_stride_floats;
     if (host) {
         const size_t brow = static_cast<size_t>((nb_max + 7) / 8 + 1);
-        if ((rc = grow(&m->d_bits, &m->bits_bytes, S * brow))) return rc;
+        if ((rc = staged(m->d_bits.grow(S * brow)))) return rc;
         if (nb_max > 0)
             QPSK_HIP_TRY(hipMemcpy2DAsync(m->d_bits, brow, bits, bits_stride_bytes, (nb_max + 7) / 8, S,
                                           hipMemcpyHostToDevice, st));
-        if (S > m->nbits_cap) {
-            hipFree(m->d_nbits);
-            m->d_nbits = nullptr;
-            m->nbits_cap = 0;
-            if (hipMalloc(reinterpret_cast<void **>(&m->d_nbits), S * sizeof(int64_t)) != hipSuccess)
-                return fail(QPSK_ERR_DEVICE, "hipMalloc");
-            m->nbits_cap = S;
-        }
+        if (m->d_nbits.grow(S * sizeof(int64_t)) != hipSuccess) return fail(QPSK_ERR_DEVICE, "hipMalloc");
         QPSK_HIP_TRY(hipMemcpyAsync(m->d_nbits, nb.data(), S * sizeof(int64_t), hipMemcpyHostToDevice, st));
         const size_t orow = static_cast<size_t>(2 * std::max<int64_t>(tot_max, 1));
-        if ((rc = grow(&m->d_out, &m->out_bytes, S * orow * sizeof(float)))) return rc;
+        if ((rc = staged(m->d_out.grow(S * orow * sizeof(float))))) return rc;
         a.bits = m->d_bits;
         a.bits_stride = static_cast<int64_t>(brow);
         a.n_bits = m->d_nbits;
         a.out = m->d_out;
         a.out_stride = static_cast<int64_t>(orow);
     }
-    if ((rc = grow(&m->d_quad, &m->quad_bytes, static_cast<size_t>(S) * std::max<int64_t>(nd_max, 1)))) return rc;
+    if ((rc = staged(m->d_quad.grow(static_cast<size_t>(S) * std::max<int64_t>(nd_max, 1))))) return rc;
     a.tsc = m->d_tsc;
     a.tsc_len = static_cast<int>(m->tsc.size());
     a.differential = m->p.differential;

@@ -14,8 +14,12 @@
 //
 // What the two stages share: the per-stream StreamState (its FLL fields are
 // written only by the FLL, every other field only by the loop kernel), and the
-// buffer at the stage boundary (MF rows, or FLL output rows), which is
-// double-buffered (fll_out[2] / mf[2]; the second only when pipelined).
+// MF rows at the stage boundary, which are double-buffered (mf[2]; the second
+// only when pipelined).  The FLL's output rows are one buffer: the FLL of call
+// k+1 runs behind the FIR of call k, their only reader, on the front stream.
+//
+// Every buffer, event and stream is a member that releases itself
+// (qpsk_device.h); the handle's destructor only waits for the queued work.
 //
 // Device layout (HBM, stream-major so every stage reads/writes each stream's
 // time axis contiguously):
@@ -45,12 +49,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "qpsk_demod.h"
 #include "qpsk_design.h"
+#include "qpsk_device.h"
 #include "qpsk_internal.h"
 #include "qpsk_kernels.h"
 #include "qpsk_state_blob.h"
@@ -58,14 +64,9 @@
 using namespace qpsk;
 
 namespace {
-template <typename T>
-int dev_alloc(T **p, size_t count) {
-    *p = nullptr;
-    if (count == 0) return QPSK_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T));
-    if (e != hipSuccess)
-        return fail(QPSK_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    return QPSK_OK;
+// the status of a DevBuf's alloc or grow
+int dev(hipError_t e) {
+    return e == hipSuccess ? QPSK_OK : fail(QPSK_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
 }
 
 // launch-timestamp slots of one timed call, a pair per kernel: its (start, end)
@@ -137,78 +138,74 @@ struct qpsk_demod {
     LoopParams lp{};
     int loop_variant = 0;
     FllParams fp{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    // the streams in front of every buffer and event: members go in reverse
+    // order of declaration, so what a stream's work used is released first
+    Stream stream;                   // the handle's own or its caller's (qpsk_demod_set_stream)
+    Stream s_front, s_back;          // pipelined calls
     int64_t n_max = 0;
     int64_t mf_stride = 0;       // float2
     int64_t bits_words = 0;      // per stream
     int64_t syms_cap = 0;        // per stream
-    float *d_hrev = nullptr;
-    void *d_in = nullptr;            // host-input staging, in the call's format
-    size_t in_bytes = 0;
+    DevBuf<float> d_hrev;
+    DevBuf<char> d_in;               // host-input staging, in the call's format
     // per input format (CF32 has none): CS16 (float)int16 * scale, SoapySDR's
     // CS16 -> CF32 convention; CS8 / CU8 full scale 128 (S8toF32, U8toS8)
     float in_scale[kFmts] = {0.0f, 1.0f / 32768, 1.0f / 128, 1.0f / 128};
-    float *d_fll_out[2] = {nullptr, nullptr};
-    float *d_iqb = nullptr;          // [S][n_max] float2, IQ_Balancer output (iq_balance only)
-    float *d_hist[2] = {nullptr, nullptr};
+    DevBuf<float> d_fll_out;         // [S][n_max] float2, FLL output (enable_fll only)
+    DevBuf<float> d_iqb;             // [S][n_max] float2, IQ_Balancer output (iq_balance only)
+    DevBuf<float> d_hist[2];
     int hist_cur = 0;
-    float *d_mf[2] = {nullptr, nullptr};
-    float *d_carry = nullptr;
-    StreamState *d_state = nullptr;
-    float *d_fll_delay = nullptr;
-    uint32_t *d_bits = nullptr;
-    float *d_syms = nullptr;
-    int64_t *d_counts = nullptr;     // [2][S]: n_bits, n_syms
-    int64_t *d_lengths[2] = {nullptr, nullptr};
-    int64_t *h_counts = nullptr;     // pinned
+    DevBuf<float> d_mf[2];
+    DevBuf<float> d_carry;
+    DevBuf<StreamState> d_state;
+    DevBuf<float> d_fll_delay;
+    DevBuf<uint32_t> d_bits;
+    DevBuf<float> d_syms;
+    DevBuf<int64_t> d_counts;        // [2][S]: n_bits, n_syms
+    DevBuf<int64_t> d_lengths[2];
+    PinnedBuf<int64_t> h_counts;
     // status flags (QPSK_STATUS_*): [0] = raised by device-memory calls since the
     // last qpsk_demod_status, [1] = raised by the current host-memory call
-    uint32_t *d_flags = nullptr;
-    uint32_t *h_flags = nullptr;     // pinned
+    DevBuf<uint32_t> d_flags;
+    PinnedBuf<uint32_t> h_flags;
     uint32_t status_host = 0;        // raised by host-memory calls since the last status
     // chunked calls (longer than max_samples_per_call): running per-stream
     // output offsets [2][S] and, for host-memory calls, device staging of the
     // whole call's output rows
-    int64_t *d_acc = nullptr;
-    uint8_t *d_xbits = nullptr;
-    size_t xbits_bytes = 0;
-    float *d_xsyms = nullptr;
-    size_t xsyms_bytes = 0;
+    DevBuf<int64_t> d_acc;
+    DevBuf<uint8_t> d_xbits;
+    DevBuf<float> d_xsyms;
     // link statistics (qpsk_demod_link_stats): the per-stream running sums the
     // loop kernel's decode wave continues while link_on, and the rows a
     // host-memory read is gathered into (both made by the first enable)
     bool link_on = false;
-    LinkAcc *d_link = nullptr;
-    qpsk_link_stats *d_link_rows = nullptr;
+    DevBuf<LinkAcc> d_link;
+    DevBuf<qpsk_link_stats> d_link_rows;
     // rows of selected streams (qpsk_stream_state.hip): the packed sub-blob and
     // the index list behind it, grown on demand
-    void *d_rows = nullptr;
-    size_t rows_bytes = 0;
+    DevBuf<char> d_rows;
     bool timing = false;
     // launch timestamps of the timed calls ([call][kKtPerCall] wall-clock ticks,
     // written by the kernels themselves: qpsk_kernels.h kt_start / kt_end)
-    unsigned long long *d_kt = nullptr;
+    DevBuf<unsigned long long> d_kt;
     int kt_used = 0;
     // FIR phase sample (qpsk_demod_enable_fir_phases): per-phase cycle sums
     // [2][8] and the map of CUs a loop workgroup holds [kCuKeys]
     bool fir_phases = false;
-    unsigned long long *d_phases = nullptr;
-    unsigned *d_cu_map = nullptr;
+    DevBuf<unsigned long long> d_phases;
+    DevBuf<unsigned> d_cu_map;
     int wall_khz = 100000;
     int cus = 0;
     // ---- pipelined calls (qpsk_demod_process_async) ----------------------
     bool pipe_ready = false;
     int pipe_bufs = 0;               // 2 = double-buffered stage boundary, 1 = no room for it
     int pipe_cur = 0;
-    hipStream_t s_front = nullptr, s_back = nullptr;
-    hipEvent_t e_in = nullptr;
-    hipEvent_t e_front[2] = {nullptr, nullptr}, e_back[2] = {nullptr, nullptr};
-    bool front_rec[2] = {false, false}, back_rec[2] = {false, false};
+    Event e_in;
+    Event e_front[2], e_back[2];
     // FLL off: residency counter (signal memory) the loop kernel's workgroups
     // increment as they start; the next call's FIR waits for it to reach
     // resident_gate (see process_async_one)
-    unsigned long long *d_resident = nullptr;
+    DevBuf<unsigned long long> d_resident;
     uint64_t resident_issued = 0;    // workgroups of every gated loop launch so far
     uint64_t resident_gate = 0;      // what the newest gated loop launch brings it to, at least
     bool gate_pending = false;       // the next FIR has a loop launch to wait for
@@ -221,19 +218,21 @@ struct qpsk_demod {
     // when it runs out; gate_publish = false (QPSK_GATE_NO_PUBLISH=1 together
     // with QPSK_PIPELINE_GATE=1, tests only) keeps the loop workgroups from
     // counting, so every wait runs out
-    unsigned *d_gate = nullptr;
+    DevBuf<unsigned> d_gate;
     unsigned long long gate_cap_ticks = 0;
     bool gate_publish = true;
     int last_back = -1;              // boundary buffer of the newest back stage, -1 = none
-    int64_t *h_len[2] = {nullptr, nullptr};   // pinned staging of per-call lengths
+    PinnedBuf<int64_t> h_len[2];     // staging of per-call lengths
     // FLL on: the back stage (loop kernel) of the newest call is issued by the
     // next call, after that call's FLL, or by a flush (see process_async_one)
-    hipEvent_t e_fll = nullptr;
+    Event e_fll;
     bool deferred = false;
     Call dcall{};
     int dbuf = 0;
     const int64_t *dlen = nullptr;
     unsigned long long *dkt = nullptr;
+
+    ~qpsk_demod();
 };
 
 namespace qpsk {
@@ -246,14 +245,14 @@ int handle_device(const qpsk_demod *h) { return h->p.device; }
 int handle_taps(const qpsk_demod *h) { return h->T; }
 StreamRows handle_rows(qpsk_demod *h) {
     return StreamRows{&h->p,      h->S,       h->T,      h->stream,  h->d_state, h->d_carry, h->d_hist[h->hist_cur],
-                      h->d_fll_delay, h->d_link, &h->d_rows, &h->rows_bytes};
+                      h->d_fll_delay, h->d_link, &h->d_rows};
 }
 }  // namespace qpsk
 
 namespace {
 
 // The newest pipelined call's back stage, or nullptr.
-hipEvent_t last_async(const qpsk_demod *h) { return h->last_back >= 0 ? h->e_back[h->last_back] : nullptr; }
+const Event *last_async(const qpsk_demod *h) { return h->last_back >= 0 ? &h->e_back[h->last_back] : nullptr; }
 
 int flush_deferred(qpsk_demod *h);   // issues a deferred back stage (with the stage runners)
 
@@ -262,7 +261,7 @@ int flush_deferred(qpsk_demod *h);   // issues a deferred back stage (with the s
 int drain_async(qpsk_demod *h) {
     int rc;
     if ((rc = flush_deferred(h))) return rc;
-    if (hipEvent_t e = last_async(h)) QPSK_HIP_TRY(hipEventSynchronize(e));
+    if (const Event *e = last_async(h)) QPSK_HIP_TRY(e->sync());
     return QPSK_OK;
 }
 
@@ -272,26 +271,18 @@ int ensure_syms(qpsk_demod *h) {
     // on the handle's device whatever the calling thread's current one is
     // (a group's worker threads, qpsk_group.cpp)
     QPSK_HIP_TRY(hipSetDevice(h->p.device));
-    return dev_alloc(&h->d_syms, static_cast<size_t>(2 * h->S * h->syms_cap));
-}
-
-// grow-on-demand scratch: *p holds at least need bytes afterwards (what it
-// held is dropped; nothing queued may still use it)
-template <typename T>
-int ensure_bytes(T **p, size_t *have, size_t need) {
-    if (need <= *have) return QPSK_OK;
-    hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    char *q = nullptr;
-    int rc;
-    if ((rc = dev_alloc(&q, need))) return rc;
-    *p = static_cast<T *>(static_cast<void *>(q));
-    *have = need;
-    return QPSK_OK;
+    return dev(h->d_syms.alloc(static_cast<size_t>(2 * h->S * h->syms_cap)));
 }
 
 }  // namespace
+
+// What the members cannot do for themselves: on the handle's device (the
+// frees and the stream teardown behind this body too), after all queued work.
+qpsk_demod::~qpsk_demod() {
+    (void)hipSetDevice(p.device);
+    drain_async(this);
+    if (stream) hipStreamSynchronize(stream);
+}
 
 int qpsk::handle_sync(qpsk_demod *h) {
     int rc;
@@ -413,8 +404,8 @@ void pre_stages(qpsk_demod *h, InRows *in, const int64_t *d_len, int64_t n_call,
     }
     if (h->p.enable_fll) {
         const float *x = float_rows(h, in, d_len, n_call, mf, st);
-        run_fll(h, x, in->stride, d_len, n_call, h->d_fll_out[0], st, kt);
-        *in = InRows{h->d_fll_out[0], h->n_max, kFmtCf32, 0.0f};
+        run_fll(h, x, in->stride, d_len, n_call, h->d_fll_out, st, kt);
+        *in = InRows{h->d_fll_out, h->n_max, kFmtCf32, 0.0f};
     }
 }
 
@@ -598,8 +589,7 @@ int issue_back(qpsk_demod *h, const Call &c, const int64_t *d_len, int buf, unsi
                unsigned long long *resident) {
     int rc;
     if ((rc = run_loop(h, c, d_len, h->d_mf[buf], h->s_back, kt, resident))) return rc;
-    QPSK_HIP_TRY(hipEventRecord(h->e_back[buf], h->s_back));
-    h->back_rec[buf] = true;
+    QPSK_HIP_TRY(h->e_back[buf].record(h->s_back));
     h->last_back = buf;
     return QPSK_OK;
 }
@@ -613,44 +603,41 @@ namespace {
 // latency-bound stage, the front stage fills the CUs it leaves idle.
 int pipe_setup(qpsk_demod *h) {
     if (h->pipe_ready) return QPSK_OK;
-    // every step is guarded: a set-up that failed part way runs again on the
-    // next pipelined call and completes what is missing, leaking nothing and
-    // keeping (not re-zeroing) the counters it already made
+    // every step makes what is missing and keeps what is there: a set-up that
+    // failed part way runs again on the next pipelined call and completes,
+    // without re-zeroing the counters it already made
     int least = 0, greatest = 0;
     QPSK_HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    if (!h->s_front) QPSK_HIP_TRY(hipStreamCreateWithPriority(&h->s_front, hipStreamNonBlocking, least));
-    if (!h->s_back) QPSK_HIP_TRY(hipStreamCreateWithPriority(&h->s_back, hipStreamNonBlocking, greatest));
-    if (!h->e_in) QPSK_HIP_TRY(hipEventCreateWithFlags(&h->e_in, hipEventDisableTiming));
+    QPSK_HIP_TRY(h->s_front.create(hipStreamNonBlocking, least));
+    QPSK_HIP_TRY(h->s_back.create(hipStreamNonBlocking, greatest));
+    QPSK_HIP_TRY(h->e_in.ensure());
     for (int b = 0; b < 2; ++b) {
-        if (!h->e_front[b]) QPSK_HIP_TRY(hipEventCreateWithFlags(&h->e_front[b], hipEventDisableTiming));
-        if (!h->e_back[b]) QPSK_HIP_TRY(hipEventCreateWithFlags(&h->e_back[b], hipEventDisableTiming));
-        if (!h->h_len[b]) QPSK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_len[b]), h->S * sizeof(int64_t)));
+        QPSK_HIP_TRY(h->e_front[b].ensure());
+        QPSK_HIP_TRY(h->e_back[b].ensure());
+        QPSK_HIP_TRY(h->h_len[b].alloc(h->S));
     }
-    if (!h->e_fll) QPSK_HIP_TRY(hipEventCreateWithFlags(&h->e_fll, hipEventDisableTiming));
+    QPSK_HIP_TRY(h->e_fll.ensure());
     if (!h->d_resident) {
-        QPSK_HIP_TRY(hipExtMallocWithFlags(reinterpret_cast<void **>(&h->d_resident), sizeof(unsigned long long),
-                                           hipMallocSignalMemory));
+        // signal memory: the one allocation made here, released like any other
+        unsigned long long *r = nullptr;
+        QPSK_HIP_TRY(hipExtMallocWithFlags(reinterpret_cast<void **>(&r), sizeof(*r), hipMallocSignalMemory));
+        h->d_resident.adopt(r, sizeof(*r));
         QPSK_HIP_TRY(hipMemset(h->d_resident, 0, sizeof(unsigned long long)));
     }
     int rc;
     if (!h->d_gate) {
-        if ((rc = dev_alloc(&h->d_gate, 1))) return rc;
+        if ((rc = dev(h->d_gate.alloc(1)))) return rc;
         QPSK_HIP_TRY(hipMemset(h->d_gate, 0, sizeof(unsigned)));
     }
-    if (!h->d_lengths[1] && (rc = dev_alloc(&h->d_lengths[1], h->S))) return rc;
+    if ((rc = dev(h->d_lengths[1].alloc(h->S)))) return rc;
     // the second boundary buffer: MF rows (the FIR of one call writes one while
     // the loop kernel of the previous call reads the other).  No room for it
     // (batches near the 288 GB) -> calls still queue back to back, but each
     // front stage waits for the previous back stage
     const size_t S = static_cast<size_t>(h->S);
     if (!h->d_mf[1]) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&h->d_mf[1]), 2 * S * h->mf_stride * sizeof(float));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            h->d_mf[1] = nullptr;
-        } else {
-            QPSK_HIP_TRY(hipMemset(h->d_mf[1], 0, 2 * S * h->mf_stride * sizeof(float)));
-        }
+        if (h->d_mf[1].alloc(2 * S * h->mf_stride) != hipSuccess) (void)hipGetLastError();
+        else QPSK_HIP_TRY(hipMemset(h->d_mf[1], 0, 2 * S * h->mf_stride * sizeof(float)));
     }
     // as at creation: the memsets above (counter, gate, MF rows) ran on the null
     // stream and are done before any pipelined call uses what they cleared
@@ -716,9 +703,9 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
     if (p->costas_trig != 0 && p->costas_trig != 1)
         return fail(QPSK_ERR_ARGUMENT, "costas_trig must be 0 (portable) or 1 (glibc)");
 
-    // every knob is good: from here on a failure is the device's, and the one
-    // way out is cleanup_fail
-    auto *h = new qpsk_demod();
+    // every knob is good: from here on a failure is the device's, and the
+    // handle's destructor releases whatever was made before it
+    std::unique_ptr<qpsk_demod> h(new qpsk_demod());
     h->p = *p;
     h->S = n_streams;
     h->W = W;
@@ -754,12 +741,7 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
         if (up != ((k & 1) ? (lo ^ 0x80000000u) : lo)) h->fp.conj_taps = 0;
     }
 
-    auto cleanup_fail = [&](int code) {
-        qpsk_demod_destroy(h);
-        return code;
-    };
-    if (hipSetDevice(p->device) != hipSuccess)
-        return cleanup_fail(fail(QPSK_ERR_DEVICE, "hipSetDevice failed (no GPU?)"));
+    if (hipSetDevice(p->device) != hipSuccess) return fail(QPSK_ERR_DEVICE, "hipSetDevice failed (no GPU?)");
     if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess)
         h->cus = 0;
     if (hipDeviceGetAttribute(&h->wall_khz, hipDeviceAttributeWallClockRate, p->device) != hipSuccess ||
@@ -777,33 +759,28 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
         const bool forced = force && std::strcmp(force, "1") == 0;
         h->gate_publish = !(forced && np && *np && std::strcmp(np, "0") != 0);
     }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-        return cleanup_fail(fail(QPSK_ERR_DEVICE, "hipStreamCreate failed"));
-    h->own_stream = true;
+    if (h->stream.create(hipStreamNonBlocking) != hipSuccess) return fail(QPSK_ERR_DEVICE, "hipStreamCreate failed");
 
     const int64_t S = n_streams;
     h->n_max = p->max_samples_per_call;
     h->mf_stride = ((kMfPrefix + h->n_max + 2 + 63) / 64) * 64;   // + row slack for the loop loader
-    h->syms_cap = qpsk_demod_max_symbols(h, h->n_max);
+    h->syms_cap = qpsk_demod_max_symbols(h.get(), h->n_max);
     h->bits_words = (2 * h->syms_cap + 31) / 32 + 1;
     const int H = h->T - 1;
-    if ((rc = dev_alloc(&h->d_hrev, h->T)) || (rc = dev_alloc(&h->d_hist[0], 2 * S * H)) ||
-        (rc = dev_alloc(&h->d_hist[1], 2 * S * H)) ||
-        (rc = dev_alloc(&h->d_mf[0], static_cast<size_t>(2 * S * h->mf_stride))) ||
-        (rc = dev_alloc(&h->d_carry, 2 * S * kCarryMax)) || (rc = dev_alloc(&h->d_state, S)) ||
-        (rc = dev_alloc(&h->d_fll_delay, 2 * S * 2 * kFllTaps)) ||
-        (rc = dev_alloc(&h->d_bits, static_cast<size_t>(S * h->bits_words))) ||
-        (rc = dev_alloc(&h->d_counts, 2 * S)) || (rc = dev_alloc(&h->d_lengths[0], S)))
-        return cleanup_fail(rc);
-    if (p->enable_fll && (rc = dev_alloc(&h->d_fll_out[0], static_cast<size_t>(2 * S * h->n_max))))
-        return cleanup_fail(rc);
-    if (p->iq_balance && (rc = dev_alloc(&h->d_iqb, static_cast<size_t>(2 * S * h->n_max))))
-        return cleanup_fail(rc);
-    if (hipHostMalloc(reinterpret_cast<void **>(&h->h_counts), 2 * S * sizeof(int64_t)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&h->h_flags), sizeof(uint32_t)) != hipSuccess)
-        return cleanup_fail(fail(QPSK_ERR_DEVICE, "hipHostMalloc"));
-    if ((rc = dev_alloc(&h->d_flags, 2)) || hipMemset(h->d_flags, 0, 2 * sizeof(uint32_t)) != hipSuccess)
-        return cleanup_fail(rc ? rc : fail(QPSK_ERR_DEVICE, "hipMemset"));
+    hipError_t e;
+    if ((e = h->d_hrev.alloc(h->T)) || (e = h->d_hist[0].alloc(2 * S * H)) || (e = h->d_hist[1].alloc(2 * S * H)) ||
+        (e = h->d_mf[0].alloc(static_cast<size_t>(2 * S * h->mf_stride))) ||
+        (e = h->d_carry.alloc(2 * S * kCarryMax)) || (e = h->d_state.alloc(S)) ||
+        (e = h->d_fll_delay.alloc(2 * S * 2 * kFllTaps)) ||
+        (e = h->d_bits.alloc(static_cast<size_t>(S * h->bits_words))) || (e = h->d_counts.alloc(2 * S)) ||
+        (e = h->d_lengths[0].alloc(S)) ||
+        (p->enable_fll && (e = h->d_fll_out.alloc(static_cast<size_t>(2 * S * h->n_max)))) ||
+        (p->iq_balance && (e = h->d_iqb.alloc(static_cast<size_t>(2 * S * h->n_max)))))
+        return dev(e);
+    if (h->h_counts.alloc(2 * S) != hipSuccess || h->h_flags.alloc(1) != hipSuccess)
+        return fail(QPSK_ERR_DEVICE, "hipHostMalloc");
+    if ((rc = dev(h->d_flags.alloc(2))) || hipMemset(h->d_flags, 0, 2 * sizeof(uint32_t)) != hipSuccess)
+        return rc ? rc : fail(QPSK_ERR_DEVICE, "hipMemset");
     std::vector<float> hrev(h->T);
     for (int k = 0; k < h->T; ++k) hrev[k] = h->d.rrc_f32[h->T - 1 - k];
     // Fresh instances: zero delay lines (FIRFilter.cs:50-51), M&M baseIndex = 1
@@ -824,54 +801,13 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
         // without this the first call's kernels race a multi-GB clear of the
         // MF rows (seen as 4 KB of zero MF samples in the middle of a row)
         hipStreamSynchronize(nullptr) != hipSuccess)
-        return cleanup_fail(fail(QPSK_ERR_DEVICE, "device init failed"));
-    *out = h;
+        return fail(QPSK_ERR_DEVICE, "device init failed");
+    *out = h.release();
     return QPSK_OK;
 }
 
 int qpsk_demod_destroy(qpsk_demod *h) {
-    if (!h) return QPSK_OK;
-    (void)hipSetDevice(h->p.device);   // frees and stream teardown on the handle's device
-    drain_async(h);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    hipFree(h->d_hrev);
-    hipFree(h->d_in);
-    for (int b = 0; b < 2; ++b) {
-        hipFree(h->d_fll_out[b]);
-        hipFree(h->d_hist[b]);
-        hipFree(h->d_mf[b]);
-        hipFree(h->d_lengths[b]);
-        if (h->h_len[b]) hipHostFree(h->h_len[b]);
-        if (h->e_front[b]) hipEventDestroy(h->e_front[b]);
-        if (h->e_back[b]) hipEventDestroy(h->e_back[b]);
-    }
-    if (h->d_resident) hipFree(h->d_resident);
-    hipFree(h->d_gate);
-    hipFree(h->d_kt);
-    hipFree(h->d_phases);
-    hipFree(h->d_cu_map);
-    hipFree(h->d_carry);
-    hipFree(h->d_iqb);
-    hipFree(h->d_state);
-    hipFree(h->d_fll_delay);
-    hipFree(h->d_bits);
-    hipFree(h->d_syms);
-    hipFree(h->d_counts);
-    if (h->h_counts) hipHostFree(h->h_counts);
-    if (h->h_flags) hipHostFree(h->h_flags);
-    hipFree(h->d_flags);
-    hipFree(h->d_acc);
-    hipFree(h->d_xbits);
-    hipFree(h->d_xsyms);
-    hipFree(h->d_link);
-    hipFree(h->d_link_rows);
-    hipFree(h->d_rows);
-    if (h->e_in) hipEventDestroy(h->e_in);
-    if (h->e_fll) hipEventDestroy(h->e_fll);
-    if (h->s_front) hipStreamDestroy(h->s_front);
-    if (h->s_back) hipStreamDestroy(h->s_back);
-    if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // nullptr included; ~qpsk_demod waits for the handle's work
     return QPSK_OK;
 }
 
@@ -879,14 +815,7 @@ int qpsk_demod_set_stream(qpsk_demod *h, void *hip_stream) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     int rc;
     if ((rc = handle_sync(h))) return rc;
-    if (hip_stream) {
-        if (h->own_stream) hipStreamDestroy(h->stream);
-        h->stream = static_cast<hipStream_t>(hip_stream);
-        h->own_stream = false;
-    } else if (!h->own_stream) {
-        QPSK_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
+    QPSK_HIP_TRY(h->stream.rebind(hip_stream));
     return QPSK_OK;
 }
 
@@ -898,7 +827,7 @@ int qpsk_demod_enable_timing(qpsk_demod *h, int32_t on) {
     QPSK_HIP_TRY(hipSetDevice(h->p.device));
     int rc;
     const size_t n = static_cast<size_t>(kKtCalls) * kKtPerCall;
-    if (!h->d_kt && (rc = dev_alloc(&h->d_kt, n))) return rc;
+    if ((rc = dev(h->d_kt.alloc(n)))) return rc;
     // spans: start = +inf for the atomic minimum, end = 0 for the maximum;
     // clock sums = 0
     std::vector<unsigned long long> init(n, 0ull);
@@ -916,12 +845,9 @@ int qpsk_demod_enable_fir_phases(qpsk_demod *h, int32_t on) {
     if (on && (!h->d_phases || !h->d_cu_map)) {
         // both or neither: a half-allocated pair would let the sampled FIR
         // workgroups read a null cu_map
-        if ((!h->d_phases && (rc = dev_alloc(&h->d_phases, kFirPhaseWords))) ||
-            (!h->d_cu_map && (rc = dev_alloc(&h->d_cu_map, kCuKeys)))) {
-            hipFree(h->d_phases);
-            hipFree(h->d_cu_map);
-            h->d_phases = nullptr;
-            h->d_cu_map = nullptr;
+        if ((rc = dev(h->d_phases.alloc(kFirPhaseWords))) || (rc = dev(h->d_cu_map.alloc(kCuKeys)))) {
+            h->d_phases.reset();
+            h->d_cu_map.reset();
             return rc;
         }
         QPSK_HIP_TRY(hipMemset(h->d_cu_map, 0, kCuKeys * sizeof(unsigned)));
@@ -1042,7 +968,7 @@ int process_one(qpsk_demod *h, const Call &c) {
     QPSK_HIP_TRY(hipSetDevice(h->p.device));
     // pipelined calls issued before this one finish first (they share the state)
     if ((rc = flush_deferred(h))) return rc;
-    if (hipEvent_t e = last_async(h)) QPSK_HIP_TRY(hipStreamWaitEvent(st, e, 0));
+    if (const Event *e = last_async(h)) QPSK_HIP_TRY(e->wait(st));
     unsigned long long *kt = next_kt(h);
     if (mem == QPSK_MEM_HOST && !c.append) QPSK_HIP_TRY(hipMemsetAsync(h->d_flags + 1, 0, sizeof(uint32_t), st));
 
@@ -1054,7 +980,7 @@ int process_one(qpsk_demod *h, const Call &c) {
         const size_t eb = elem_bytes(c.fmt);
         const int64_t pitch = stage_pitch(c.fmt, h->n_max);   // samples
         // the last host-memory call has returned, so nothing reads d_in
-        if ((rc = ensure_bytes(&h->d_in, &h->in_bytes, static_cast<size_t>(S) * pitch * 2 * eb))) return rc;
+        if ((rc = dev(h->d_in.grow(static_cast<size_t>(S) * pitch * 2 * eb)))) return rc;
         QPSK_HIP_TRY(hipMemcpy2DAsync(h->d_in, 2 * pitch * eb, c.iq, stride_floats * eb, 2 * n_call * eb, S,
                                       hipMemcpyHostToDevice, st));
         in.x = h->d_in;
@@ -1086,15 +1012,15 @@ int process_async_one(qpsk_demod *h, const Call &c) {
     // the front stage starts after the work already on the handle's stream
     // (the producer of iq, earlier synchronous calls) and after the back stage
     // that last used boundary buffer b
-    QPSK_HIP_TRY(hipEventRecord(h->e_in, h->stream));
-    QPSK_HIP_TRY(hipStreamWaitEvent(F, h->e_in, 0));
+    QPSK_HIP_TRY(h->e_in.record(h->stream));
+    QPSK_HIP_TRY(h->e_in.wait(F));
     const int prev = h->pipe_bufs == 2 ? b : h->last_back;
-    if (prev >= 0 && h->back_rec[prev]) QPSK_HIP_TRY(hipStreamWaitEvent(F, h->e_back[prev], 0));
+    if (prev >= 0) QPSK_HIP_TRY(h->e_back[prev].wait(F));
     unsigned long long *kt = next_kt(h);
     const int64_t *d_len = nullptr;
     if (lengths) {
         // pinned staging row b is free once the front stage that last read it ran
-        if (h->front_rec[b]) QPSK_HIP_TRY(hipEventSynchronize(h->e_front[b]));
+        QPSK_HIP_TRY(h->e_front[b].sync());
         std::memcpy(h->h_len[b], lengths, S * sizeof(int64_t));
         QPSK_HIP_TRY(hipMemcpyAsync(h->d_lengths[b], h->h_len[b], S * sizeof(int64_t), hipMemcpyHostToDevice, F));
         d_len = h->d_lengths[b];
@@ -1118,16 +1044,15 @@ int process_async_one(qpsk_demod *h, const Call &c) {
         // a flush (pipeline_wait, a synchronous call, state access, destroy).
         // FLL(k) waited above for loop(k-2), the last reader of MF rows b, and
         // follows FIR(k-1) on F, so it runs alone.
-        QPSK_HIP_TRY(hipEventRecord(h->e_fll, F));
+        QPSK_HIP_TRY(h->e_fll.record(F));
         if (h->deferred) {
-            QPSK_HIP_TRY(hipStreamWaitEvent(B, h->e_fll, 0));
+            QPSK_HIP_TRY(h->e_fll.wait(B));
             h->deferred = false;
             if ((rc = issue_back(h, h->dcall, h->dlen, h->dbuf, h->dkt, resident))) return rc;
         }
         if ((rc = gate_wait(h, F))) return rc;
         if ((rc = run_fir(h, in, d_len, n_call, mf, F, kt))) return rc;
-        QPSK_HIP_TRY(hipEventRecord(h->e_front[b], F));
-        h->front_rec[b] = true;
+        QPSK_HIP_TRY(h->e_front[b].record(F));
         h->dcall = c;
         h->dbuf = b;
         h->dlen = d_len;
@@ -1152,10 +1077,9 @@ int process_async_one(qpsk_demod *h, const Call &c) {
         // workgroups run, and every one of those was dispatched before it.
         if ((rc = gate_wait(h, F))) return rc;
         if ((rc = run_fir(h, in, d_len, n_call, mf, F, kt))) return rc;
-        QPSK_HIP_TRY(hipEventRecord(h->e_front[b], F));
-        QPSK_HIP_TRY(hipStreamWaitEvent(B, h->e_front[b], 0));
+        QPSK_HIP_TRY(h->e_front[b].record(F));
+        QPSK_HIP_TRY(h->e_front[b].wait(B));
     }
-    h->front_rec[b] = true;
     return issue_back(h, c, d_len, b, kt, resident);
 }
 
@@ -1164,7 +1088,7 @@ int flush_deferred(qpsk_demod *h) {
     if (!h->deferred) return QPSK_OK;
     QPSK_HIP_TRY(hipSetDevice(h->p.device));
     h->deferred = false;
-    QPSK_HIP_TRY(hipStreamWaitEvent(h->s_back, h->e_front[h->dbuf], 0));
+    QPSK_HIP_TRY(h->e_front[h->dbuf].wait(h->s_back));
     return issue_back(h, h->dcall, h->dlen, h->dbuf, h->dkt, nullptr);
 }
 
@@ -1190,7 +1114,7 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
     const int64_t N = h->n_max;
     int rc;
     QPSK_HIP_TRY(hipSetDevice(h->p.device));
-    if (!h->d_acc && (rc = dev_alloc(&h->d_acc, 2 * static_cast<size_t>(S)))) return rc;
+    if ((rc = dev(h->d_acc.alloc(2 * static_cast<size_t>(S))))) return rc;
     const bool host = c.mem == QPSK_MEM_HOST;   // synchronous calls only: pipelined ones take device memory
     const int64_t bytes_row = (2 * c.max_sym + 7) / 8;
     uint8_t *dbits = c.bits;
@@ -1199,13 +1123,13 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
     int64_t dsyms_stride = c.syms_stride_floats;
     if (host) {
         if (c.bits) {
-            if ((rc = ensure_bytes(&h->d_xbits, &h->xbits_bytes, static_cast<size_t>(S) * bytes_row))) return rc;
+            if ((rc = dev(h->d_xbits.grow(static_cast<size_t>(S) * bytes_row)))) return rc;
             dbits = h->d_xbits;
             dbits_stride = bytes_row;
         }
         if (c.syms) {
             const size_t need = static_cast<size_t>(S) * 2 * c.max_sym * sizeof(float);
-            if ((rc = ensure_bytes(&h->d_xsyms, &h->xsyms_bytes, need))) return rc;
+            if ((rc = dev(h->d_xsyms.grow(need)))) return rc;
             dsyms = h->d_xsyms;
             dsyms_stride = 2 * c.max_sym;
         }
@@ -1250,8 +1174,8 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
             // with the FLL the newest one is only issued by flush_deferred.
             if (k > 0) {
                 (void)flush_deferred(h);
-                if (hipEvent_t e = last_async(h)) (void)hipStreamWaitEvent(h->stream, e, 0);
-                (void)hipMemset2DAsync(reinterpret_cast<char *>(h->d_state) + offsetof(StreamState, tofs),
+                if (const Event *e = last_async(h)) (void)e->wait(h->stream);
+                (void)hipMemset2DAsync(reinterpret_cast<char *>(h->d_state.get()) + offsetof(StreamState, tofs),
                                        sizeof(StreamState), 0, sizeof(int64_t), S, h->stream);
             }
             return rc;
@@ -1404,8 +1328,7 @@ int qpsk_demod_enable_link_stats(qpsk_demod *h, int32_t on) {
     if ((rc = handle_sync(h))) return rc;
     if (on) {
         const size_t S = static_cast<size_t>(h->S);
-        if (!h->d_link && (rc = dev_alloc(&h->d_link, S))) return rc;
-        if (!h->d_link_rows && (rc = dev_alloc(&h->d_link_rows, S))) return rc;
+        if ((rc = dev(h->d_link.alloc(S))) || (rc = dev(h->d_link_rows.alloc(S)))) return rc;
         // +0.0, +0.0, 0; on the handle's stream, which every later call and
         // read is ordered behind (a null-stream memset is not: the handle's
         // streams do not synchronise with it)
@@ -1446,10 +1369,10 @@ int qpsk_demod_pipeline_wait(qpsk_demod *h, void *hip_stream) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     int rc;
     if ((rc = flush_deferred(h))) return rc;
-    hipEvent_t e = last_async(h);
+    const Event *e = last_async(h);
     if (!e) return QPSK_OK;
-    if (hip_stream) QPSK_HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), e, 0));
-    else QPSK_HIP_TRY(hipEventSynchronize(e));
+    if (hip_stream) QPSK_HIP_TRY(e->wait(static_cast<hipStream_t>(hip_stream)));
+    else QPSK_HIP_TRY(e->sync());
     return QPSK_OK;
 }
 
@@ -1530,24 +1453,31 @@ int64_t qpsk_demod_state_bytes(const qpsk_demod *h) {
     return state_blob_bytes(h->S, h->T);
 }
 
+// The four sections of a blob behind its header, in the blob's order, each
+// against the array of the handle that holds it (handle_rows).
+static int copy_state(qpsk_demod *h, char *blob, hipMemcpyKind kind) {
+    const StreamRows v = handle_rows(h);
+    void *const rows[kStateSections] = {v.state, v.carry, v.hist, v.fll_delay};
+    int64_t words[kStateSections];
+    state_row_words(v.T, words);
+    char *p = blob + sizeof(StateHeader);
+    for (int k = 0; k < kStateSections; ++k) {
+        const size_t n = static_cast<size_t>(v.S) * 8 * words[k];
+        const bool out = kind == hipMemcpyDeviceToHost;
+        if (n) QPSK_HIP_TRY(hipMemcpy(out ? p : rows[k], out ? rows[k] : p, n, kind));
+        p += n;
+    }
+    return QPSK_OK;
+}
+
 int qpsk_demod_get_state(qpsk_demod *h, void *host_buf, int64_t buf_bytes) {
     if (!h || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     if (buf_bytes < qpsk_demod_state_bytes(h)) return fail(QPSK_ERR_ARGUMENT, "state buffer too small");
-    const int64_t S = h->S, H = h->T - 1;
-    char *p = static_cast<char *>(host_buf);
     int rc;
     if ((rc = handle_sync(h))) return rc;
     const StateHeader hd = state_header(h->S, h->T);
-    std::memcpy(p, &hd, sizeof(hd));
-    p += sizeof(hd);
-    QPSK_HIP_TRY(hipMemcpy(p, h->d_state, S * sizeof(StreamState), hipMemcpyDeviceToHost));
-    p += S * sizeof(StreamState);
-    QPSK_HIP_TRY(hipMemcpy(p, h->d_carry, S * 8 * kCarryMax, hipMemcpyDeviceToHost));
-    p += S * 8 * kCarryMax;
-    if (H > 0) QPSK_HIP_TRY(hipMemcpy(p, h->d_hist[h->hist_cur], S * 8 * H, hipMemcpyDeviceToHost));
-    p += S * 8 * H;
-    QPSK_HIP_TRY(hipMemcpy(p, h->d_fll_delay, S * 8 * 2 * kFllTaps, hipMemcpyDeviceToHost));
-    return QPSK_OK;
+    std::memcpy(host_buf, &hd, sizeof(hd));
+    return copy_state(h, static_cast<char *>(host_buf), hipMemcpyDeviceToHost);
 }
 
 int qpsk_demod_set_state(qpsk_demod *h, const void *host_buf, int64_t buf_bytes) {
@@ -1556,17 +1486,8 @@ int qpsk_demod_set_state(qpsk_demod *h, const void *host_buf, int64_t buf_bytes)
     // on the host, before the handle is waited for or a byte is copied: a
     // rejected blob leaves the handle as it was
     if ((rc = qpsk_state_blob_check(&h->p, h->S, host_buf, buf_bytes))) return rc;
-    const int64_t S = h->S, H = h->T - 1;
-    const char *p = static_cast<const char *>(host_buf) + sizeof(StateHeader);
     if ((rc = handle_sync(h))) return rc;
-    QPSK_HIP_TRY(hipMemcpy(h->d_state, p, S * sizeof(StreamState), hipMemcpyHostToDevice));
-    p += S * sizeof(StreamState);
-    QPSK_HIP_TRY(hipMemcpy(h->d_carry, p, S * 8 * kCarryMax, hipMemcpyHostToDevice));
-    p += S * 8 * kCarryMax;
-    if (H > 0) QPSK_HIP_TRY(hipMemcpy(h->d_hist[h->hist_cur], p, S * 8 * H, hipMemcpyHostToDevice));
-    p += S * 8 * H;
-    QPSK_HIP_TRY(hipMemcpy(h->d_fll_delay, p, S * 8 * 2 * kFllTaps, hipMemcpyHostToDevice));
-    return QPSK_OK;
+    return copy_state(h, static_cast<char *>(const_cast<void *>(host_buf)), hipMemcpyHostToDevice);
 }
 
 int qpsk_demod_loop_shape(int32_t requested, int32_t n_streams, double sps, int32_t cus, int32_t rrc_taps,

@@ -31,20 +31,20 @@
 #include <vector>
 
 #include "qpsk_demod.h"
+#include "qpsk_device.h"
 #include "qpsk_internal.h"
 
 namespace {
 using qpsk::fail;
 
 struct Slot {
-    void *h_in = nullptr;       // pinned [S][in_stride] elements of the ring's format
-    void *d_in = nullptr;       // device [S][dev_stride]
-    uint8_t *d_bits = nullptr;  // device [S][bits_stride]
-    int64_t *d_nb = nullptr;    // device [S]
-    uint8_t *h_bits = nullptr;  // pinned
-    int64_t *h_nb = nullptr;    // pinned
-    hipEvent_t in_free = nullptr, out_done = nullptr;
-    bool in_rec = false, out_rec = false;
+    qpsk::PinnedBuf<char> h_in;      // [S][in_stride] elements of the ring's format
+    qpsk::DevBuf<char> d_in;         // [S][dev_stride]
+    qpsk::DevBuf<uint8_t> d_bits;    // [S][bits_stride]
+    qpsk::DevBuf<int64_t> d_nb;      // [S]
+    qpsk::PinnedBuf<uint8_t> h_bits;
+    qpsk::PinnedBuf<int64_t> h_nb;
+    qpsk::Event in_free, out_done;
     int64_t row_bytes = 0;      // bit bytes per row this chunk can hold
 };
 }  // namespace
@@ -60,46 +60,30 @@ struct qpsk_rx {
     size_t elem = sizeof(float);   // bytes per element of a slot
     int64_t bits_stride = 0;    // bytes
     int device = 0;
-    hipStream_t up = nullptr, down = nullptr;
+    qpsk::Stream up, down;      // in front of the slots, which go first
     std::vector<Slot> slots;
     int64_t submitted = 0, collected = 0;
 };
 
 namespace {
-void release(qpsk_rx *r) {
-    for (auto &s : r->slots) {
-        if (s.h_in) hipHostFree(s.h_in);
-        if (s.h_bits) hipHostFree(s.h_bits);
-        if (s.h_nb) hipHostFree(s.h_nb);
-        if (s.d_in) hipFree(s.d_in);
-        if (s.d_bits) hipFree(s.d_bits);
-        if (s.d_nb) hipFree(s.d_nb);
-        if (s.in_free) hipEventDestroy(s.in_free);
-        if (s.out_done) hipEventDestroy(s.out_done);
-    }
-    if (r->up) hipStreamDestroy(r->up);
-    if (r->down) hipStreamDestroy(r->down);
-    delete r;
-}
-
 int setup(qpsk_rx *r) {
     QPSK_HIP_TRY(hipSetDevice(r->device));
-    QPSK_HIP_TRY(hipStreamCreateWithFlags(&r->up, hipStreamNonBlocking));
-    QPSK_HIP_TRY(hipStreamCreateWithFlags(&r->down, hipStreamNonBlocking));
+    QPSK_HIP_TRY(r->up.create(hipStreamNonBlocking));
+    QPSK_HIP_TRY(r->down.create(hipStreamNonBlocking));
     const size_t S = static_cast<size_t>(r->S);
     const size_t in_bytes = S * static_cast<size_t>(r->in_stride) * r->elem;
     const size_t dev_bytes = S * static_cast<size_t>(r->dev_stride) * r->elem;
     const size_t bit_bytes = S * static_cast<size_t>(r->bits_stride);
     r->slots.resize(r->depth);
     for (auto &s : r->slots) {
-        QPSK_HIP_TRY(hipHostMalloc(&s.h_in, in_bytes));
-        QPSK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_bits), bit_bytes));
-        QPSK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_nb), S * sizeof(int64_t)));
-        QPSK_HIP_TRY(hipMalloc(&s.d_in, dev_bytes));
-        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_bits), bit_bytes));
-        QPSK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_nb), S * sizeof(int64_t)));
-        QPSK_HIP_TRY(hipEventCreateWithFlags(&s.in_free, hipEventDisableTiming));
-        QPSK_HIP_TRY(hipEventCreateWithFlags(&s.out_done, hipEventDisableTiming));
+        QPSK_HIP_TRY(s.h_in.alloc(in_bytes));
+        QPSK_HIP_TRY(s.h_bits.alloc(bit_bytes));
+        QPSK_HIP_TRY(s.h_nb.alloc(S));
+        QPSK_HIP_TRY(s.d_in.alloc(dev_bytes));
+        QPSK_HIP_TRY(s.d_bits.alloc(bit_bytes));
+        QPSK_HIP_TRY(s.d_nb.alloc(S));
+        QPSK_HIP_TRY(s.in_free.ensure());
+        QPSK_HIP_TRY(s.out_done.ensure());
     }
     return QPSK_OK;
 }
@@ -126,7 +110,7 @@ int create(qpsk_demod *h, int32_t depth, int32_t fmt, qpsk_rx **out) {
     int rc = setup(r);
     if (rc == QPSK_OK) rc = qpsk_demod_set_stream(h, r->up);
     if (rc != QPSK_OK) {
-        release(r);
+        delete r;
         return rc;
     }
     *out = r;
@@ -149,7 +133,7 @@ int next_slot(qpsk_rx *r, int32_t fmt, void **iq, int64_t *stride_floats) {
         return fail(QPSK_ERR_STATE, "every ring slot holds an uncollected chunk");
     Slot &sl = r->slots[r->submitted % r->depth];
     // the caller writes the slot next: its previous chunk must have been read
-    if (sl.in_rec) QPSK_HIP_TRY(hipEventSynchronize(sl.in_free));
+    QPSK_HIP_TRY(sl.in_free.sync());
     *iq = sl.h_in;
     if (stride_floats) *stride_floats = r->in_stride;
     return QPSK_OK;
@@ -179,34 +163,32 @@ int submit(qpsk_rx *r, int32_t fmt, const void *iq, int64_t stride_floats, int64
     // the slot's previous chunk: its input was consumed (front stage) and its
     // bits were downloaded before this chunk overwrites either (the back stage
     // of this chunk follows the upload through the handle's stream)
-    if (sl.in_rec) QPSK_HIP_TRY(hipEventSynchronize(sl.in_free));
-    if (n_call > 0 && iq != sl.h_in) {
+    QPSK_HIP_TRY(sl.in_free.sync());
+    if (n_call > 0 && iq != sl.h_in.get()) {
         for (int s = 0; s < S; ++s) {
             const int64_t len = lengths ? lengths[s] : n_call;
-            std::memcpy(static_cast<char *>(sl.h_in) + static_cast<int64_t>(s) * r->in_stride * r->elem,
+            std::memcpy(sl.h_in + static_cast<int64_t>(s) * r->in_stride * r->elem,
                         static_cast<const char *>(iq) + static_cast<int64_t>(s) * stride_floats * r->elem,
                         static_cast<size_t>(2 * len) * r->elem);
         }
     } else if (n_call > 0 && stride_floats != r->in_stride) {
         return fail(QPSK_ERR_ARGUMENT, "a ring slot has a stride of 2 * max_samples_per_call elements");
     }
-    if (sl.out_rec) QPSK_HIP_TRY(hipStreamWaitEvent(r->up, sl.out_done, 0));
+    QPSK_HIP_TRY(sl.out_done.wait(r->up));
     if (n_call > 0)
         QPSK_HIP_TRY(hipMemcpy2DAsync(sl.d_in, r->dev_stride * r->elem, sl.h_in, r->in_stride * r->elem,
                                       2 * n_call * r->elem, S, hipMemcpyHostToDevice, r->up));
     rc = qpsk_demod_process_async_fmt(r->h, fmt, QPSK_MODE_DEMODULATE, sl.d_in, r->dev_stride, n_samples, lengths,
                                       sl.d_bits, r->bits_stride, sl.d_nb, nullptr, 0, nullptr);
     if (rc != QPSK_OK) return rc;
-    QPSK_HIP_TRY(hipEventRecord(sl.in_free, qpsk::pipe_front_stream(r->h)));
-    sl.in_rec = true;
+    QPSK_HIP_TRY(sl.in_free.record(qpsk::pipe_front_stream(r->h)));
     if ((rc = qpsk_demod_pipeline_wait(r->h, r->down)) != QPSK_OK) return rc;
     sl.row_bytes = (2 * qpsk_demod_max_symbols(r->h, n_call) + 7) / 8;
     QPSK_HIP_TRY(hipMemcpyAsync(sl.h_nb, sl.d_nb, S * sizeof(int64_t), hipMemcpyDeviceToHost, r->down));
     if (sl.row_bytes > 0)
         QPSK_HIP_TRY(hipMemcpy2DAsync(sl.h_bits, r->bits_stride, sl.d_bits, r->bits_stride, sl.row_bytes, S,
                                       hipMemcpyDeviceToHost, r->down));
-    QPSK_HIP_TRY(hipEventRecord(sl.out_done, r->down));
-    sl.out_rec = true;
+    QPSK_HIP_TRY(sl.out_done.record(r->down));
     if (ticket) *ticket = r->submitted;
     ++r->submitted;
     return QPSK_OK;
@@ -250,7 +232,7 @@ int qpsk_rx_destroy(qpsk_rx *r) {
     hipStreamSynchronize(r->up);
     hipStreamSynchronize(r->down);
     const int rc = qpsk_demod_set_stream(r->h, nullptr);
-    release(r);
+    delete r;
     return rc;
 }
 
@@ -262,7 +244,7 @@ int qpsk_rx_collect(qpsk_rx *r, uint8_t *bits, int64_t bits_stride_bytes, int64_
     if (bits_stride_bytes < sl.row_bytes)
         return fail(QPSK_ERR_ARGUMENT, "bits_stride_bytes smaller than 2*max_symbols/8");
     QPSK_HIP_TRY(hipSetDevice(r->device));
-    QPSK_HIP_TRY(hipEventSynchronize(sl.out_done));
+    QPSK_HIP_TRY(sl.out_done.sync());
     for (int s = 0; s < r->S; ++s) {
         const int64_t nb = sl.h_nb[s];
         n_bits[s] = nb;

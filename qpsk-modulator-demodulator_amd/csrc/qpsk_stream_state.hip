@@ -80,19 +80,6 @@ __global__ __launch_bounds__(kRowsThreads) void stream_rows_kernel(const RowsArg
     if (MODE == kReset && a.link && lane < kLinkWords) a.link[s * kLinkWords + lane] = make_uint2(0u, 0u);
 }
 
-// the staging buffer holds at least need bytes afterwards (what it held is
-// dropped: every user of it has returned)
-int ensure_staging(const StreamRows &v, size_t need) {
-    if (need <= *v.staging_bytes) return QPSK_OK;
-    hipFree(*v.staging);
-    *v.staging = nullptr;
-    *v.staging_bytes = 0;
-    hipError_t e = hipMalloc(v.staging, need);
-    if (e != hipSuccess) return fail(QPSK_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    *v.staging_bytes = need;
-    return QPSK_OK;
-}
-
 // The listed rows in one launch on the handle's stream, which the call then
 // waits for.  host: the caller's sub-blob (read by scatter, written by gather).
 int move_rows(qpsk_demod *h, int mode, const int32_t *streams, int32_t n, void *host, int64_t bytes) {
@@ -101,8 +88,10 @@ int move_rows(qpsk_demod *h, int mode, const int32_t *streams, int32_t n, void *
     const StreamRows v = handle_rows(h);
     const size_t blob = mode == kReset ? 0 : static_cast<size_t>(bytes);
     const size_t list_bytes = static_cast<size_t>(n) * sizeof(int32_t);
-    if ((rc = ensure_staging(v, blob + list_bytes))) return rc;
-    char *stage = static_cast<char *>(*v.staging);
+    // what the staging buffer held is dropped: every user of it has returned
+    const hipError_t e = v.staging->grow(blob + list_bytes);
+    if (e != hipSuccess) return fail(QPSK_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
+    char *stage = *v.staging;
 
     RowsArgs a{};
     a.rows[0] = reinterpret_cast<uint2 *>(v.state);

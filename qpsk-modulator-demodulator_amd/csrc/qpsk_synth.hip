@@ -25,6 +25,7 @@
 
 #include "qpsk_demod.h"
 #include "qpsk_design.h"
+#include "qpsk_device.h"
 
 namespace {
 
@@ -144,8 +145,6 @@ __global__ void synth_samples_kernel(SynthArgs a, Pulse p) {
     o[1] = static_cast<float>(zi);
 }
 
-thread_local std::string g_synth_err;
-
 }  // namespace
 
 extern "C" {
@@ -218,13 +217,13 @@ int qpsk_synth_generate(const qpsk_synth_params *p, int32_t device, void *hip_st
     if (tx_bits_dev && bits_stride_bytes * 8 < 2 * a.nsym) return QPSK_ERR_ARGUMENT;
     if (hipSetDevice(device) != hipSuccess) return QPSK_ERR_DEVICE;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    if (hipMalloc(reinterpret_cast<void **>(&a.quad), static_cast<size_t>(n_streams) * a.nsym) != hipSuccess)
-        return QPSK_ERR_DEVICE;
+    qpsk::DevBuf<uint8_t> quad;   // freed on return, behind the wait for the kernels that use it
+    if (quad.alloc(static_cast<size_t>(n_streams) * a.nsym) != hipSuccess) return QPSK_ERR_DEVICE;
+    a.quad = quad;
     hipLaunchKernelGGL(synth_symbols_kernel, dim3((n_streams + 63) / 64), dim3(64), 0, st, a);
     dim3 grid(static_cast<unsigned>((n_samples + 255) / 256), static_cast<unsigned>(n_streams));
     hipLaunchKernelGGL(synth_samples_kernel, grid, dim3(256), 0, st, a, pulse);
     hipError_t e = hipStreamSynchronize(st);
-    hipFree(a.quad);
     return e == hipSuccess ? QPSK_OK : QPSK_ERR_DEVICE;
 }
 
