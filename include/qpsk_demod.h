@@ -738,6 +738,103 @@ int qpsk_tsc_find_device(const uint8_t *bits, int64_t bits_stride_bytes, const i
                          int32_t n_streams, const char *tsc, int64_t *offsets, void *hip_stream);
 
 /* ---------------------------------------------------------------------------
+ * Frames on the device (additive within ABI version 3): the receive loop of
+ * the reference calls DeModulateTextUtf8 on each buffer and looks only at the
+ * frame that comes back (ModDemodOverSDR.cs:136; DeModulateBytes,
+ * QPSKDeModulator.cs:169-259, behind the TSC strip, :412-422).  The three
+ * pieces below put that chain behind a qpsk_rx ring, so that a chunk returns
+ * the frames it completed and nothing else.
+ *
+ * qpsk_framer_dev_reset_streams: the framer half of `new QPSKDeModulator(...)`
+ * on the listed rows.  One launch writes the construction-time framer state
+ * (not in a frame, no lock offset, empty packer, empty ring, no carry bits)
+ * into them.  The list is checked first by qpsk_stream_list_check (a bad list
+ * changes nothing); the call is ordered on the framer's stream and returns
+ * when done.  n = 0 is QPSK_OK and does nothing.
+ */
+int qpsk_framer_dev_reset_streams(qpsk_framer_dev *f, const int32_t *streams, int32_t n);
+
+/* qpsk_frames_pack_device: the frames of one qpsk_framer_dev_push, packed
+ * densely.  Every pointer is device memory; the call is ordered on hip_stream
+ * (NULL = the null stream).  payload [n_streams][payload_stride] and n_payload
+ * are what qpsk_framer_dev_push wrote; P = payload_stride must be a multiple of
+ * 16 and > 0, C = packed_cap a multiple of 16 and >= 0, packed 16-byte
+ * aligned (NULL only with C = 0), offsets and head 8-byte aligned; anything
+ * else is QPSK_ERR_ARGUMENT and nothing is written.
+ *
+ * The packing rule, with L_s = n_payload[s]: k_s = min(L_s, P), a_s = k_s
+ * rounded up to 16, E_s = the sum of a_t over t < s (int64).  Stream s is
+ * stored iff k_s > 0 and E_s + a_s <= C.  offsets[s] = E_s if stored, else -1.
+ * A stored frame occupies packed[E_s .. E_s + a_s): its k_s bytes, then zeros.
+ * head[0] = the largest E_s + a_s over the stored streams, 0 if none: E_s
+ * counts the earlier frames whether stored or not, so once one frame does not
+ * fit no later one does, and packed[0 .. head[0]) is dense and fully written.
+ * head[1] = QPSK_FRAMES_TRUNCATED if some L_s > P, | QPSK_FRAMES_DROPPED if
+ * some frame with k_s > 0 was not stored for lack of capacity.
+ */
+#define QPSK_FRAMES_TRUNCATED 1
+#define QPSK_FRAMES_DROPPED 2
+int qpsk_frames_pack_device(const uint8_t *payload, int64_t payload_stride, const int64_t *n_payload,
+                            int32_t n_streams, uint8_t *packed, int64_t packed_cap, int64_t *offsets,
+                            int64_t *head, void *hip_stream);
+
+/* A framed ring.  qpsk_rx_attach_framer gives the ring a device framer of its
+ * own (qpsk_framer_dev_create's markers and ring_capacity, bound to the ring's
+ * download stream); allowed once per ring and only with no chunk outstanding,
+ * else QPSK_ERR_STATE.  tsc as in qpsk_tsc_find_device (NULL or blank = none).
+ * Entering a frame appends the rest of the chunk's bits to the framer's ring
+ * (QPSKDeModulator.cs:203-220), so a ring_capacity below one chunk's bit bytes
+ * drops every frame, as the reference does at that FrameBuffer size.
+ * max_frame_bytes (> 0, rounded up to 16) is the bytes of a frame the ring
+ * returns; chunk_frame_bytes (rounded up to 16; 0 = n_streams *
+ * max_frame_bytes) the bytes of frames one chunk can return, as
+ * qpsk_rx_frames_bytes reports it (0 for a ring without a framer).  From then
+ * on every submit queues, behind the chunk's DeModulate and on the download
+ * stream: qpsk_tsc_find_device, qpsk_framer_dev_push, qpsk_frames_pack_device,
+ * the download of the index (lengths, offsets, head) and, only with keep_bits
+ * != 0, the download of the bits.  Chunk k + 1's framer step follows chunk
+ * k's, the order DeModulateBytes needs.  A ring without a framer is what it
+ * was.
+ *
+ * qpsk_rx_collect_frames waits for the oldest outstanding chunk, fetches
+ * exactly head[0] packed bytes (on a stream of its own, which never waits for
+ * a later chunk) and fills: frame_len[s] = the length of the array
+ * DeModulateBytes returned for this buffer on stream s (0 = none, as in
+ * qpsk_framer_dev_push); frame_offset[s] = the offset in `frames` of its first
+ * byte, a multiple of 16, or -1 (no frame, or dropped); min(frame_len[s],
+ * max_frame_bytes) bytes are present.  A buffer of qpsk_rx_frames_bytes bytes
+ * always suffices; frames_cap smaller than head[0] is QPSK_ERR_ARGUMENT and
+ * the chunk stays outstanding.  bits / n_bits (as in qpsk_rx_collect) may both
+ * be NULL; non-NULL on a keep_bits = 0 ring is QPSK_ERR_STATE.  When head[1]
+ * != 0 (a frame truncated or dropped) it returns QPSK_ERR_CAPACITY with the
+ * outputs written and the chunk consumed, as the host process calls do.  A
+ * rejected call neither waits nor fetches (frames_cap alone is known only
+ * after the wait).  QPSK_ERR_STATE on a ring without a framer.
+ *
+ * qpsk_rx_collect on a framed ring: with keep_bits it works as before (the
+ * chunk's frames are dropped; the framer state has advanced); with keep_bits
+ * = 0 it returns QPSK_ERR_STATE.
+ *
+ * qpsk_rx_set_markers: markers are per-call arguments of DeModulateBytes; the
+ * new pair applies to later submits.  It waits for the framer work already
+ * queued.  qpsk_rx_reset_streams: `new QPSKDeModulator(...)` on the listed
+ * rows of the ring, between submits: it waits for the outstanding chunks'
+ * framer work, then qpsk_demod_reset_streams on the handle and
+ * qpsk_framer_dev_reset_streams on the framer (the handle alone on a ring
+ * without a framer).  A bad list changes neither; n = 0 does nothing.
+ * qpsk_rx_destroy also destroys the framer.
+ */
+int qpsk_rx_attach_framer(qpsk_rx *r, const uint8_t *start, int32_t n_start, const uint8_t *end, int32_t n_end,
+                          const char *tsc, int64_t ring_capacity, int64_t max_frame_bytes,
+                          int64_t chunk_frame_bytes, int32_t keep_bits);
+int qpsk_rx_set_markers(qpsk_rx *r, const uint8_t *start, int32_t n_start, const uint8_t *end, int32_t n_end);
+int64_t qpsk_rx_frames_bytes(const qpsk_rx *r);
+int qpsk_rx_collect_frames(qpsk_rx *r, uint8_t *frames, int64_t frames_cap, int64_t *frame_offset,
+                           int64_t *frame_len, uint8_t *bits, int64_t bits_stride_bytes, int64_t *n_bits,
+                           int64_t *ticket);
+int qpsk_rx_reset_streams(qpsk_rx *r, const int32_t *streams, int32_t n);
+
+/* ---------------------------------------------------------------------------
  * Synthetic batched input (QPSKModulator.Modulate + the test bench channel),
  * generated in device memory.  Stream s draws its payload from
  * splitmix64(seed ^ s); tx_bits receives the payload bits (packed MSB-first).

@@ -444,6 +444,13 @@ tsc_find_kernel(const uint8_t *bits, int64_t stride, const int64_t *n_bits, TscP
     if (threadIdx.x == 0) offsets[s] = best == ULLONG_MAX ? -1 : static_cast<int64_t>(best) + m;
 }
 
+// `new QPSKDeModulator(...)` on the listed rows: the framer fields as
+// qpsk_framer_dev_create leaves them (an empty ring, no carry, not in a frame)
+__global__ void framer_reset_rows_kernel(FrState *st, const int32_t *rows, int32_t n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) st[rows[i]] = FrState{0, -1, 0, 0, 0, 0};
+}
+
 using qpsk::fail;
 
 }  // namespace
@@ -461,6 +468,7 @@ struct qpsk_framer_dev {
     int64_t ring_cap = kRefRing;
     qpsk::DevBuf<uint8_t> markers;   // start bytes then end bytes
     int32_t ns = 0, ne = 0;
+    qpsk::DevBuf<int32_t> rows;      // the list of a reset_streams call
 
     ~qpsk_framer_dev() {
         if (stream) hipStreamSynchronize(stream);
@@ -598,6 +606,24 @@ int qpsk_framer_dev_status(const qpsk_framer_dev *f, int32_t *in_frame, int64_t 
         if (ring_count) ring_count[s] = h[s].count;
         if (carry_bits) carry_bits[s] = h[s].carry_bits;
     }
+    return QPSK_OK;
+}
+
+int qpsk_framer_dev_reset_streams(qpsk_framer_dev *f, const int32_t *streams, int32_t n) {
+    if (!f) return fail(QPSK_ERR_ARGUMENT_NULL, "null framer");
+    if (n == 0) return QPSK_OK;
+    int rc;
+    if ((rc = qpsk_stream_list_check(f->n_streams, streams, n))) return rc;
+    QPSK_HIP_TRY(hipSetDevice(f->device));
+    if (f->rows.bytes() < sizeof(int32_t) * n) {
+        QPSK_HIP_TRY(hipStreamSynchronize(f->stream));           // an earlier reset may still read the list
+        QPSK_HIP_TRY(f->rows.grow(sizeof(int32_t) * f->n_streams));
+    }
+    QPSK_HIP_TRY(hipMemcpyAsync(f->rows, streams, sizeof(int32_t) * n, hipMemcpyHostToDevice, f->stream));
+    hipLaunchKernelGGL(framer_reset_rows_kernel, dim3((n + kFrThreads - 1) / kFrThreads), dim3(kFrThreads), 0,
+                       f->stream, f->st.get(), f->rows.get(), n);
+    QPSK_HIP_TRY(hipGetLastError());
+    QPSK_HIP_TRY(hipStreamSynchronize(f->stream));               // pageable source outlives the copy
     return QPSK_OK;
 }
 

@@ -24,9 +24,21 @@
 // ring (qpsk_rx_create_fmt) has byte slots, 2 bytes a sample; its device
 // slots' rows are pitched to 8 samples so the matched filter reads them with
 // 16-byte loads whatever max_samples_per_call is.
+//
+// A framed ring (qpsk_rx_attach_framer) owns a device framer and returns what
+// the reference's loop looks at, DeModulateBytes' frames (ModDemodOverSDR.cs:136):
+//
+//   submit k:  download stream : wait(back stage) -> TSC search -> framer step
+//              -> pack the completed frames -> D2H index [-> D2H bits] -> out_done[slot]
+//   collect_frames: wait out_done, D2H exactly head[0] packed bytes on the
+//              fetch stream (the download stream may hold chunk k+1 already)
+//
+// The framer's state passes from chunk to chunk in submit order because every
+// chunk's framer step is queued on the one download stream.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -46,6 +58,29 @@ struct Slot {
     qpsk::PinnedBuf<int64_t> h_nb;
     qpsk::Event in_free, out_done;
     int64_t row_bytes = 0;      // bit bytes per row this chunk can hold
+    // a framed ring (qpsk_rx_attach_framer)
+    qpsk::DevBuf<uint8_t> d_packed;     // [chunk_frame_bytes] the chunk's frames, packed
+    qpsk::PinnedBuf<uint8_t> h_packed;
+    qpsk::PinnedBuf<int64_t> h_index;   // frame_len[S], offsets[S], head[2]
+};
+
+// The device framer behind a framed ring.  The payload rows, the TSC offsets
+// and the index are shared by the slots: a framer's chunks are serial on the
+// download stream, and each chunk's index is copied to its slot's pinned
+// memory before the next chunk's framer step runs.
+struct Framed {
+    qpsk_framer_dev *fr = nullptr;
+    std::string tsc;
+    int64_t P = 0;                      // max_frame_bytes, a multiple of 16
+    int64_t C = 0;                      // chunk_frame_bytes, a multiple of 16
+    bool keep_bits = false;
+    qpsk::Stream fetch;                 // collect_frames' D2H: no chunk's work is ever queued on it
+    qpsk::DevBuf<uint8_t> rows;         // [S][P]
+    qpsk::DevBuf<int64_t> tsc_off;      // [S]
+    qpsk::DevBuf<int64_t> index;        // frame_len[S], offsets[S], head[2]
+    ~Framed() {
+        if (fr) qpsk_framer_dev_destroy(fr);
+    }
 };
 }  // namespace
 
@@ -63,6 +98,7 @@ struct qpsk_rx {
     qpsk::Stream up, down;      // in front of the slots, which go first
     std::vector<Slot> slots;
     int64_t submitted = 0, collected = 0;
+    std::unique_ptr<Framed> fr;     // behind the streams and the slots: it goes first
 };
 
 namespace {
@@ -89,6 +125,18 @@ int setup(qpsk_rx *r) {
 }
 
 const char *kUnknownFormat = "unknown sample format";
+const char *kNoFramer = "the ring has no framer (qpsk_rx_attach_framer)";
+const char *kNoBits = "the ring's framer keeps no bits (keep_bits = 0)";
+
+// the collected chunk's bit rows and counts, from the slot's pinned memory
+void copy_bits(const qpsk_rx *r, const Slot &sl, uint8_t *bits, int64_t bits_stride_bytes, int64_t *n_bits) {
+    for (int s = 0; s < r->S; ++s) {
+        const int64_t nb = sl.h_nb[s];
+        n_bits[s] = nb;
+        std::memcpy(bits + static_cast<int64_t>(s) * bits_stride_bytes, sl.h_bits + static_cast<int64_t>(s) * r->bits_stride,
+                    static_cast<size_t>((nb + 7) / 8));
+    }
+}
 
 int create(qpsk_demod *h, int32_t depth, int32_t fmt, qpsk_rx **out) {
     if (!h || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
@@ -184,10 +232,24 @@ int submit(qpsk_rx *r, int32_t fmt, const void *iq, int64_t stride_floats, int64
     QPSK_HIP_TRY(sl.in_free.record(qpsk::pipe_front_stream(r->h)));
     if ((rc = qpsk_demod_pipeline_wait(r->h, r->down)) != QPSK_OK) return rc;
     sl.row_bytes = (2 * qpsk_demod_max_symbols(r->h, n_call) + 7) / 8;
-    QPSK_HIP_TRY(hipMemcpyAsync(sl.h_nb, sl.d_nb, S * sizeof(int64_t), hipMemcpyDeviceToHost, r->down));
-    if (sl.row_bytes > 0)
-        QPSK_HIP_TRY(hipMemcpy2DAsync(sl.h_bits, r->bits_stride, sl.d_bits, r->bits_stride, sl.row_bytes, S,
-                                      hipMemcpyDeviceToHost, r->down));
+    if (Framed *f = r->fr.get()) {
+        // one DeModulateBytes step behind the chunk's bits, on the download
+        // stream: chunk k + 1's step follows chunk k's, the order the framer's
+        // state needs.  The frames stay on the device until collect_frames.
+        int64_t *len = f->index, *offsets = f->index + S, *head = f->index + 2 * S;
+        if ((rc = qpsk_tsc_find_device(sl.d_bits, r->bits_stride, sl.d_nb, S, f->tsc.empty() ? nullptr : f->tsc.c_str(),
+                                       f->tsc_off, r->down)) ||
+            (rc = qpsk_framer_dev_push(f->fr, sl.d_bits, r->bits_stride, f->tsc_off, sl.d_nb, f->rows, f->P, len)) ||
+            (rc = qpsk_frames_pack_device(f->rows, f->P, len, S, sl.d_packed, f->C, offsets, head, r->down)))
+            return rc;
+        QPSK_HIP_TRY(hipMemcpyAsync(sl.h_index, f->index, (2 * S + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, r->down));
+    }
+    if (!r->fr || r->fr->keep_bits) {
+        QPSK_HIP_TRY(hipMemcpyAsync(sl.h_nb, sl.d_nb, S * sizeof(int64_t), hipMemcpyDeviceToHost, r->down));
+        if (sl.row_bytes > 0)
+            QPSK_HIP_TRY(hipMemcpy2DAsync(sl.h_bits, r->bits_stride, sl.d_bits, r->bits_stride, sl.row_bytes, S,
+                                          hipMemcpyDeviceToHost, r->down));
+    }
     QPSK_HIP_TRY(sl.out_done.record(r->down));
     if (ticket) *ticket = r->submitted;
     ++r->submitted;
@@ -239,21 +301,115 @@ int qpsk_rx_destroy(qpsk_rx *r) {
 int qpsk_rx_collect(qpsk_rx *r, uint8_t *bits, int64_t bits_stride_bytes, int64_t *n_bits,
                     int64_t *ticket) {
     if (!r || !bits || !n_bits) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    if (r->fr && !r->fr->keep_bits) return fail(QPSK_ERR_STATE, kNoBits);
     if (r->collected == r->submitted) return fail(QPSK_ERR_STATE, "no chunk outstanding");
     Slot &sl = r->slots[r->collected % r->depth];
     if (bits_stride_bytes < sl.row_bytes)
         return fail(QPSK_ERR_ARGUMENT, "bits_stride_bytes smaller than 2*max_symbols/8");
     QPSK_HIP_TRY(hipSetDevice(r->device));
     QPSK_HIP_TRY(sl.out_done.sync());
-    for (int s = 0; s < r->S; ++s) {
-        const int64_t nb = sl.h_nb[s];
-        n_bits[s] = nb;
-        std::memcpy(bits + static_cast<int64_t>(s) * bits_stride_bytes, sl.h_bits + static_cast<int64_t>(s) * r->bits_stride,
-                    static_cast<size_t>((nb + 7) / 8));
-    }
+    copy_bits(r, sl, bits, bits_stride_bytes, n_bits);
     if (ticket) *ticket = r->collected;
     ++r->collected;
     return QPSK_OK;
+}
+
+int qpsk_rx_attach_framer(qpsk_rx *r, const uint8_t *start, int32_t n_start, const uint8_t *end, int32_t n_end,
+                          const char *tsc, int64_t ring_capacity, int64_t max_frame_bytes,
+                          int64_t chunk_frame_bytes, int32_t keep_bits) {
+    if (!r || !start || !end) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    if (max_frame_bytes <= 0) return fail(QPSK_ERR_ARGUMENT, "max_frame_bytes must be positive");
+    if (chunk_frame_bytes < 0) return fail(QPSK_ERR_ARGUMENT, "chunk_frame_bytes must not be negative");
+    if (r->fr) return fail(QPSK_ERR_STATE, "the ring has a framer already");
+    if (r->collected != r->submitted) return fail(QPSK_ERR_STATE, "attach a framer with no chunk outstanding");
+    const size_t S = static_cast<size_t>(r->S);
+    std::unique_ptr<Framed> f(new Framed);
+    f->P = (max_frame_bytes + 15) / 16 * 16;
+    f->C = chunk_frame_bytes ? (chunk_frame_bytes + 15) / 16 * 16 : static_cast<int64_t>(S) * f->P;
+    f->keep_bits = keep_bits != 0;
+    if (tsc) f->tsc = tsc;
+    int rc = qpsk_framer_dev_create(r->S, start, n_start, end, n_end, ring_capacity, r->device, &f->fr);
+    if (rc == QPSK_OK) rc = qpsk_framer_dev_set_stream(f->fr, r->down);
+    if (rc != QPSK_OK) return rc;
+    QPSK_HIP_TRY(hipSetDevice(r->device));
+    QPSK_HIP_TRY(f->fetch.create(hipStreamNonBlocking));
+    QPSK_HIP_TRY(f->rows.alloc(S * static_cast<size_t>(f->P)));
+    QPSK_HIP_TRY(f->tsc_off.alloc(S));
+    QPSK_HIP_TRY(f->index.alloc(2 * S + 2));
+    // packed buffers of their own, so that a failed attach leaves the slots as they were
+    std::vector<qpsk::DevBuf<uint8_t>> d_packed(r->depth);
+    std::vector<qpsk::PinnedBuf<uint8_t>> h_packed(r->depth);
+    std::vector<qpsk::PinnedBuf<int64_t>> h_index(r->depth);
+    for (int k = 0; k < r->depth; ++k) {
+        QPSK_HIP_TRY(d_packed[k].alloc(static_cast<size_t>(f->C)));
+        QPSK_HIP_TRY(h_packed[k].alloc(static_cast<size_t>(f->C)));
+        QPSK_HIP_TRY(h_index[k].alloc(2 * S + 2));
+    }
+    for (int k = 0; k < r->depth; ++k) {
+        r->slots[k].d_packed.swap(d_packed[k]);
+        r->slots[k].h_packed.swap(h_packed[k]);
+        r->slots[k].h_index.swap(h_index[k]);
+    }
+    r->fr = std::move(f);
+    return QPSK_OK;
+}
+
+int qpsk_rx_set_markers(qpsk_rx *r, const uint8_t *start, int32_t n_start, const uint8_t *end, int32_t n_end) {
+    if (!r || !start || !end) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    if (!r->fr) return fail(QPSK_ERR_STATE, kNoFramer);
+    return qpsk_framer_dev_set_markers(r->fr->fr, start, n_start, end, n_end);
+}
+
+int64_t qpsk_rx_frames_bytes(const qpsk_rx *r) { return r && r->fr ? r->fr->C : 0; }
+
+int qpsk_rx_collect_frames(qpsk_rx *r, uint8_t *frames, int64_t frames_cap, int64_t *frame_offset,
+                           int64_t *frame_len, uint8_t *bits, int64_t bits_stride_bytes, int64_t *n_bits,
+                           int64_t *ticket) {
+    if (!r || !frames || !frame_offset || !frame_len) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    if (!r->fr) return fail(QPSK_ERR_STATE, kNoFramer);
+    if ((bits || n_bits) && !r->fr->keep_bits) return fail(QPSK_ERR_STATE, kNoBits);
+    if (!bits != !n_bits) return fail(QPSK_ERR_ARGUMENT_NULL, "bits and n_bits go together");
+    if (r->collected == r->submitted) return fail(QPSK_ERR_STATE, "no chunk outstanding");
+    Slot &sl = r->slots[r->collected % r->depth];
+    if (bits && bits_stride_bytes < sl.row_bytes)
+        return fail(QPSK_ERR_ARGUMENT, "bits_stride_bytes smaller than 2*max_symbols/8");
+    QPSK_HIP_TRY(hipSetDevice(r->device));
+    QPSK_HIP_TRY(sl.out_done.sync());
+    const int S = r->S;
+    const int64_t total = sl.h_index[2 * S], flags = sl.h_index[2 * S + 1];
+    if (frames_cap < total)
+        return fail(QPSK_ERR_ARGUMENT, "frames_cap smaller than the chunk's frames (" + std::to_string(total) + " bytes)");
+    if (total > 0) {
+        // exactly the frames' bytes, on a stream of their own: the download
+        // stream may hold the next chunks' work already
+        QPSK_HIP_TRY(hipMemcpyAsync(sl.h_packed, sl.d_packed, static_cast<size_t>(total), hipMemcpyDeviceToHost,
+                                    r->fr->fetch));
+        QPSK_HIP_TRY(hipStreamSynchronize(r->fr->fetch));
+        std::memcpy(frames, sl.h_packed, static_cast<size_t>(total));
+    }
+    std::memcpy(frame_len, sl.h_index, S * sizeof(int64_t));
+    std::memcpy(frame_offset, sl.h_index + S, S * sizeof(int64_t));
+    if (bits) copy_bits(r, sl, bits, bits_stride_bytes, n_bits);
+    if (ticket) *ticket = r->collected;
+    ++r->collected;
+    if (flags)
+        return fail(QPSK_ERR_CAPACITY, (flags & QPSK_FRAMES_TRUNCATED)
+                                           ? "a frame is longer than max_frame_bytes (truncated)"
+                                           : "the chunk's frames exceed chunk_frame_bytes (dropped)");
+    return QPSK_OK;
+}
+
+int qpsk_rx_reset_streams(qpsk_rx *r, const int32_t *streams, int32_t n) {
+    if (!r) return fail(QPSK_ERR_ARGUMENT_NULL, "null ring");
+    if (n == 0) return QPSK_OK;
+    int rc;
+    if ((rc = qpsk_stream_list_check(r->S, streams, n))) return rc;
+    QPSK_HIP_TRY(hipSetDevice(r->device));
+    // the outstanding chunks' framer steps have run before a row is rewritten
+    // (the handle's reset waits for its own queued calls)
+    QPSK_HIP_TRY(hipStreamSynchronize(r->down));
+    if ((rc = qpsk_demod_reset_streams(r->h, streams, n))) return rc;
+    return r->fr ? qpsk_framer_dev_reset_streams(r->fr->fr, streams, n) : QPSK_OK;
 }
 
 }  // extern "C"

@@ -33,6 +33,9 @@ QPSK_ERR_OUT_OF_RANGE = -3
 QPSK_ERR_DEVICE = -4
 QPSK_ERR_CAPACITY = -5
 QPSK_ERR_STATE = -6
+# head[1] of qpsk_frames_pack_device, and the flags HostRing.collect_frames returns
+FRAMES_TRUNCATED = 1          # a frame longer than the payload row (max_frame_bytes)
+FRAMES_DROPPED = 2            # a frame not stored for lack of capacity (chunk_frame_bytes)
 STATUS_CARRY_OVERFLOW = 1
 STATUS_OUTPUT_TRUNCATED = 2
 STATUS_NONFINITE_TIMING = 4
@@ -281,6 +284,9 @@ def lib():
     L.qpsk_framer_dev_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.qpsk_tsc_find_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_char_p,
                                        C.c_void_p, C.c_void_p]
+    L.qpsk_framer_dev_reset_streams.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    L.qpsk_frames_pack_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
     L.qpsk_synth_params_init.argtypes = [C.POINTER(SynthParams), C.c_int32, C.c_int32]
     L.qpsk_synth_generate.argtypes = [C.POINTER(SynthParams), C.c_int32, C.c_void_p, C.c_int32,
                                       C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
@@ -296,6 +302,15 @@ def lib():
     L.qpsk_rx_create_fmt.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.qpsk_rx_next_slot_fmt.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.qpsk_rx_submit_fmt.argtypes = [C.c_void_p, C.c_int32] + L.qpsk_rx_submit.argtypes[1:]
+    # a framed ring: the chunk's completed frames instead of its bits
+    L.qpsk_rx_attach_framer.argtypes = [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, C.c_char_p, C.c_int64,
+                                        C.c_int64, C.c_int64, C.c_int32]
+    L.qpsk_rx_set_markers.argtypes = [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32]
+    L.qpsk_rx_frames_bytes.argtypes = [C.c_void_p]
+    L.qpsk_rx_frames_bytes.restype = C.c_int64
+    L.qpsk_rx_collect_frames.argtypes = [C.c_void_p, _u8p, C.c_int64, _i64p, _i64p, _u8p, C.c_int64, _i64p,
+                                         C.POINTER(C.c_int64)]
+    L.qpsk_rx_reset_streams.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     L.qpsk_shard_streams.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32)]
     L.qpsk_demod_group_create.argtypes = [C.POINTER(DemodParams), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
@@ -366,6 +381,8 @@ EXPORTED_SYMBOLS = [
     "qpsk_demod_reset_streams", "qpsk_demod_streams_state_bytes", "qpsk_demod_get_streams_state",
     "qpsk_demod_set_streams_state", "qpsk_demod_group_reset_streams", "qpsk_demod_group_streams_state_bytes",
     "qpsk_demod_group_get_streams_state", "qpsk_demod_group_set_streams_state",
+    "qpsk_framer_dev_reset_streams", "qpsk_frames_pack_device", "qpsk_rx_attach_framer", "qpsk_rx_set_markers",
+    "qpsk_rx_frames_bytes", "qpsk_rx_collect_frames", "qpsk_rx_reset_streams",
 ]
 
 _EXC = {
@@ -1076,6 +1093,74 @@ class HostRing:
                                      nb.ctypes.data_as(_i64p), C.byref(t)))
         return bits, nb, t.value
 
+    def attach_framer(self, start: bytes, end: bytes, tsc: str | None = None, ring_capacity=1 << 16,
+                      max_frame_bytes=256, chunk_frame_bytes=0, keep_bits=False):
+        """Give the ring a device framer (qpsk_rx_attach_framer): from now on
+        every chunk's bits go through the TSC strip, the DeModulateBytes state
+        machine (markers start / end, ring_capacity bytes a stream) and the
+        packing kernel on the device, and collect_frames() returns the frames
+        the chunk completed.  max_frame_bytes: the bytes of a frame that come
+        back (longer ones are truncated and flagged); chunk_frame_bytes: the
+        bytes of frames one chunk returns (0: n_streams * max_frame_bytes).
+        keep_bits=False queues no bit download at all.  ring_capacity must hold
+        one chunk's bit bytes (entering a frame appends the rest of the chunk's
+        bits; the default suits chunks of up to 2^20 samples at sps 4).  Once
+        per ring, with nothing outstanding (QPSKError otherwise)."""
+        s, e = _markers(start, end)
+        _check(lib().qpsk_rx_attach_framer(self._r, s.ctypes.data_as(_u8p), s.size, e.ctypes.data_as(_u8p), e.size,
+                                           tsc.encode() if tsc else None, int(ring_capacity), int(max_frame_bytes),
+                                           int(chunk_frame_bytes), 1 if keep_bits else 0))
+        self.max_frame_bytes = (int(max_frame_bytes) + 15) // 16 * 16
+        self.keep_bits = bool(keep_bits)
+
+    def frames_bytes(self) -> int:
+        """The bytes of frames one chunk can return (0: no framer attached)."""
+        return int(lib().qpsk_rx_frames_bytes(self._r))
+
+    def set_markers(self, start: bytes, end: bytes):
+        """The markers of later submits (DeModulateBytes takes them per call);
+        waits for the framer work already queued."""
+        s, e = _markers(start, end)
+        _check(lib().qpsk_rx_set_markers(self._r, s.ctypes.data_as(_u8p), s.size, e.ctypes.data_as(_u8p), e.size))
+
+    def collect_frames(self, want_bits=False, frames_cap=None):
+        """The oldest outstanding chunk of a framed ring: (frames, lengths,
+        flags, ticket).  frames[s] is the frame DeModulateBytes returned on
+        stream s for this chunk (its first max_frame_bytes bytes), or None;
+        lengths (S,) int64 the frames' full lengths (0 = none); flags the OR
+        of FRAMES_TRUNCATED and FRAMES_DROPPED (a dropped frame has a length
+        and None for its bytes).  want_bits (a keep_bits ring): the chunk's
+        (bits, n_bits) as collect() returns them follow the ticket.
+        frames_cap: the size of the buffer handed to the library (default
+        frames_bytes(), which always suffices)."""
+        cap = self.frames_bytes() if frames_cap is None else int(frames_cap)
+        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+        off = np.zeros(self.S, dtype=np.int64)
+        lens = np.zeros(self.S, dtype=np.int64)
+        bits = np.zeros((self.S, self.bits_stride), dtype=np.uint8) if want_bits else None
+        nb = np.zeros(self.S, dtype=np.int64) if want_bits else None
+        t = C.c_int64()
+        rc = lib().qpsk_rx_collect_frames(self._r, buf.ctypes.data_as(_u8p), cap, off.ctypes.data_as(_i64p),
+                                          lens.ctypes.data_as(_i64p),
+                                          bits.ctypes.data_as(_u8p) if want_bits else None, self.bits_stride,
+                                          nb.ctypes.data_as(_i64p) if want_bits else None, C.byref(t))
+        if rc != QPSK_ERR_CAPACITY:     # a flagged chunk is consumed and its outputs are written
+            _check(rc)
+        P = getattr(self, "max_frame_bytes", 0)
+        frames = [bytes(buf[int(off[s]): int(off[s]) + min(int(lens[s]), P)]) if off[s] >= 0 else None
+                  for s in range(self.S)]
+        flags = (FRAMES_TRUNCATED if (lens > P).any() else 0) | \
+                (FRAMES_DROPPED if ((lens > 0) & (off < 0)).any() else 0)
+        assert (rc == QPSK_ERR_CAPACITY) == bool(flags)
+        return (frames, lens, flags, t.value) + ((bits, nb) if want_bits else ())
+
+    def reset_streams(self, streams):
+        """`new QPSKDeModulator(...)` on the listed rows between submits: the
+        handle's rows (BatchDemodulator.reset_streams) and the framer's.  Waits
+        for the outstanding chunks' work.  An empty list does nothing."""
+        ids, n = _stream_list(streams)
+        _check(lib().qpsk_rx_reset_streams(self._r, ids, n))
+
     def close(self):
         if getattr(self, "_r", None):
             _check(lib().qpsk_rx_destroy(self._r))
@@ -1169,6 +1254,19 @@ def tsc_find_device(bits_dev, n_bits_dev, tsc: str | None, offsets_dev, hip_stre
         hip_stream))
 
 
+def frames_pack_device(payload_dev, n_payload_dev, packed_dev, offsets_dev, head_dev, hip_stream=None,
+                       packed_cap=None):
+    """qpsk_frames_pack_device on torch CUDA tensors: the frames DeviceFramer.push
+    left in payload_dev [S][P] / n_payload_dev [S], packed densely at 16-byte
+    offsets into packed_dev (uint8, packed_cap bytes of it, default all);
+    offsets_dev [S] int64 receives each frame's offset or -1, head_dev [2]
+    int64 the bytes used and the FRAMES_* flags.  Ordered on hip_stream."""
+    cap = packed_dev.numel() if packed_cap is None else int(packed_cap)
+    _check(lib().qpsk_frames_pack_device(payload_dev.data_ptr(), payload_dev.stride(0), n_payload_dev.data_ptr(),
+                                         int(payload_dev.shape[0]), packed_dev.data_ptr(), cap,
+                                         offsets_dev.data_ptr(), head_dev.data_ptr(), hip_stream))
+
+
 class DeviceFramer:
     """The DeModulateBytes framer (QPSKDeModulator.cs:169-259) resident on the
     GPU: fed straight from BatchDemodulator.process_device's bit rows."""
@@ -1197,6 +1295,12 @@ class DeviceFramer:
             self._h, bits_dev.data_ptr(), bits_dev.stride(0) * bits_dev.element_size(),
             offsets_dev.data_ptr() if offsets_dev is not None else None, n_bits_dev.data_ptr(),
             payload_dev.data_ptr(), payload_dev.stride(0), n_payload_dev.data_ptr()))
+
+    def reset_streams(self, streams):
+        """The listed rows go back to construction (qpsk_framer_dev_reset_streams):
+        not in a frame, empty ring, no carry.  An empty list does nothing."""
+        ids, n = _stream_list(streams)
+        _check(lib().qpsk_framer_dev_reset_streams(self._h, ids, n))
 
     def status(self):
         inf = np.zeros(self.S, np.int32)
