@@ -907,6 +907,73 @@ int qpsk_mod_modulate_bytes(qpsk_mod *m, int32_t n_streams, const uint8_t *paylo
                             const uint8_t *end_marker, int32_t n_end, int32_t pulse_shaping, float *out,
                             int64_t out_stride_floats, int64_t *n_out_floats);
 
+/* ---------------------------------------------------------------------------
+ * The modulator's output in a radio's own sample format.  The transmit half of
+ * the reference program (ModDemodOverSDR.cs:87-111: ModulateTextUtf8, then
+ * txStream.Write) hands the driver floats; a device that takes CS16 or CS8
+ * wants integers, and the reference's own integer writer is SaveAsCs16
+ * (HelperFunctions.cs:75-106).  x is a float component of the modulator's
+ * output; full = 32767 (CS16) or 127 (CS8, CU8); [lo, hi] = [-32768, 32767]
+ * or [-128, 127].
+ *
+ *   QPSK_MOD_NORM_FIXED  v = x * scale, one float multiply rounded once;
+ *       clamp v to [lo, hi] (+-inf saturate); truncate toward zero: the
+ *       reference's (short)Math.Max(short.MinValue, Math.Min(short.MaxValue,
+ *       ...)) (HelperFunctions.cs:97-101).  CU8 stores the CS8 value + 128.
+ *       CF32 stores v itself, so scale 1.0f gives the bits of
+ *       qpsk_mod_modulate.  scale must be finite and > 0, else
+ *       QPSK_ERR_OUT_OF_RANGE.  peak may be NULL and is not written.
+ *   QPSK_MOD_NORM_PEAK   SaveAsCs16 per row, in double as there:
+ *       (double)x / maxVal * (double)full, a division and then a
+ *       multiplication (:97-98), clamped and truncated as above.  maxVal is
+ *       the largest |component| of the row's whole output (:82-86), replaced
+ *       by 1.0 when < 1e-12 (:88), so the peak sample stores exactly +-full.
+ *       scale is ignored.  peak[s] (required) receives the row's largest
+ *       |component| as found, a float: 0 for an empty row.  With
+ *       QPSK_FMT_CF32 it is QPSK_ERR_ARGUMENT.
+ *
+ * qpsk_quantise_iq applies the rules to one row of n_floats host floats (needs
+ * no device); the modulator's kernels share its arithmetic
+ * (csrc/qpsk_quantise.h) and equal it element for element.  A rejected call
+ * writes nothing.
+ */
+#define QPSK_MOD_NORM_FIXED 0
+#define QPSK_MOD_NORM_PEAK 1
+int qpsk_quantise_iq(int32_t fmt, int32_t norm, float scale, const float *iq, int64_t n_floats, void *out,
+                     float *peak);
+/* Output samples one workgroup of the sample kernel covers, and dibits one
+ * pass of the symbol kernel's scan covers: the row lengths at which the
+ * kernels change blocks (tests/test_gpu_mod_fmt.py spans them). */
+#define QPSK_MOD_TILE_SAMPLES 512
+#define QPSK_MOD_SCAN_DIBITS 1024
+/* qpsk_mod_modulate / qpsk_mod_modulate_bytes with the output in fmt
+ * (QPSK_FMT_*; unknown: QPSK_ERR_ARGUMENT): out is [n_streams][out_stride_elems]
+ * floats, int16 or bytes, n_out_elems[s] = 2 x the row's complex samples (what
+ * qpsk_mod_output_floats returns, the same in every format).  mem covers bits /
+ * payload, their counts, out, n_out_elems and peak; markers are always host
+ * memory.  With QPSK_MEM_DEVICE the payload rows of _bytes_fmt stay where they
+ * are: the symbol kernel reads TSC, START, payload and END by index
+ * (QPSKModulator.cs:54-72, :112-126), no framed copy is built.
+ * Device output rows: out aligned to one complex sample (8 / 4 / 2 / 2 bytes),
+ * out_stride_elems even and >= the longest row, else QPSK_ERR_ARGUMENT before
+ * anything is launched.  Rows 16-byte aligned with a stride of a multiple of 16
+ * bytes are written 16 bytes a store (the wide-load condition of
+ * qpsk_demod_process_fmt, which can take them as they are), other rows one
+ * sample a store; the values are the same.  Elements past n_out_elems[s] of a
+ * device row are not written; what lies there in a host row is unspecified.
+ * n_streams above 65535 (the grid dimension the streams run on) is
+ * QPSK_ERR_ARGUMENT. */
+int qpsk_mod_modulate_fmt(qpsk_mod *m, int32_t fmt, int32_t norm, float scale, int32_t n_streams,
+                          const uint8_t *bits, int64_t bits_stride_bytes, const int64_t *n_bits,
+                          int32_t pulse_shaping, int32_t mem, void *out, int64_t out_stride_elems,
+                          int64_t *n_out_elems, float *peak);
+int qpsk_mod_modulate_bytes_fmt(qpsk_mod *m, int32_t fmt, int32_t norm, float scale, int32_t n_streams,
+                                const uint8_t *payload, int64_t payload_stride, const int64_t *n_payload,
+                                const uint8_t *start_marker, int32_t n_start,
+                                const uint8_t *end_marker, int32_t n_end, int32_t pulse_shaping,
+                                int32_t mem, void *out, int64_t out_stride_elems,
+                                int64_t *n_out_elems, float *peak);
+
 const char *qpsk_last_error(void);
 int qpsk_abi_version(void);
 

@@ -58,6 +58,15 @@ _FORMATS = {"cf32": (FMT_CF32, np.float32, C.c_float), "cs16": (FMT_CS16, np.int
             "cs8": (FMT_CS8, np.int8, C.c_int8), "cu8": (FMT_CU8, np.uint8, C.c_uint8)}
 
 
+# qpsk_mod_modulate_fmt's norm (QPSK_MOD_NORM_*), and the row lengths at which its
+# kernels change blocks (QPSK_MOD_TILE_SAMPLES, QPSK_MOD_SCAN_DIBITS)
+NORM_FIXED = 0
+NORM_PEAK = 1
+_NORMS = {"fixed": NORM_FIXED, "peak": NORM_PEAK}
+MOD_TILE_SAMPLES = 512
+MOD_SCAN_DIBITS = 1024
+
+
 def _format(fmt):
     """(QPSK_FMT_*, numpy dtype, ctypes type) of a format name or tag."""
     for name, rec in _FORMATS.items():
@@ -242,6 +251,13 @@ def lib():
     L.qpsk_mod_modulate_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_int64, C.c_void_p]
+    # format-tagged modulator: fmt, norm, scale in front, void rows, peak behind
+    L.qpsk_mod_modulate_fmt.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_float] +
+                                        L.qpsk_mod_modulate.argtypes[1:] + [C.c_void_p])
+    L.qpsk_mod_modulate_bytes_fmt.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_float] +
+                                              L.qpsk_mod_modulate_bytes.argtypes[1:10] + [C.c_int32] +
+                                              L.qpsk_mod_modulate_bytes.argtypes[10:] + [C.c_void_p])
+    L.qpsk_quantise_iq.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.qpsk_demod_pipeline_depth.argtypes = [C.c_void_p]
     L.qpsk_demod_max_symbols.argtypes = [C.c_void_p, C.c_int64]
     L.qpsk_demod_max_symbols.restype = C.c_int64
@@ -383,6 +399,7 @@ EXPORTED_SYMBOLS = [
     "qpsk_demod_group_get_streams_state", "qpsk_demod_group_set_streams_state",
     "qpsk_framer_dev_reset_streams", "qpsk_frames_pack_device", "qpsk_rx_attach_framer", "qpsk_rx_set_markers",
     "qpsk_rx_frames_bytes", "qpsk_rx_collect_frames", "qpsk_rx_reset_streams",
+    "qpsk_quantise_iq", "qpsk_mod_modulate_fmt", "qpsk_mod_modulate_bytes_fmt",
 ]
 
 _EXC = {
@@ -1418,8 +1435,34 @@ class QPSKModulator:
     def output_floats(self, n_bits, pulse_shaping=True) -> int:
         return int(lib().qpsk_mod_output_floats(self._h, int(n_bits), 1 if pulse_shaping else 0))
 
-    def modulate_batch(self, bit_rows, n_bits, pulse_shaping=True):
-        """bit_rows [S, B] uint8 packed MSB-first, n_bits [S] -> list of float32 arrays."""
+    def set_stream(self, hip_stream_ptr: int | None):
+        """Order the handle's calls on a caller's stream (torch's); None goes
+        back to the handle's own."""
+        _check(lib().qpsk_mod_set_stream(self._h, C.c_void_p(hip_stream_ptr or 0)))
+        self._bound = bool(hip_stream_ptr)
+
+    # ---- host memory -------------------------------------------------------
+    def _host_rows(self, call, S, n_max_bits, pulse_shaping, fmt, norm, scale, raw):
+        """One host call: call(tag, norm, scale, out, width, n_out, peak) fills S
+        rows of fmt wide enough for n_max_bits payload bits.  Returns the rows
+        cut to their lengths, or with raw (out [S, width], n_out [S]) as the
+        library left them; a PEAK call leaves its peaks in last_peaks."""
+        tag, dtype, _ = _format(fmt)
+        width = max(self.output_floats(n_max_bits, pulse_shaping), 2)
+        out = np.zeros((S, width), dtype=dtype)
+        nout = np.zeros(S, dtype=np.int64)
+        peak = np.zeros(S, dtype=np.float32) if _norm(norm) == NORM_PEAK else None
+        _check(call(tag, _norm(norm), C.c_float(float(np.float32(scale))), out.ctypes.data, width, nout.ctypes.data,
+                    peak.ctypes.data if peak is not None else None))
+        self.last_peaks = peak
+        return (out, nout) if raw else [out[s, : int(nout[s])].copy() for s in range(S)]
+
+    def modulate_batch(self, bit_rows, n_bits, pulse_shaping=True, fmt="cf32", norm="fixed", scale=1.0, raw=False):
+        """bit_rows [S, B] uint8 packed MSB-first, n_bits [S] -> list of arrays of
+        fmt's element type ("cf32" float32, "cs16" int16, "cs8" int8, "cu8"
+        uint8; qpsk_mod_modulate_fmt).  norm "fixed": x * scale, clamped and
+        truncated; "peak": each row scaled by its own peak (SaveAsCs16), the
+        peaks in last_peaks."""
         rows = np.ascontiguousarray(bit_rows, dtype=np.uint8)
         nb = np.ascontiguousarray(n_bits, dtype=np.int64)
         S = nb.size
@@ -1427,49 +1470,127 @@ class QPSKModulator:
             raise ValueError("bit_rows must be [S, B] with one n_bits per row")
         if S and int(nb.max()) > 8 * rows.shape[1]:
             raise ValueError("a bit count exceeds its row")
-        width = max(self.output_floats(int(nb.max()) if S else 0, pulse_shaping), 2)
-        out = np.zeros((S, width), dtype=np.float32)
-        nout = np.zeros(S, dtype=np.int64)
-        _check(lib().qpsk_mod_modulate(self._h, S, rows.ctypes.data if rows.size else None,
-                                       rows.shape[1], nb.ctypes.data, 1 if pulse_shaping else 0,
-                                       MEM_HOST, out.ctypes.data, width, nout.ctypes.data))
-        return [out[s, : int(nout[s])].copy() for s in range(S)]
+        fn = lib().qpsk_mod_modulate_fmt
+        return self._host_rows(
+            lambda tag, nrm, sc, out, width, nout, peak: fn(
+                self._h, tag, nrm, sc, S, rows.ctypes.data if rows.size else None, rows.shape[1], nb.ctypes.data,
+                1 if pulse_shaping else 0, MEM_HOST, out, width, nout, peak),
+            S, int(nb.max()) if S else 0, pulse_shaping, fmt, norm, scale, raw)
 
-    def Modulate(self, data: str, pulseShaping=True) -> np.ndarray:
+    def modulate_bytes_batch(self, payload_rows, n_payload, startMarker: bytes, endMarker: bytes,
+                             pulse_shaping=True, fmt="cf32", norm="fixed", scale=1.0, raw=False):
+        """ModulateBytes on every row: payload_rows [S, P] uint8, n_payload [S]
+        bytes each -> list of arrays of fmt (qpsk_mod_modulate_bytes_fmt)."""
+        st, en = _markers(startMarker, endMarker)
+        rows = np.ascontiguousarray(payload_rows, dtype=np.uint8)
+        npay = np.ascontiguousarray(n_payload, dtype=np.int64)
+        S = npay.size
+        if rows.ndim != 2 or rows.shape[0] != S:
+            raise ValueError("payload_rows must be [S, P] with one n_payload per row")
+        if S and int(npay.max()) > rows.shape[1]:
+            raise ValueError("a payload length exceeds its row")
+        fn = lib().qpsk_mod_modulate_bytes_fmt
+        return self._host_rows(
+            lambda tag, nrm, sc, out, width, nout, peak: fn(
+                self._h, tag, nrm, sc, S, rows.ctypes.data if rows.size else None, max(rows.shape[1], 1),
+                npay.ctypes.data, st.ctypes.data, st.size, en.ctypes.data, en.size, 1 if pulse_shaping else 0, MEM_HOST,
+                out, width, nout, peak),
+            S, 8 * (len(startMarker) + (int(npay.max()) if S else 0) + len(endMarker)), pulse_shaping, fmt, norm,
+            scale, raw)
+
+    def Modulate(self, data: str, pulseShaping=True, fmt="cf32", norm="fixed", scale=1.0) -> np.ndarray:
         if data is None:
             raise ValueError("data")                                   # ArgumentNullException :107
         if any(c not in "01" for c in data):
             raise ValueError("data must be a '0'/'1' string")
         row = pack_bits(data) if data else np.zeros(1, np.uint8)
-        return self.modulate_batch(row[None, :], [len(data)], pulseShaping)[0]
+        return self.modulate_batch(row[None, :], [len(data)], pulseShaping, fmt, norm, scale)[0]
 
     def ModulateBytes(self, payload: bytes, startMarker: bytes, endMarker: bytes,
-                      pulseShaping=True) -> np.ndarray:
+                      pulseShaping=True, fmt="cf32", norm="fixed", scale=1.0) -> np.ndarray:
         if len(startMarker) == 0:
             raise ValueError("startMarker cannot be empty.")              # :60
         if len(endMarker) == 0:
             raise ValueError("endMarker cannot be empty.")                # :61
-        pay = np.frombuffer(bytes(payload), dtype=np.uint8).copy()
-        st = np.frombuffer(bytes(startMarker), dtype=np.uint8).copy()
-        en = np.frombuffer(bytes(endMarker), dtype=np.uint8).copy()
-        nbits = 8 * (st.size + pay.size + en.size)
-        width = max(self.output_floats(nbits, pulseShaping), 2)
-        out = np.zeros((1, width), dtype=np.float32)
-        nout = np.zeros(1, dtype=np.int64)
-        npay = np.array([pay.size], dtype=np.int64)
-        _check(lib().qpsk_mod_modulate_bytes(self._h, 1, pay.ctypes.data if pay.size else None,
-                                             max(pay.size, 1), npay.ctypes.data, st.ctypes.data,
-                                             st.size, en.ctypes.data, en.size,
-                                             1 if pulseShaping else 0, out.ctypes.data, width,
-                                             nout.ctypes.data))
-        return out[0, : int(nout[0])].copy()
+        pay = np.frombuffer(bytes(payload), dtype=np.uint8)
+        return self.modulate_bytes_batch(pay.reshape(1, -1), [pay.size], bytes(startMarker), bytes(endMarker),
+                                         pulseShaping, fmt, norm, scale)[0]
 
     def ModulateTextUtf8(self, text: str, startMarker="\u0002", endMarker="\u0003",
-                         pulseShaping=True) -> np.ndarray:
+                         pulseShaping=True, fmt="cf32", norm="fixed", scale=1.0) -> np.ndarray:
         if text is None:
             raise ValueError("text")                                   # :81
         return self.ModulateBytes(text.encode("utf-8"), startMarker.encode("utf-8"),
-                                  endMarker.encode("utf-8"), pulseShaping)
+                                  endMarker.encode("utf-8"), pulseShaping, fmt, norm, scale)
+
+    # ---- device memory (torch tensors resident in HBM) ----------------------
+    def _device_rows(self, call, rows_dev, counts_dev, out_dev, n_out_dev, fmt, norm, peak_dev):
+        """One device call: checks what the library cannot see of the tensors
+        (device, dtypes, contiguous rows, one count a row) and leaves alignment
+        and strides to it.  The call returns when the rows are complete."""
+        import torch
+        tag = _format(fmt)[0]
+        S = counts_dev.numel()
+        for t, dt, what in ((rows_dev, torch.uint8, "rows"), (out_dev, _torch_dtype(fmt), "out_dev")):
+            if not t.is_cuda or t.dtype != dt or t.dim() != 2 or t.shape[0] != S or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise ValueError(f"{what} must be a contiguous-row {dt} [n_streams, k] device tensor")
+        for t, what in ((counts_dev, "counts"), (n_out_dev, "n_out_dev")):
+            if not t.is_cuda or t.dtype != torch.int64 or t.numel() != S or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous int64 [n_streams] device tensor")
+        if _norm(norm) == NORM_PEAK and (peak_dev is None or not peak_dev.is_cuda or peak_dev.dtype != torch.float32 or
+                                         peak_dev.numel() != S or not peak_dev.is_contiguous()):
+            raise ValueError("norm 'peak' needs peak_dev, a contiguous float32 [n_streams] device tensor")
+        if not getattr(self, "_bound", False):   # the handle's own stream does not order against torch's
+            torch.cuda.current_stream(out_dev.device).synchronize()
+        _check(call(tag, rows_dev.data_ptr(), rows_dev.stride(0), counts_dev.data_ptr(), out_dev.data_ptr(),
+                    out_dev.stride(0), n_out_dev.data_ptr(), peak_dev.data_ptr() if peak_dev is not None else None))
+
+    def modulate_device(self, bits_dev, n_bits_dev, out_dev, n_out_dev, pulse_shaping=True, fmt="cf32",
+                        norm="fixed", scale=1.0, peak_dev=None):
+        """modulate_batch on device tensors: bits_dev uint8 [S, B], n_bits_dev
+        int64 [S], out_dev [S, >= longest row] of fmt's element type, n_out_dev
+        int64 [S] (elements written a row), peak_dev float32 [S] for norm
+        "peak".  Rows aligned to 16 bytes with a pitch of a multiple of 16
+        bytes are written 16 bytes a store and go into process_device_fmt as
+        they are; elements past a row's length are not written."""
+        fn = lib().qpsk_mod_modulate_fmt
+        sc = C.c_float(float(np.float32(scale)))
+        self._device_rows(lambda tag, rows, rstride, cnt, out, ostride, nout, peak: fn(
+            self._h, tag, _norm(norm), sc, n_bits_dev.numel(), rows, rstride, cnt, 1 if pulse_shaping else 0,
+            MEM_DEVICE, out, ostride, nout, peak), bits_dev, n_bits_dev, out_dev, n_out_dev, fmt, norm, peak_dev)
+
+    def modulate_bytes_device(self, payload_dev, n_payload_dev, startMarker: bytes, endMarker: bytes, out_dev,
+                              n_out_dev, pulse_shaping=True, fmt="cf32", norm="fixed", scale=1.0, peak_dev=None):
+        """modulate_bytes_batch on device tensors: the payload rows (uint8
+        [S, P], n_payload_dev int64 [S]) stay where they are, the markers are
+        host bytes."""
+        st, en = _markers(startMarker, endMarker)
+        fn = lib().qpsk_mod_modulate_bytes_fmt
+        sc = C.c_float(float(np.float32(scale)))
+        self._device_rows(lambda tag, rows, rstride, cnt, out, ostride, nout, peak: fn(
+            self._h, tag, _norm(norm), sc, n_payload_dev.numel(), rows, rstride, cnt, st.ctypes.data, st.size,
+            en.ctypes.data, en.size, 1 if pulse_shaping else 0, MEM_DEVICE, out, ostride, nout, peak),
+            payload_dev, n_payload_dev, out_dev, n_out_dev, fmt, norm, peak_dev)
+
+
+def _norm(norm):
+    """QPSK_MOD_NORM_* of "fixed" / "peak" or a tag (passed on for the library to check)."""
+    return _NORMS[norm] if isinstance(norm, str) else int(norm)
+
+
+def quantise_iq(iq, fmt, norm="fixed", scale=1.0):
+    """qpsk_quantise_iq: one row of host float32 I,Q to fmt by the modulator's
+    own rules (needs no device).  Returns (row of fmt's element type, the
+    row's peak as np.float32 for norm "peak", else None)."""
+    tag, dtype, _ = _format(fmt)
+    x = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
+    out = np.zeros(x.size, dtype=dtype)
+    peak = np.zeros(1, dtype=np.float32)
+    is_peak = _norm(norm) == NORM_PEAK
+    _check(lib().qpsk_quantise_iq(tag, _norm(norm), C.c_float(float(np.float32(scale))),
+                                  x.ctypes.data if x.size else None, x.size, out.ctypes.data if x.size else None,
+                                  peak.ctypes.data if is_peak else None))
+    return out, (peak[0] if is_peak else None)
 
 
 def synth_generate(n_streams, n_samples, sample_rate, symbol_rate, rrc_alpha=float(np.float32(0.4)),
