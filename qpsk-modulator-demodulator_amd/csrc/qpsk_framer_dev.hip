@@ -10,11 +10,15 @@
 //                == the first bit position q of the marker's bit pattern with
 //                the smallest q mod 8 (the offset loop runs first, the byte
 //                index second); each thread scans 32 positions from one 64-bit
-//                window and the 8 per-offset minima reduce in LDS
-//   append       AppendBitsToRing (:108-129) == a funnel-shifted copy of the
-//                bit row behind the packer's partial byte into the ring
+//                window and the smallest (q mod 8, q) reduces in LDS
+//   keep carry   no start: the candidate string's tail stays for the next call
+//   pack         AppendBitsToRing (:108-129) == a funnel-shifted view of the
+//                bit row behind the packer's partial byte, cut into bytes
 //   end search   RingIndexOf from count - (appended + |end|) (:133-149, :246)
-//   copy-out     RingCopyOut + ResetFramer (:151-167)
+//   close        RingCopyOut + ResetFramer (:151-167)
+//   append       else the bytes go into the ring
+//
+// framer_step is that state machine; all three searches are first_match.
 //
 // Work per call is O(bits) with no serial walk, and the scans stop at the
 // first match (the chunk holding it): on real traffic the start and end
@@ -72,14 +76,21 @@ __device__ inline uint32_t bit_at(const uint8_t *row, int64_t p) {
     return (row[p >> 3] >> (7 - (p & 7))) & 1u;
 }
 
-// 8 bits at bit position p (p + 8 <= valid bits of row).
-__device__ inline uint32_t bits8(const uint8_t *row, int64_t p) {
+// n bits (0 <= n <= 8) at bit position p, as the low bits of the result.  Only
+// the bytes that hold them are read, none for n == 0: a byte that straddles an
+// edge (carry | row, packer | row, a string's end) is two such pieces.  The
+// second load repeats the first byte where the bits end in it (the shift drops
+// it), so both loads are in flight together, not one behind a branch.
+__device__ inline uint32_t bits_at(const uint8_t *row, int64_t p, int n) {
+    if (n <= 0) return 0;
     const int64_t b = p >> 3;
     const int sh = static_cast<int>(p & 7);
-    uint32_t v = static_cast<uint32_t>(row[b]) << 8;
-    if (sh) v |= row[b + 1];
-    return (v >> (8 - sh)) & 0xffu;
+    const uint32_t v = (static_cast<uint32_t>(row[b]) << 8) | row[b + (sh + n > 8)];
+    return (v >> (16 - sh - n)) & ((1u << n) - 1);
 }
+
+// 8 bits at bit position p (p + 8 <= valid bits of row).
+__device__ inline uint32_t bits8(const uint8_t *row, int64_t p) { return bits_at(row, p, 8); }
 
 // 64 bits from byte b on (MSB-first), bytes at or past nbytes read as 0.
 __device__ inline uint64_t load_be64(const uint8_t *row, int64_t b, int64_t nbytes) {
@@ -114,32 +125,104 @@ __device__ inline uint64_t load_be64_any(const uint8_t *row, int64_t b, int64_t 
     return load_be64(row, b, nbytes);
 }
 
-// The candidate bit string of a hunt: carry bits, then the row from bit off0.
+// Positions a search chunk covers before the workgroup looks at its result:
+// the reference's scans stop at the first match (IndexOf, RingIndexOf), and on
+// real traffic that sits near the start of the row.
+constexpr int kHuntWindows = kFrThreads;        // 32 positions each: 1 KB of candidate bits
+constexpr int kEndPerThread = 8;                // ring positions per thread and chunk
+constexpr unsigned long long kNoMatch = ULLONG_MAX;
+
+
+// The workgroup's smallest match key over the positions [first, last]
+// (first >= 0), kNoMatch if there is none; every thread calls it and gets the
+// answer.  Positions are taken in ascending chunks.  Per chunk prepare(c0) runs
+// first, a step of the whole workgroup (ending in a barrier if the probes read
+// what it wrote); then probe(c0) returns the smallest key among the calling
+// thread's share of [c0, c0 + chunk), or kNoMatch.  A key is its position, with
+// or without a rank in the high bits: never smaller than the position.  So once
+// the minimum lies below the next chunk's first position the search stops.
+template <class Prepare, class Probe>
+__device__ unsigned long long first_match(int64_t first, int64_t last, int64_t chunk, Prepare prepare,
+                                          Probe probe) {
+    __shared__ unsigned long long best;
+    if (threadIdx.x == 0) best = kNoMatch;
+    __syncthreads();                       // an empty range reads nothing, a first chunk reads this
+    unsigned long long found = kNoMatch;
+    for (int64_t c0 = first; c0 <= last; c0 += chunk) {
+        prepare(c0);
+        const unsigned long long mine = probe(c0);
+        if (mine != kNoMatch) atomicMin(&best, mine);
+        __syncthreads();
+        // The exit must be one decision for the whole workgroup: every wave
+        // reads the minimum, and only after a second barrier may any wave go
+        // on to the next chunk's atomicMin.  Without it a wave late to read
+        // could see a match a faster wave had already posted for the NEXT
+        // chunk and leave with a partial minimum.  (The window is a few
+        // instructions inside one workgroup, so no test goes red on it
+        // reliably; the chunk edge cases of tests/test_framer.py put matches
+        // where it would bite.)
+        found = best;
+        __syncthreads();
+        if (found < static_cast<unsigned long long>(c0 + chunk)) break;
+    }
+    return found;
+}
+
+// The candidate bit string of a hunt: carry bits, then the row from bit off0,
+// n bits in all.  Inside a frame it is rxBits alone (no carry).
 struct Cand {
     const uint8_t *carry;
     int64_t ncarry;
     const uint8_t *row;
     int64_t off0;
-    __device__ uint32_t bit(int64_t q) const {
-        return q < ncarry ? bit_at(carry, q) : bit_at(row, off0 + q - ncarry);
+    int64_t n;
+    // bits [q, q + k) as the low bits of the result (k <= 8, q + k <= n)
+    __device__ uint32_t bits(int64_t q, int k) const {
+        if (q >= ncarry) return bits_at(row, off0 + q - ncarry, k);
+        const int kc = static_cast<int>(ncarry - q < k ? ncarry - q : k);    // of them in the carry
+        return (bits_at(carry, q, kc) << (k - kc)) | bits_at(row, off0, k - kc);
     }
-    // bits [q, q + 8) (q + 8 <= the string's length)
+    // bits [q, q + 8), zero past n (q < n)
     __device__ uint32_t bits8_at(int64_t q) const {
-        if (q >= ncarry) return bits8(row, off0 + q - ncarry);
-        if (q + 8 <= ncarry) return bits8(carry, q);
-        uint32_t v = 0;
-        for (int i = 0; i < 8; ++i) v = (v << 1) | bit(q + i);
-        return v;
+        const int k = static_cast<int>(n - q < 8 ? n - q : 8);
+        return bits(q, k) << (8 - k);
     }
-    // byte j of the candidate string (bits 8j..8j+7, zero past n)
-    __device__ uint32_t byte(int64_t j, int64_t n) const {
-        const int64_t q = 8 * j;
-        if (q >= ncarry && q + 8 <= n) return bits8(row, off0 + q - ncarry);
-        if (q + 8 <= ncarry) return carry[j];
-        uint32_t v = 0;
-        for (int i = 0; i < 8; ++i) v = (v << 1) | (q + i < n ? bit(q + i) : 0u);
-        return v;
+};
+
+// The candidate string as bytes in the stream's scratch row, where the hunt's
+// windows are aligned loads: bytes [0, mat) are there, zero behind the string.
+struct CandRow {
+    uint8_t *bytes;
+    Cand src;
+    int64_t mat;
+    __device__ int64_t pad_end() const { return ((src.n + 7) >> 3) + 8; }   // zero bytes behind the string (scratch slack)
+    // bytes [mat, min(upto, pad_end())) by the whole workgroup
+    __device__ void fill(int64_t upto) {
+        const int64_t ncb = (src.n + 7) >> 3;
+        upto = upto < pad_end() ? upto : pad_end();
+        for (int64_t j = mat + threadIdx.x; j < upto; j += kFrThreads)
+            bytes[j] = static_cast<uint8_t>(j < ncb ? src.bits8_at(8 * j) : 0u);
+        mat = upto > mat ? upto : mat;
+        __syncthreads();
     }
+};
+
+// W, the bit string a call cuts into ring bytes: the packer's P held bits,
+// then the candidate string from bit `base` on.  A call that enters a frame
+// has an empty packer and base = the first bit behind the start marker (:203-214);
+// inside a frame the candidate string is rxBits and base = 0 (:238-246).
+struct Packed {
+    Cand c;
+    int64_t base;
+    uint32_t pack_byte;
+    int P;
+    // bits [w, w + k) of W as the low bits of the result (k <= 8, w + k <= |W|)
+    __device__ uint32_t bits(int64_t w, int k) const {
+        if (w >= P) return c.bits(base + w - P, k);
+        const int kp = static_cast<int>(P - w < k ? P - w : k);              // of them in the packer
+        return (((pack_byte >> (P - w - kp)) & ((1u << kp) - 1)) << (k - kp)) | c.bits(base, k - kp);
+    }
+    __device__ uint32_t byte(int64_t j) const { return bits(8 * j, 8); }     // 8j + 8 <= |W|
 };
 
 __device__ void reset_state(FrState &s) {   // ResetFramer (:159-167)
@@ -151,214 +234,145 @@ __device__ void reset_state(FrState &s) {   // ResetFramer (:159-167)
     s.carry_bits = 0;
 }
 
-// Positions a hunt / search chunk covers before the workgroup looks at its
-// result: the reference's scans stop at the first match (IndexOf,
-// RingIndexOf), and on real traffic that sits near the start of the row, so
-// the chunks run in ascending position order and stop as soon as the answer
-// cannot change.  (Until round 6 every position of the row was scanned and
-// the whole row copied into the candidate scratch and the ring first.)
-constexpr int kHuntWindows = kFrThreads;        // 32 positions each: 1 KB of candidate bits
-constexpr int kEndPerThread = 8;                // ring positions per thread and chunk
+constexpr int kOffShift = 61;               // a hunt key: q mod 8 above bit 61, q below
 
-__global__ void __launch_bounds__(kFrThreads) framer_push_kernel(FrArgs a) {
-    __shared__ unsigned long long best[8];
-    __shared__ unsigned long long best_end;
-    const int s = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int64_t off0 = a.bit_offset ? a.bit_offset[s] : 0;
-    const int64_t nb = a.n_bits[s] - off0;
-    if (tid == 0) a.n_payload[s] = 0;
-    if (off0 < 0 || nb <= 0) return;                       // rxBits empty (:179-180)
-
-    const uint8_t *row = a.bits + s * a.bits_stride;
-    uint8_t *ring = a.ring + s * a.ring_cap;
-    FrState st = a.st[s];
-    __syncthreads();                       // every wave holds st before thread 0 may rewrite it
-
-    // the bytes this call appends to the ring, as a function (materialised only
-    // when the frame stays open past this call): case A = candidate bits from
-    // the end of the start marker, case B = the packer's partial byte + rxBits
-    bool entering = false;                 // case A (the frame opens in this call)
-    Cand src{nullptr, 0, row, off0};
-    int64_t mend = 0;                      // case A: first candidate bit after the start marker
-    const int P = st.pack_bits;            // case B
-    const uint32_t pack_byte = static_cast<uint32_t>(st.pack_byte);
-    int64_t produced = 0;
-    int rem = 0;
-
-    if (!st.in_frame) {
-        // ---- 1) start hunt over carry + rxBits (:183-236) ----
-        // BitsToBytes(cand, off) + IndexOf for off = 0..7 == the first bit
-        // position q of the marker pattern with the smallest q mod 8; every
-        // thread tests 32 positions of one 64-bit window per chunk
-        uint8_t *carry = a.carry + s * a.carry_stride;
-        uint8_t *cand = a.scratch + s * a.scr_stride;
-        src.carry = carry;
-        src.ncarry = st.carry_bits;
-        const int64_t nc = st.carry_bits + nb;
-        const int64_t ncb = (nc + 7) >> 3;
-        const int64_t pad_end = ncb + 8;                 // zero bytes behind the string (scratch slack)
-        if (tid < 8) best[tid] = ULLONG_MAX;
-        const int64_t limit = nc - 8 * static_cast<int64_t>(a.ns);   // last start position
-        const uint32_t m0 = a.start[0];
-        int64_t mat = 0;                                 // candidate bytes [0, mat) are in the scratch
-        for (int64_t w0 = 0; 32 * w0 <= limit; w0 += kHuntWindows) {
-            // the chunk's windows read bytes < 4 (w0 + kHuntWindows) + 8, the
-            // marker checks up to ns + 1 bytes beyond
-            int64_t need = 4 * (w0 + kHuntWindows) + 8 + a.ns + 1;
-            need = need < pad_end ? need : pad_end;
-            for (int64_t j = mat + tid; j < need; j += kFrThreads)
-                cand[j] = static_cast<uint8_t>(j < ncb ? src.byte(j, nc) : 0u);
-            mat = need > mat ? need : mat;
-            __syncthreads();
-            const int64_t w = w0 + tid;
-            if (32 * w <= limit) {
-                const uint64_t win = load_be64_aligned(cand, 4 * w);
-                const int jmax = static_cast<int>(limit - 32 * w < 31 ? limit - 32 * w : 31);
-                for (int j = 0; j <= jmax; ++j) {
-                    if (((win >> (56 - j)) & 0xffu) != m0) continue;
-                    const int64_t q = 32 * w + j;
-                    int k = 1;
-                    while (k < a.ns && bits8(cand, q + 8 * k) == a.start[k]) ++k;
-                    if (k == a.ns) atomicMin(&best[j & 7], static_cast<unsigned long long>(q));
-                }
-            }
-            __syncthreads();
-            // offset 0 matched: no later chunk can hold a smaller offset-0
-            // position, and offset 0 wins over every other offset
-            if (best[0] != ULLONG_MAX) break;
-        }
-        int64_t q = -1;
-        int off = -1;
-        for (int o = 0; o < 8; ++o)
-            if (best[o] != ULLONG_MAX) { q = static_cast<int64_t>(best[o]); off = o; break; }
-
-        if (q < 0) {
-            // no start: keep min(|cand|, 8|start|+7) tail bits (:233-235),
-            // copied from the scratch (the carry is rewritten in place)
-            for (int64_t j = mat + tid; j < pad_end; j += kFrThreads)
-                cand[j] = static_cast<uint8_t>(j < ncb ? src.byte(j, nc) : 0u);
-            __syncthreads();
-            const int64_t keep = nc < 8 * static_cast<int64_t>(a.ns) + 7 ? nc : 8 * static_cast<int64_t>(a.ns) + 7;
-            const int64_t base = nc - keep;
-            for (int64_t j = tid; j < (keep + 7) >> 3; j += kFrThreads) {
-                const int64_t p = base + 8 * j;
-                uint32_t v;
-                if (p + 8 <= nc) v = bits8(cand, p);
-                else {
-                    v = 0;
-                    for (int i = 0; i < 8; ++i) v = (v << 1) | (p + i < nc ? bit_at(cand, p + i) : 0u);
-                }
-                carry[j] = static_cast<uint8_t>(v);
-            }
-            if (tid == 0) {
-                st.carry_bits = keep;
-                a.st[s] = st;
-            }
-            return;
-        }
-        // enter the frame: ring cleared, payload = cand bits after the marker (:203-214)
-        mend = q + 8 * static_cast<int64_t>(a.ns);
-        const int64_t len = nc - mend;
-        produced = len >> 3;
-        if (produced > a.ring_cap) {                         // overflow -> drop + resync (:215-220)
-            if (tid == 0) {
-                reset_state(st);
-                a.st[s] = st;
-            }
-            return;
-        }
-        entering = true;
-        st.in_frame = 1;
-        st.locked_off = off;
-        rem = static_cast<int>(len & 7);
-        uint32_t pb = 0;
-        for (int r = 0; r < rem; ++r) pb = (pb << 1) | src.bit(mend + 8 * produced + r);
-        st.pack_byte = static_cast<int32_t>(pb);
-        st.pack_bits = rem;
-        st.count = 0;                                        // the ring restarts (RingClear)
-    } else {
-        // ---- 2) inside a frame: pack rxBits behind the partial byte (:238-246) ----
-        const int64_t total = P + nb;
-        produced = total >> 3;
-        if (st.count + produced > a.ring_cap) {
-            if (tid == 0) {
-                reset_state(st);
-                a.st[s] = st;
-            }
-            return;
-        }
-        // leftover bits: W[8*produced, total) of W = pack prefix + rxBits
-        rem = static_cast<int>(total & 7);
-        uint32_t pb = 0;
-        for (int r = 0; r < rem; ++r) {
-            const int64_t w = 8 * produced + r;
-            pb = (pb << 1) | (w < P ? (pack_byte >> (P - 1 - w)) & 1u : bit_at(row, off0 + w - P));
-        }
-        st.pack_byte = static_cast<int32_t>(pb);
-        st.pack_bits = rem;
-    }
-    const int64_t old_count = st.count;
-    const int64_t count = old_count + produced;
-    // byte j of this call's appended bytes (j < produced)
-    auto newbyte = [&](int64_t j) -> uint32_t {
-        if (entering) return src.bits8_at(mend + 8 * j);
-        if (j == 0 && P > 0) {
-            uint32_t v = pack_byte;
-            for (int i = 0; i < 8 - P; ++i) v = (v << 1) | bit_at(row, off0 + i);
-            return v & 0xffu;
-        }
-        return bits8(row, off0 + 8 * j - P);
-    };
-    // ring byte i after the append (i < count), without writing the ring
-    auto ring_byte = [&](int64_t i) -> uint32_t { return i < old_count ? ring[i] : newbyte(i - old_count); };
-
-    // ---- 3) end search: RingIndexOf from count - (appended + |end|) (:133-149, :246)
-    const int64_t from = count - (produced + a.ne) > 0 ? count - (produced + a.ne) : 0;
-    const int64_t last = count - a.ne;                       // last start position of the end marker
-    if (tid == 0) best_end = ULLONG_MAX;
-    __syncthreads();
-    const uint32_t e0 = a.end[0];
-    for (int64_t c0 = from; c0 <= last; c0 += kFrThreads * kEndPerThread) {
+// Start hunt over carry + rxBits (:183-236).  BitsToBytes(cand, off) + IndexOf
+// for off = 0..7 == the first bit position q of the marker pattern with the
+// smallest q mod 8, so the key is (q mod 8, q) and the search stops after the
+// first chunk with an offset-0 match.  Every thread tests the 32 positions of
+// one 64-bit window; the chunk's candidate bytes go into the scratch row first.
+__device__ unsigned long long hunt_start(CandRow &cr, const uint8_t *start, int ns) {
+    const int64_t limit = cr.src.n - 8 * static_cast<int64_t>(ns);   // last start position
+    const uint32_t m0 = start[0];
+    return first_match(
+        0, limit, 32 * kHuntWindows,
+        // the chunk's windows read bytes < c0 / 8 + 4 kHuntWindows + 8, the
+        // marker checks up to ns + 1 bytes beyond
+        [&](int64_t c0) { cr.fill((c0 >> 3) + 4 * kHuntWindows + 8 + ns + 1); },
+        [&](int64_t c0) {
+            unsigned long long mine = kNoMatch;
+            const int64_t w = (c0 >> 5) + threadIdx.x;
+            if (32 * w > limit) return mine;
+            const uint64_t win = load_be64_aligned(cr.bytes, 4 * w);
+            const int jmax = static_cast<int>(limit - 32 * w < 31 ? limit - 32 * w : 31);
+            uint32_t hits = 0;                               // bit j: position j starts with the marker's first byte
 #pragma unroll
+            for (int j = 0; j < 32; ++j) hits |= static_cast<uint32_t>(((win >> (56 - j)) & 0xffu) == m0) << j;
+            for (hits &= 0xffffffffu >> (31 - jmax); hits; hits &= hits - 1) {
+                const int j = __ffs(hits) - 1;
+                const int64_t q = 32 * w + j;
+                int k = 1;
+                while (k < ns && bits8(cr.bytes, q + 8 * k) == start[k]) ++k;
+                const unsigned long long key = (static_cast<unsigned long long>(j & 7) << kOffShift) | q;
+                if (k == ns && key < mine) mine = key;
+            }
+            return mine;
+        });
+}
+
+// No start: keep min(|cand|, 8|start|+7) tail bits (:233-235), copied from the
+// scratch row (the carry is rewritten in place; both are zero behind their bits).
+__device__ int64_t keep_carry(CandRow &cr, uint8_t *carry, int ns) {
+    cr.fill(cr.pad_end());
+    const int64_t nc = cr.src.n;
+    const int64_t keep = nc < 8 * static_cast<int64_t>(ns) + 7 ? nc : 8 * static_cast<int64_t>(ns) + 7;
+    for (int64_t j = threadIdx.x; j < (keep + 7) >> 3; j += kFrThreads)
+        carry[j] = static_cast<uint8_t>(bits8(cr.bytes, nc - keep + 8 * j));
+    return keep;
+}
+
+// End search: RingIndexOf from count - (appended + |end|) (:133-149, :246) over
+// the ring as it is after the append; the position of the end marker or -1.
+template <class RingByte>
+__device__ int64_t end_search(RingByte ring_byte, int64_t count, int64_t produced, const uint8_t *end, int ne) {
+    const int64_t from = count - (produced + ne) > 0 ? count - (produced + ne) : 0;
+    const int64_t last = count - ne;                         // last start position of the end marker
+    const uint32_t e0 = end[0];
+    const unsigned long long at = first_match(from, last, kFrThreads * kEndPerThread, [](int64_t) {}, [&](int64_t c0) {
+        unsigned long long mine = kNoMatch;
         for (int k = 0; k < kEndPerThread; ++k) {
-            const int64_t i = c0 + k * kFrThreads + tid;
+            const int64_t i = c0 + k * kFrThreads + threadIdx.x;
             if (i > last || ring_byte(i) != e0) continue;
             int m = 1;
-            while (m < a.ne && ring_byte(i + m) == a.end[m]) ++m;
-            if (m == a.ne) atomicMin(&best_end, static_cast<unsigned long long>(i));
+            while (m < ne && ring_byte(i + m) == end[m]) ++m;
+            if (m == ne && static_cast<unsigned long long>(i) < mine) mine = i;
         }
-        __syncthreads();
-        // The exit must be one decision for the whole workgroup: every wave
-        // reads the flag, and only after a second barrier may any wave go on
-        // to the next chunk's atomicMin.  Without it a wave late to read could
-        // see a match a faster wave had already posted for the NEXT chunk and
-        // leave with a partial minimum.  (The window is a few instructions
-        // inside one workgroup, so no test goes red on it reliably; the chunk
-        // edge cases of tests/test_framer.py put matches where it would bite.)
-        const bool found = best_end != ULLONG_MAX;           // the first occurrence is in this chunk
-        __syncthreads();
-        if (found) break;
+        return mine;
+    });
+    return at == kNoMatch ? -1 : static_cast<int64_t>(at);
+}
+
+// dst[i] = byte(i), i < n, by the workgroup: RingCopyOut, and the append to the ring
+template <class Byte>
+__device__ void store_bytes(uint8_t *dst, int64_t n, Byte byte) {
+    for (int64_t i = threadIdx.x; i < n; i += kFrThreads) dst[i] = static_cast<uint8_t>(byte(i));
+}
+
+// One DeModulateBytes step on non-empty rxBits: the state it leaves in st, the
+// payload length it returns.  Every thread runs it with the same state, so each
+// return below is taken by the whole workgroup and no barrier is left waiting.
+__device__ int64_t framer_step(const FrArgs &a, int s, int64_t off0, int64_t nb, FrState &st) {
+    uint8_t *ring = a.ring + s * a.ring_cap;
+    Packed w{Cand{nullptr, 0, a.bits + s * a.bits_stride, off0, nb}, 0, static_cast<uint32_t>(st.pack_byte),
+             st.pack_bits};
+    if (!st.in_frame) {
+        uint8_t *carry = a.carry + s * a.carry_stride;
+        w.c.carry = carry;
+        w.c.ncarry = st.carry_bits;
+        w.c.n = st.carry_bits + nb;
+        CandRow cr{a.scratch + s * a.scr_stride, w.c, 0};
+        const unsigned long long key = hunt_start(cr, a.start, a.ns);
+        if (key == kNoMatch) {
+            st.carry_bits = keep_carry(cr, carry, a.ns);
+            return 0;
+        }
+        // enter the frame: ring cleared, W = cand bits after the marker (:203-214)
+        w.base = static_cast<int64_t>(key & ((1ull << kOffShift) - 1)) + 8 * static_cast<int64_t>(a.ns);
+        w.P = 0;
+        st.in_frame = 1;
+        st.locked_off = static_cast<int32_t>(key >> kOffShift);
+        st.count = 0;                                        // the ring restarts (RingClear)
     }
-    const int64_t end_at = best_end == ULLONG_MAX ? -1 : static_cast<int64_t>(best_end);
+    // pack W behind the ring's bytes (AppendBitsToRing): whole bytes to the
+    // ring, the leftover bits W[8 produced, |W|) stay in the packer
+    const int64_t len = w.P + w.c.n - w.base;
+    const int64_t produced = len >> 3;
+    if (st.count + produced > a.ring_cap) {                  // overflow -> drop + resync (:215-220, :241-245)
+        reset_state(st);
+        return 0;
+    }
+    st.pack_bits = static_cast<int32_t>(len & 7);
+    st.pack_byte = static_cast<int32_t>(w.bits(8 * produced, st.pack_bits));
+    const int64_t old_count = st.count;
+    // ring byte i after the append (i < old_count + produced), without writing the ring
+    auto ring_byte = [&](int64_t i) -> uint32_t { return i < old_count ? ring[i] : w.byte(i - old_count); };
+
+    const int64_t end_at = end_search(ring_byte, old_count + produced, produced, a.end, a.ne);
     if (end_at >= 0) {                                       // RingCopyOut + ResetFramer (:223-226)
         // the frame closes: its payload comes straight from the ring and this
         // call's bits; the appended bytes never need to be stored
-        uint8_t *out = a.payload ? a.payload + s * a.payload_stride : nullptr;
-        const int64_t n = end_at < a.payload_stride ? end_at : a.payload_stride;
-        if (out)
-            for (int64_t i = tid; i < n; i += kFrThreads) out[i] = static_cast<uint8_t>(ring_byte(i));
-        if (tid == 0) {
-            a.n_payload[s] = end_at;
-            reset_state(st);
-            a.st[s] = st;
-        }
-        return;
+        if (a.payload)
+            store_bytes(a.payload + s * a.payload_stride, end_at < a.payload_stride ? end_at : a.payload_stride,
+                        ring_byte);
+        reset_state(st);
+        return end_at;
     }
-    // the frame stays open: the appended bytes go into the ring (AppendBitsToRing)
-    for (int64_t j = tid; j < produced; j += kFrThreads) ring[old_count + j] = static_cast<uint8_t>(newbyte(j));
-    if (tid == 0) {
-        st.count = count;
+    // the frame stays open: the appended bytes go into the ring
+    store_bytes(ring + old_count, produced, [&](int64_t j) { return w.byte(j); });
+    st.count = old_count + produced;
+    return 0;
+}
+
+__global__ void __launch_bounds__(kFrThreads) framer_push_kernel(FrArgs a) {
+    const int s = blockIdx.x;
+    const int64_t off0 = a.bit_offset ? a.bit_offset[s] : 0;
+    const int64_t nb = a.n_bits[s] - off0;
+    FrState st = a.st[s];
+    __syncthreads();                       // every wave holds st before thread 0 rewrites it
+    int64_t n_payload = 0;
+    if (off0 >= 0 && nb > 0) n_payload = framer_step(a, s, off0, nb, st);   // else rxBits empty (:179-180)
+    if (threadIdx.x == 0) {
+        a.n_payload[s] = n_payload;
         a.st[s] = st;
     }
 }
@@ -371,13 +385,11 @@ struct TscPat {
 
 // rx.IndexOf(tsc, Ordinal) per stream (:413-422).  Each thread tests 32
 // positions against the first min(m, 32) pattern bits from one 64-bit window,
-// the rest bit by bit; the minimum position reduces in LDS.  Chunks of
-// kFrThreads windows run in ascending position order and the search stops
-// after the chunk holding the first match.
+// the rest bit by bit; first_match takes chunks of kFrThreads windows and
+// stops after the one holding the first match.
 __global__ void __launch_bounds__(kFrThreads)
 tsc_find_kernel(const uint8_t *bits, int64_t stride, const int64_t *n_bits, TscPat small,
                 const uint8_t *big, int32_t m, int64_t *offsets) {
-    __shared__ unsigned long long best;
     const uint8_t *pat = big ? big : small.b;
     const int s = blockIdx.x;
     const uint8_t *row = bits + s * stride;
@@ -388,60 +400,47 @@ tsc_find_kernel(const uint8_t *bits, int64_t stride, const int64_t *n_bits, TscP
     uint32_t key = 0;
     for (int i = 0; i < km; ++i) key = (key << 1) | bit_at(pat, i);
     const uint64_t kmask = km == 32 ? 0xffffffffull : ((1ull << km) - 1);
-    if (threadIdx.x == 0) best = ULLONG_MAX;
-    __syncthreads();
-    for (int64_t w0 = 0; 32 * w0 <= limit; w0 += kFrThreads) {
-        const int64_t w = w0 + threadIdx.x;
-        if (32 * w <= limit) {
-            const uint64_t win = load_be64_any(row, 4 * w, nbytes);
-            const int jmax = static_cast<int>(limit - 32 * w < 31 ? limit - 32 * w : 31);
-            // position j of the window matches the first km pattern bits
-            auto full = [&](int j) -> bool {
-                if (j > jmax || ((win >> (64 - km - j)) & kmask) != key) return false;
-                const int64_t q = 32 * w + j;
-                int k = km;
-                while (k < m && bit_at(row, q + k) == bit_at(pat, k)) ++k;
-                return k == m;
-            };
-            if (m >= 16) {
-                // a 16-bit prefix filter on two positions per 32-bit word: the
-                // word of bits [o, o + 32) holds the 16-bit values at o (high
-                // half) and o + 16 (low half), so 16 funnel shifts cover the
-                // window's 32 positions; a half equal to the prefix (haszero on
-                // the XOR, false positives possible, never false negatives) is
-                // checked in full.  ~5 ops per two positions instead of ~6 per one
-                const uint32_t k16 = key >> (km - 16);
-                const uint32_t kk = (k16 << 16) | k16;
-                const uint32_t whi = static_cast<uint32_t>(win >> 32), wlo = static_cast<uint32_t>(win);
-                int first = 64;
+    const unsigned long long at = first_match(0, limit, 32 * kFrThreads, [](int64_t) {}, [&](int64_t c0) {
+        const int64_t w = (c0 >> 5) + threadIdx.x;
+        if (32 * w > limit) return kNoMatch;
+        const uint64_t win = load_be64_any(row, 4 * w, nbytes);
+        const int jmax = static_cast<int>(limit - 32 * w < 31 ? limit - 32 * w : 31);
+        // position j of the window matches the first km pattern bits
+        auto full = [&](int j) -> bool {
+            if (j > jmax || ((win >> (64 - km - j)) & kmask) != key) return false;
+            const int64_t q = 32 * w + j;
+            int k = km;
+            while (k < m && bit_at(row, q + k) == bit_at(pat, k)) ++k;
+            return k == m;
+        };
+        int first = 64;                                      // the window's first match
+        if (m >= 16) {
+            // a 16-bit prefix filter on two positions per 32-bit word: the
+            // word of bits [o, o + 32) holds the 16-bit values at o (high
+            // half) and o + 16 (low half), so 16 funnel shifts cover the
+            // window's 32 positions; a half equal to the prefix (haszero on
+            // the XOR, false positives possible, never false negatives) is
+            // checked in full.  ~5 ops per two positions instead of ~6 per one
+            const uint32_t k16 = key >> (km - 16);
+            const uint32_t kk = (k16 << 16) | k16;
+            const uint32_t whi = static_cast<uint32_t>(win >> 32), wlo = static_cast<uint32_t>(win);
 #pragma unroll
-                for (int o = 0; o < 16; ++o) {
-                    const uint32_t x = o ? (whi << o) | (wlo >> (32 - o)) : whi;
-                    const uint32_t z = x ^ kk;
-                    const uint32_t hz = (z - 0x00010001u) & ~z & 0x80008000u;
-                    if (__builtin_expect(hz != 0, 0)) {
-                        if ((hz & 0x80000000u) && o < first && full(o)) first = o;
-                        if ((hz & 0x00008000u) && o + 16 < first && full(o + 16)) first = o + 16;
-                    }
-                }
-                if (first < 64) atomicMin(&best, static_cast<unsigned long long>(32 * w + first));
-            } else {
-                for (int j = 0; j <= jmax; ++j) {
-                    if (full(j)) {
-                        atomicMin(&best, static_cast<unsigned long long>(32 * w + j));
-                        break;                               // later j of this window are larger
-                    }
+            for (int o = 0; o < 16; ++o) {
+                const uint32_t x = o ? (whi << o) | (wlo >> (32 - o)) : whi;
+                const uint32_t z = x ^ kk;
+                const uint32_t hz = (z - 0x00010001u) & ~z & 0x80008000u;
+                if (__builtin_expect(hz != 0, 0)) {
+                    if ((hz & 0x80000000u) && o < first && full(o)) first = o;
+                    if ((hz & 0x00008000u) && o + 16 < first && full(o + 16)) first = o + 16;
                 }
             }
+        } else {
+            for (int j = 0; j <= jmax && first == 64; ++j)
+                if (full(j)) first = j;
         }
-        __syncthreads();
-        // a uniform exit, as in the framer's end search: flag into a register,
-        // a barrier, then the break, so no wave reads a match of the next chunk
-        const bool found = best != ULLONG_MAX;               // no later chunk holds a smaller one
-        __syncthreads();
-        if (found) break;
-    }
-    if (threadIdx.x == 0) offsets[s] = best == ULLONG_MAX ? -1 : static_cast<int64_t>(best) + m;
+        return first < 64 ? static_cast<unsigned long long>(32 * w + first) : kNoMatch;
+    });
+    if (threadIdx.x == 0) offsets[s] = at == kNoMatch ? -1 : static_cast<int64_t>(at) + m;
 }
 
 // `new QPSKDeModulator(...)` on the listed rows: the framer fields as

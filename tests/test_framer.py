@@ -722,6 +722,55 @@ def test_device_framer_start_hunt_at_chunk_edges(dev, start, end, ks):
     device_matches(dev, calls, sched, RING, want)
 
 
+DRIP_MARKERS = [(b"\x02", b"\x03"), (b"\xA5\x5A\xC3", b"\x3C\xFF")]
+_drip_cases = {}
+
+
+def drip_case(start, end):
+    """Start hunt, short calls: 5 noise bits, the start marker, a 3-byte
+    payload, the end marker and 9 tail bits arrive k bits per call, one stream
+    per k (a stream that has run out gets an empty rx).  While carry + rx is
+    shorter than the start marker the hunt has no position to test."""
+    key = (start, end)
+    if key in _drip_cases:
+        return _drip_cases[key]
+    rng = np.random.default_rng(7500 + len(start))
+    ns = len(start)
+    ks = (1, 2, 3, 5, 7, 8 * ns - 1)
+    streams, payloads = [], []
+    for _ in ks:
+        payloads.append(bytes_without(rng, 3, end))
+        streams.append(place_first(rng, to_bits(start), 5 + 8 * ns, 5) + to_bits(payloads[-1]) + to_bits(end) +
+                       K.random_bits(rng, 9))
+    n_calls = max(-(-len(st) // k) for st, k in zip(streams, ks))
+    calls = [rows_of([st[c * k: (c + 1) * k] for st, k in zip(streams, ks)], rng) for c in range(n_calls)]
+    sched = [(start, end)] * n_calls
+    want, _ = ref_calls(calls, sched, RING)
+    for s in range(len(ks)):                                       # the scenario, from the string model
+        assert [w[s][0] for w in want if w[s][0]] == [payloads[s]], s
+        hunting = [(False, 0, 0)] + [w[s][1:] for w in want[:-1]]  # the state each call starts from
+        assert any(not in_frame and rows[s][2] and carry + len(rows[s][2]) < 8 * ns
+                   for rows, (in_frame, _, carry) in zip(calls, hunting)), s
+    _drip_cases[key] = (calls, sched, want)
+    return _drip_cases[key]
+
+
+@pytest.mark.parametrize("start,end", DRIP_MARKERS)
+def test_host_framer_start_hunt_on_dripping_bits(start, end):
+    calls, sched, want = drip_case(start, end)
+    fr = Q.Framer(len(calls[0]), start, end, ring_capacity=RING)
+    for ci, rows in enumerate(calls):
+        bits, nb, off = pack_rows(rows)
+        assert fr.push(bits, nb, off, payload_cap=4096) == [w[0] for w in want[ci]], ci
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("start,end", DRIP_MARKERS)
+def test_device_framer_start_hunt_on_dripping_bits(dev, start, end):
+    calls, sched, want = drip_case(start, end)
+    device_matches(dev, calls, sched, RING, want)
+
+
 # ---------------------------------------------------------------------------
 # B4.  Low-entropy streams: markers that overlap themselves, start == end, an
 # end marker inside the start marker's tail -- where a data-parallel

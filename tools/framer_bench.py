@@ -4,7 +4,12 @@ the bit rows of one DeModulate call of a BASELINE config (C2 or C3), timed
 with HIP events over `reps` pushes, with a checksum of every payload so two
 library builds (QPSK_DEMOD_LIB) can be compared for identical output.
 
-  python tools/framer_bench.py [--config c2|c3] [--reps 10]
+  python tools/framer_bench.py [--config c2|c3] [--reps 10] [--markers present|absent]
+
+--markers absent runs the same rows with a 13-byte start marker that does not
+occur in them: the start hunt scans every chunk of every row and the
+keep-carry path runs, where the default's 1-byte markers end both searches in
+their first chunk.
 """
 import argparse
 import json
@@ -19,10 +24,16 @@ import bench  # noqa: E402
 sys.argv = _argv
 
 
+# the synthetic rows are random bits: 104 given bits sit at one position with
+# probability 2^-104, and "frames_per_call": 0.0 in the result line confirms it
+ABSENT_START = b"MESSAGE_START"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4"])
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--markers", default="present", choices=["present", "absent"])
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -43,7 +54,8 @@ def main():
     d.process_device(iq, n, bits, nbits)
     stream.synchronize()
     del iq
-    fr = Q.DeviceFramer(S, b"\x02", b"\x03", ring_capacity=1 << 16)
+    start = b"\x02" if args.markers == "present" else ABSENT_START
+    fr = Q.DeviceFramer(S, start, b"\x03", ring_capacity=1 << 16)
     fr.set_stream(stream.cuda_stream)
     offs = torch.zeros(S, dtype=torch.int64, device=dev)
     pay = torch.zeros((S, 256), dtype=torch.uint8, device=dev)
@@ -71,7 +83,7 @@ def main():
     inf, cnt, car = fr.status()
     state = int(np.asarray(inf).sum()) * 1000003 + int(np.asarray(cnt).sum()) * 31 + int(np.asarray(car).sum())
     print(json.dumps({"lib": os.path.basename(os.environ.get("QPSK_DEMOD_LIB", "in-tree")), "config": args.config,
-                      "streams": S, "tsc_ms": round(float(np.median(t_tsc)), 4),
+                      "markers": args.markers, "streams": S, "tsc_ms": round(float(np.median(t_tsc)), 4),
                       "framer_ms": round(float(np.median(t_push)), 4),
                       "framer_ms_all": [round(x, 4) for x in t_push],
                       "frames_per_call": frames / args.reps,
