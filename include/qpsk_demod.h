@@ -974,6 +974,105 @@ int qpsk_mod_modulate_bytes_fmt(qpsk_mod *m, int32_t fmt, int32_t norm, float sc
                                 int32_t mem, void *out, int64_t out_stride_elems,
                                 int64_t *n_out_elems, float *peak);
 
+/* ---------------------------------------------------------------------------
+ * Bit errors, counted where the bits are.  (Added within ABI version 3: no
+ * existing entry point, kernel or layout changed.)
+ *
+ * The reference's test bench compares what it received with what it sent
+ * (testAtDataLevel.cs:44-46) around a modulator, an impaired channel and a
+ * demodulator driven in a loop (testFullDemodChain.cs).  For packed bit rows
+ * the comparison has to find where in the sent bits a received stretch lies:
+ * the differential decoder drops the first dibit and a symbol slip of the
+ * timing loop moves the offset by 2 bits.  The definition below is the one the
+ * project reports as "BER after lock" (bench.py, ber_after_lock), restated for
+ * one stream s.
+ *
+ * rx(j) and ref(j) are bit j of the stream's rx_bits and ref_bits rows, packed
+ * MSB-first (bit 7 - j % 8 of byte j / 8) like every bit row of this ABI.
+ * R = n_rx_bits[s], N = n_ref_bits[s]; w0 = skip_bits, W = window, K =
+ * key_bits, D = search.  find(w, lo, hi) is the smallest i with lo <= i,
+ * i + K <= hi and ref(i + t) == rx(w + t) for all t < K, or -1 if there is
+ * none (an empty or inverted range gives -1).
+ *
+ *     located = 0; errs = bits = lost = slips = windows = 0
+ *     for (w = w0; w + W <= R; w += W):
+ *         windows += 1
+ *         i = located ? find(w, max(0, w + off - D), min(N, w + off + D + K))
+ *                     : find(w, 0,                   min(N, w + 4 * W))
+ *         if i < 0: lost += 1; continue               (off and located stay)
+ *         if located and i - w != off: slips += 1
+ *         located = 1; off = i - w
+ *         m = min(W, N - i)                           (>= K: the key lies inside ref)
+ *         e = #{ t < m : rx(w + t) != ref(i + t) }
+ *         tail_ok = rx[w + m - K, w + m) == ref[i + m - K, i + m)
+ *         if !tail_ok or e > m / 8 (integer division): lost += 1
+ *         else: errs += e; bits += m
+ *
+ * All positions are int64 and off may be negative.  A row with R < w0 + W
+ * yields a row of zeros, for every w0 up to INT64_MAX (the loop condition is
+ * evaluated as w <= R - W).  The first match is part of the definition: on
+ * low-entropy data the key occurs before the place a human would pick, and the
+ * counts say so.  A window that cannot be located (an error or a slip inside
+ * its key) or whose last K bits no longer line up (a slip inside it) or that
+ * holds more than one error in 8 bits is a lost window, not bit errors.
+ *
+ * Known cost, by the definition: a row that never locates scans up to
+ * min(N, w + 4 W) positions in every window.
+ */
+typedef struct qpsk_ber_params {
+    int64_t skip_bits;      /* w0: bits of every rx row left out (acquisition), >= 0        */
+    int32_t window;         /* W: bits per window, key_bits .. 2^20                         */
+    int32_t key_bits;       /* K: leading bits of a window located in ref, 1 .. 64          */
+    int32_t search;         /* D: positions searched either side of the last offset, 0 .. 2^20 */
+    int32_t reserved[3];
+} qpsk_ber_params;
+/* 8000, 2048, 64, 512: the values bench.py reports with; reserved = 0. */
+void qpsk_ber_params_init(qpsk_ber_params *p);
+typedef struct qpsk_ber_row {         /* 64 bytes, no padding */
+    int64_t bit_errors;     /* errs                                                         */
+    int64_t bits;           /* bits compared in the windows that count                      */
+    int64_t lost_windows;   /* lost                                                         */
+    int64_t slips;          /* windows located at another offset than the one before        */
+    int64_t windows;        /* windows looked at: max(0, (R - w0) / W)                      */
+    int64_t last_offset;    /* off after the last window; 0 while located == 0              */
+    int32_t located;        /* 1 once a window has been located                             */
+    int32_t reserved[3];    /* written as 0                                                 */
+} qpsk_ber_row;
+/* sizeof(qpsk_ber_row) = 64, as qpsk_link_stats_size; needs no device. */
+int qpsk_ber_row_size(void);
+/*
+ * qpsk_ber_count: every pointer is host memory, no device is needed; out[s]
+ * receives stream s's row.  qpsk_ber_count_device: every pointer but p is
+ * device memory, the counting kernel is ordered on hip_stream (NULL = the null
+ * stream) and the call returns without waiting for it; out_dev[s] is complete
+ * once hip_stream has run it.  The rows the device form writes equal the host
+ * form's byte for byte.
+ *
+ * Checked on the host before anything is launched or written, for every
+ * n_streams: a null pointer is QPSK_ERR_ARGUMENT_NULL; n_streams < 0, a
+ * negative stride or (device form) out_dev not 8-byte aligned is
+ * QPSK_ERR_ARGUMENT; skip_bits < 0, key_bits outside [1, 64], window outside
+ * [key_bits, 2^20] or search outside [0, 2^20] is QPSK_ERR_OUT_OF_RANGE.
+ * n_streams == 0 is then QPSK_OK and does nothing.  The host form also
+ * refuses a count n_rx_bits[s] or n_ref_bits[s] that is negative, larger
+ * than 8 * its stride or not below 2^61 with QPSK_ERR_ARGUMENT, and writes
+ * nothing.  The device
+ * form cannot see the counts: its kernel treats such a row as R = 0 or N = 0
+ * respectively (a row of zeros, or one whose windows are all lost).
+ *
+ * Bit rows may have any byte alignment and any stride (row s starts at
+ * s * stride bytes).  Bits at or past n_*_bits[s] are never interpreted, the
+ * rest of the last byte included, and no byte at or past ceil(n / 8) of a row
+ * is read.
+ */
+int qpsk_ber_count(const qpsk_ber_params *p, const uint8_t *rx_bits, int64_t rx_stride_bytes,
+                   const int64_t *n_rx_bits, const uint8_t *ref_bits, int64_t ref_stride_bytes,
+                   const int64_t *n_ref_bits, int32_t n_streams, qpsk_ber_row *out);
+int qpsk_ber_count_device(const qpsk_ber_params *p, const uint8_t *rx_bits, int64_t rx_stride_bytes,
+                          const int64_t *n_rx_bits, const uint8_t *ref_bits, int64_t ref_stride_bytes,
+                          const int64_t *n_ref_bits, int32_t n_streams, qpsk_ber_row *out_dev,
+                          void *hip_stream);
+
 const char *qpsk_last_error(void);
 int qpsk_abi_version(void);
 

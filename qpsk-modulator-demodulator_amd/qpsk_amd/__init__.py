@@ -162,6 +162,12 @@ class ModParams(C.Structure):
     ]
 
 
+class BerParams(C.Structure):
+    """qpsk_ber_params: skip_bits, window, key_bits and search of the bit-error counter."""
+    _fields_ = [("skip_bits", C.c_int64), ("window", C.c_int32), ("key_bits", C.c_int32), ("search", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 class LoopShape(C.Structure):
     """qpsk_loop_shape (include/qpsk_demod.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -359,6 +365,14 @@ def lib():
         getattr(L, owner + "_streams_state_bytes").restype = C.c_int64
         getattr(L, owner + "_get_streams_state").argtypes = [C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_int64]
         getattr(L, owner + "_set_streams_state").argtypes = [C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_int64]
+    # bit errors where the bits are: params, rx rows, ref rows, S, out (, stream)
+    ber = [C.POINTER(BerParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+           C.c_void_p]
+    L.qpsk_ber_params_init.argtypes = [C.POINTER(BerParams)]
+    L.qpsk_ber_params_init.restype = None
+    L.qpsk_ber_row_size.restype = C.c_int
+    L.qpsk_ber_count.argtypes = ber
+    L.qpsk_ber_count_device.argtypes = ber + [C.c_void_p]
     _lib = real
     return real
 
@@ -400,6 +414,7 @@ EXPORTED_SYMBOLS = [
     "qpsk_framer_dev_reset_streams", "qpsk_frames_pack_device", "qpsk_rx_attach_framer", "qpsk_rx_set_markers",
     "qpsk_rx_frames_bytes", "qpsk_rx_collect_frames", "qpsk_rx_reset_streams",
     "qpsk_quantise_iq", "qpsk_mod_modulate_fmt", "qpsk_mod_modulate_bytes_fmt",
+    "qpsk_ber_params_init", "qpsk_ber_row_size", "qpsk_ber_count", "qpsk_ber_count_device",
 ]
 
 _EXC = {
@@ -487,6 +502,110 @@ class LinkStats(C.Structure):
 def link_stats_size() -> int:
     """sizeof(qpsk_link_stats) as the library was built (needs no device)."""
     return int(lib().qpsk_link_stats_size())
+
+
+# qpsk_ber_row (include/qpsk_demod.h): one 64-byte row per stream
+BER_ROW_DTYPE = np.dtype([("bit_errors", "i8"), ("bits", "i8"), ("lost_windows", "i8"), ("slips", "i8"),
+                          ("windows", "i8"), ("last_offset", "i8"), ("located", "i4"), ("reserved", "i4", (3,))])
+
+
+class BerRow(C.Structure):
+    """qpsk_ber_row as a ctypes structure (BER_ROW_DTYPE is the same layout)."""
+    _fields_ = [("bit_errors", C.c_int64), ("bits", C.c_int64), ("lost_windows", C.c_int64), ("slips", C.c_int64),
+                ("windows", C.c_int64), ("last_offset", C.c_int64), ("located", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+def ber_row_size() -> int:
+    """sizeof(qpsk_ber_row) as the library was built (needs no device)."""
+    return int(lib().qpsk_ber_row_size())
+
+
+def ber_params(skip_bits=None, window=None, key_bits=None, search=None) -> BerParams:
+    """qpsk_ber_params_init's values (8000, 2048, 64, 512: bench.py's), then the ones given."""
+    p = BerParams()
+    lib().qpsk_ber_params_init(C.byref(p))
+    for name, v in (("skip_bits", skip_bits), ("window", window), ("key_bits", key_bits), ("search", search)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def ber_count(rx, n_rx, ref, n_ref=None, **params) -> np.ndarray:
+    """qpsk_ber_count on host rows (needs no device): rx [S, B] and ref [S, B']
+    uint8, packed MSB-first, rows of any stride; n_rx [S] bit counts; n_ref
+    None = the whole row, 8 * ref.shape[1], as bench.py's ber_after_lock takes
+    it.  params: skip_bits, window, key_bits, search.  Returns [S] rows of
+    BER_ROW_DTYPE."""
+    rx, ref = np.asarray(rx), np.asarray(ref)
+    if rx.dtype != np.uint8 or ref.dtype != np.uint8 or rx.ndim != 2 or ref.ndim != 2:
+        raise ValueError("rx and ref are [S, bytes] uint8 rows")
+    S = rx.shape[0]
+    if ref.shape[0] != S:
+        raise ValueError("rx and ref hold different numbers of rows")
+    if S == 0:
+        return np.zeros(0, BER_ROW_DTYPE)
+    if (rx.shape[1] > 1 and rx.strides[1] != 1) or (ref.shape[1] > 1 and ref.strides[1] != 1):
+        raise ValueError("the bytes of a row must be contiguous")
+    n_rx = np.ascontiguousarray(n_rx, dtype=np.int64).reshape(-1)
+    n_ref = (np.full(S, 8 * ref.shape[1], np.int64) if n_ref is None
+             else np.ascontiguousarray(n_ref, dtype=np.int64).reshape(-1))
+    if n_rx.size != S or n_ref.size != S:
+        raise ValueError("one bit count per row")
+    out = np.zeros(S, BER_ROW_DTYPE)
+    # the caller's own strides; numpy gives a new axis stride 0, and then a lone row's width serves
+    rx_stride = rx.strides[0] if rx.strides[0] > 0 or S > 1 else rx.shape[1]
+    ref_stride = ref.strides[0] if ref.strides[0] > 0 or S > 1 else ref.shape[1]
+    _check(lib().qpsk_ber_count(C.byref(ber_params(**params)), rx.ctypes.data, rx_stride, n_rx.ctypes.data,
+                                ref.ctypes.data, ref_stride, n_ref.ctypes.data, S, out.ctypes.data))
+    return out
+
+
+def ber_count_device(rx_dev, n_rx_dev, ref_dev, n_ref_dev, out_dev=None, hip_stream=None, **params):
+    """qpsk_ber_count_device on torch CUDA tensors, nothing copied: rx_dev [S, B]
+    and ref_dev [S, B'] uint8 rows (any stride and alignment), n_rx_dev and
+    n_ref_dev [S] int64 on the device, out_dev [S, 64] uint8 (8-byte aligned;
+    made here if None).  The kernel is ordered on hip_stream, or on torch's
+    current stream if None, and the call does not wait for it.  Returns out_dev;
+    out_dev.cpu().numpy().view(BER_ROW_DTYPE).reshape(-1) are its rows."""
+    import torch
+    for t, what in ((rx_dev, "rx_dev"), (ref_dev, "ref_dev")):
+        if t.dtype != torch.uint8 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"{what} must be a contiguous-row uint8 [n_streams, bytes] tensor")
+    S = int(rx_dev.shape[0])
+    for t, what in ((n_rx_dev, "n_rx_dev"), (n_ref_dev, "n_ref_dev")):
+        if t.dtype != torch.int64 or t.numel() != S or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous int64 [n_streams] tensor")
+    if ref_dev.shape[0] != S:
+        raise ValueError("rx_dev and ref_dev hold different numbers of rows")
+    if out_dev is not None and (out_dev.dtype != torch.uint8 or not out_dev.is_contiguous()
+                                or out_dev.numel() != S * BER_ROW_DTYPE.itemsize):
+        raise ValueError("out_dev must be a contiguous uint8 tensor of 64 bytes a stream")
+    if out_dev is None:
+        out_dev = torch.empty((S, BER_ROW_DTYPE.itemsize), dtype=torch.uint8, device=rx_dev.device)
+    if S == 0:
+        return out_dev
+    if hip_stream is None:
+        hip_stream = torch.cuda.current_stream(rx_dev.device).cuda_stream
+    # the caller's own strides; a lone row of stride 0 (an expanded view) takes its width, as in ber_count
+    rx_stride = rx_dev.stride(0) if rx_dev.stride(0) > 0 or S > 1 else rx_dev.shape[1]
+    ref_stride = ref_dev.stride(0) if ref_dev.stride(0) > 0 or S > 1 else ref_dev.shape[1]
+    _check(lib().qpsk_ber_count_device(
+        C.byref(ber_params(**params)), rx_dev.data_ptr(), rx_stride, n_rx_dev.data_ptr(), ref_dev.data_ptr(),
+        ref_stride, n_ref_dev.data_ptr(), S, out_dev.data_ptr(), C.c_void_p(hip_stream or 0)))
+    return out_dev
+
+
+def ber_summary(rows) -> dict:
+    """The figures bench.py reports under "ber_after_lock", summed over rows of BER_ROW_DTYPE."""
+    rows = np.asarray(rows)
+    if rows.dtype != BER_ROW_DTYPE:                     # [S, 64] uint8, as ber_count_device returns them
+        rows = np.ascontiguousarray(rows).view(BER_ROW_DTYPE)
+    rows = rows.reshape(-1)
+    errs, bits = int(rows["bit_errors"].sum()), int(rows["bits"].sum())
+    return {"bit_errors": errs, "bits": bits, "ber": (errs / bits) if bits else None,
+            "lost_windows": int(rows["lost_windows"].sum()), "symbol_slips": int(rows["slips"].sum()),
+            "streams": int(rows.size)}
 
 
 def state_blob_check(p: DemodParams, n_streams: int, blob: bytes):
