@@ -1073,6 +1073,136 @@ int qpsk_ber_count_device(const qpsk_ber_params *p, const uint8_t *rx_bits, int6
                           const int64_t *n_ref_bits, int32_t n_streams, qpsk_ber_row *out_dev,
                           void *hip_stream);
 
+/* ---------------------------------------------------------------------------
+ * The test bench's channel on the device: the LO pair and the noise, batched.
+ * (Added within ABI version 3: no existing entry point, kernel or layout
+ * changed.)
+ *
+ * The reference's end-to-end test (testAtDataLevel.cs:24-46) multiplies every
+ * sample of ModulateTextUtf8's output by
+ * txNCO.NextSample() * rxNCO.NextSample().Conjugate() before DeModulateTextUtf8;
+ * testFullDemodChain.cs:59-73 adds NoiseGenerator.GenerateIqNoise's samples
+ * ahead of the same LO pair.  One handle is that channel for S independent
+ * streams; one call takes rows where the modulator leaves them and leaves
+ * rows the demodulator takes.
+ *
+ * LO pair.  Each stream has two oscillators, each LocalOscilator.cs:5-194:
+ *   construction (:20-60)   max = |ppm|; static = max > 0 ? (u * 2 - 1) * max : 0
+ *                           (one draw); drift = 0; total = static;
+ *                           cur_hz = lo_hz * (1 + total * 1e-6); phase = wrap(phase0);
+ *                           interval = max(1, (int)(sample_rate * 1e-3)); counter = 0
+ *   NextSample (:150-194)   max > 0: every interval-th call draws
+ *                           step = (u * 2 - 1) * (max * 0.001); drift += step;
+ *                           total = static + drift, clamped to +-max (drift =
+ *                           total - static then); cur_hz as above.
+ *                           phase = wrap(phase + 2 pi cur_hz / sample_rate);
+ *                           the sample is (cos phase, sin phase), glibc's double
+ *                           cos and sin.  max = 0: cur_hz = lo_hz, no draws.
+ *   wrap(x)                 fmod(x, 2 pi), + 2 pi if that is negative
+ *   u                       splitmix64: (z >> 11) * 2^-53
+ * Stream g = first_stream + row seeds its transmit oscillator with tx_seed + g
+ * and its receive oscillator with rx_seed + g.  With a = tx sample, b =
+ * conj(rx sample), x the input sample, all double, System.Numerics.Complex's
+ * product and no contraction (testAtDataLevel.cs:39-42):
+ *   l = (a.re b.re - a.im b.im, a.im b.re + a.re b.im)
+ *   y = (x.re l.re - x.im l.im, x.im l.re + x.re l.im), each rounded to float once.
+ *
+ * Noise (noise_rms > 0; HelperModels.cs:17-45 with linearRms = noise_rms).  For
+ * the sample at the stream's absolute position pos (samples the stream has
+ * taken since its construction or reset, kept in its state):
+ *   h = noise_seed ^ (g << 40) ^ pos ^ 0xA5A5A5A5; u1 = 1 - u(h); u2 = 1 - u(h)
+ *   mag = sqrt(-2 log(u1)) * noise_rms; ph = 2 pi u2
+ *   n = ((float)(mag cos ph), (float)(mag sin ph)), each clamped to [-1, 1]
+ *   x = (x.re + (double)n.re, x.im + (double)n.im) ahead of the product above
+ *   (testFullDemodChain.cs:73)
+ * cos and sin are glibc's, sqrt is correctly rounded, log is the device
+ * library's (the one operation of the channel that is not pinned bit for bit).
+ * The draw depends on pos alone, so the noise does not depend on how calls cut
+ * a stream.
+ *
+ * Formats.  An input sample's value is what qpsk_demod_process_fmt reads:
+ * CF32 as it stands (scale_in is ignored), (float)x * scale_in for CS16 and CS8,
+ * (float)((int)x - 128) * scale_in for CU8.  The float result y goes through
+ * QPSK_MOD_NORM_FIXED of qpsk_quantise_iq with scale_out: CF32 stores
+ * y * scale_out (1.0f: y itself), an integer row equals qpsk_quantise_iq of the
+ * CF32 row.  Per-row peak normalisation needs a second pass over the row and
+ * is not offered: norm_out other than QPSK_MOD_NORM_FIXED is
+ * QPSK_ERR_ARGUMENT.  Not modelled: multipath, a sample-clock offset.
+ */
+typedef struct qpsk_channel_params {
+    double sample_rate;         /* NCO sampleRate (LocalOscilator.cs:20), > 0             */
+    double lo_hz;               /* NCO frequencyHz of both LOs: 100e6 (testAtDataLevel.cs:27-28) */
+    double tx_ppm, rx_ppm;      /* NCO ppmError: 1 and 1 (:27-28); the sign is dropped (:30) */
+    double tx_phase0, rx_phase0;/* NCO initialPhase: 0                                    */
+    uint64_t tx_seed, rx_seed;  /* stream g draws from tx_seed + g and rx_seed + g        */
+    double noise_rms;           /* linearRms of GenerateIqNoise; 0 = no noise             */
+    uint64_t noise_seed;
+    int64_t first_stream;       /* global id of row 0: a shard equals rows first_stream.. of the batch */
+    int32_t device;             /* HIP device ordinal                                     */
+    int32_t reserved[7];
+} qpsk_channel_params;
+typedef struct qpsk_channel qpsk_channel;
+/* lo_hz = 100e6, tx_ppm = rx_ppm = 1, phases 0, tx_seed = 1000, rx_seed = 2000,
+ * noise_rms = 0, noise_seed = 0, first_stream = 0, device = 0, reserved = 0. */
+void qpsk_channel_params_init(qpsk_channel_params *p, double sample_rate);
+/* new NCO(lo_hz, sample_rate, ppm, phase0) twice per stream, pos = 0.
+ * sample_rate not finite or <= 0, a non-finite lo_hz, ppm or phase0, noise_rms
+ * not finite or < 0, or first_stream < 0: QPSK_ERR_OUT_OF_RANGE; n_streams <
+ * 1: QPSK_ERR_ARGUMENT; all before a device is touched. */
+int qpsk_channel_create(const qpsk_channel_params *p, int32_t n_streams, qpsk_channel **out);
+int qpsk_channel_destroy(qpsk_channel *ch);
+/* Calls are ordered on the handle's stream: its own, or the caller's
+ * (NULL = back to an own one), as qpsk_mod_set_stream. */
+int qpsk_channel_set_stream(qpsk_channel *ch, void *hip_stream);
+/* One call: stream s takes lengths[s] samples (lengths == NULL: n_samples for
+ * all; lengths is host memory, each 0 .. n_samples) from row s of in,
+ * [n_streams][stride_in] elements of fmt_in, and writes as many to row s of
+ * out, [n_streams][stride_out] elements of fmt_out; strides count elements
+ * (two per sample) and must hold 2 * n_samples.  Elements past a row's length
+ * are not written.  mem covers in and out.  out == in is allowed when fmt_out
+ * == fmt_in and the strides are equal (the reference works in place); rows
+ * that overlap in any other way are undefined.  Device rows follow the rules
+ * of qpsk_demod_process_fmt: an even stride, CS16 rows 4-byte and 8-bit rows
+ * 2-byte aligned, CF32 rows 4-byte aligned (rows not 8-byte aligned are read
+ * and written one float at a time), else QPSK_ERR_ARGUMENT.  scale_out, and
+ * scale_in of an integer format, must be finite and > 0, else
+ * QPSK_ERR_OUT_OF_RANGE.  A rejected call changes neither the state nor out.
+ * A device call without lengths is queued on the handle's stream and returns;
+ * a call with lengths or with host rows returns when it has run.  The
+ * caller's current device is the same on return. */
+int qpsk_channel_apply_fmt(qpsk_channel *ch, int32_t fmt_in, const void *in, int64_t stride_in, float scale_in,
+                           int32_t fmt_out, int32_t norm_out, void *out, int64_t stride_out, float scale_out,
+                           int64_t n_samples, const int64_t *lengths, int32_t mem);
+/* State: per stream 128 bytes, no header,
+ *   two oscillators (tx, rx) of 56 bytes: double static_ppm, drift_ppm,
+ *   total_ppm, cur_hz, phase; int64 counter; uint64 rng
+ *   int64 pos; 8 reserved bytes (0)
+ * qpsk_channel_state_size() = 128, needs no device.  get_state / set_state move
+ * all n_streams records (buf_bytes = 128 * n_streams, host memory) behind the
+ * calls queued so far.  set_state runs qpsk_channel_state_check first and
+ * changes nothing when it fails. */
+int qpsk_channel_state_size(void);
+int qpsk_channel_get_state(qpsk_channel *ch, void *host_buf, int64_t buf_bytes);
+int qpsk_channel_set_state(qpsk_channel *ch, const void *host_buf, int64_t buf_bytes);
+/* new NCO(...) twice and pos = 0 for the listed rows (a list as
+ * qpsk_stream_list_check accepts it); the other rows are untouched. */
+int qpsk_channel_reset_streams(qpsk_channel *ch, const int32_t *streams, int32_t n);
+/* What a state must satisfy for handle parameters p (host only, no device):
+ * buf_bytes = 128 * n_streams; per oscillator every double finite, |static_ppm|
+ * and |total_ppm| <= |ppm|, total_ppm = static_ppm + drift_ppm to within the
+ * two roundings the clamp leaves (2^-50 |ppm|), cur_hz = lo_hz * (1 + total_ppm
+ * * 1e-6) exactly, phase in [0, 2 pi] (-0 included: fmod's remainder of a negative
+ * multiple of 2 pi; wrap's "+ 2 pi" rounds a tiny negative remainder to 2 pi
+ * itself), counter in [0, interval); pos >= 0; reserved = 0.
+ * A failure is QPSK_ERR_ARGUMENT and names stream, oscillator and field in
+ * qpsk_last_error. */
+int qpsk_channel_state_check(const qpsk_channel_params *p, int32_t n_streams, const void *buf, int64_t buf_bytes);
+/* Streams one workgroup of the channel kernel holds and samples one block of
+ * its phase scan covers: the batch sizes and call lengths at which the kernel
+ * changes tiles (tests/test_gpu_channel.py spans them). */
+#define QPSK_CHANNEL_TILE_STREAMS 16
+#define QPSK_CHANNEL_BLOCK_SAMPLES 64
+
 const char *qpsk_last_error(void);
 int qpsk_abi_version(void);
 

@@ -1,0 +1,430 @@
+// qpsk_channel.hip -- the test bench's channel (include/qpsk_demod.h, "The test
+// bench's channel on the device") on S streams: the kernel and the entry points
+// that need a device.  The oscillator itself, the state record and the state
+// check are qpsk_channel.h / qpsk_channel.cpp.
+//
+// channel_kernel: one workgroup of four waves holds QPSK_CHANNEL_TILE_STREAMS =
+// 16 streams, i.e. 32 oscillators, and walks their rows in blocks of
+// QPSK_CHANNEL_BLOCK_SAMPLES = 64 samples.
+//
+//   wave 0, the scan   lane l steps oscillator l & 1 (0 tx, 1 rx) of stream
+//                      l >> 1: chan_nco_step, whose phase add and wrap round in
+//                      every sample and so stay one serial chain per oscillator,
+//                      with the drift draw and the clamp every `interval`
+//                      samples.  It leaves the block's phases in LDS.
+//   waves 1..3, trig   take the block the scan finished one step earlier (the
+//                      phases are double buffered, one barrier a block): a wave
+//                      takes whole rows, a lane one sample, so a row's 64
+//                      samples are one coalesced load and one coalesced store.
+//                      Two qpsk_glibc_sincos (branch-free form, table in LDS),
+//                      the optional noise sample (a third one), the two complex
+//                      products in double, one rounding to float, the quantiser.
+//
+// A lane reads its sample before it writes it and no other lane touches it, so
+// out == in works.  Lanes past a row's length load and store nothing.  The
+// scan lanes carry the oscillators in registers across the whole call and
+// write the state back once, behind the last barrier; pos is read by the trig
+// lanes before that and advanced by the tx lane.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "qpsk_channel.h"
+#include "qpsk_demod.h"
+#include "qpsk_device.h"
+#include "qpsk_glibc_trig.h"
+#include "qpsk_internal.h"
+#include "qpsk_quantise.h"
+
+struct qpsk_channel {
+    qpsk_channel_params p{};
+    int S = 0;
+    qpsk::Stream stream;                     // in front of the buffers, which go first
+    qpsk::DevBuf<qpsk::ChanState> d_state;   // [S]
+    qpsk::DevBuf<int64_t> d_len;             // [S]: a call's checked lengths
+    qpsk::DevBuf<uint8_t> d_in, d_out;       // host calls: 16-byte-pitched rows
+};
+
+namespace {
+
+using qpsk::ChanNco;
+using qpsk::ChanNcoConst;
+using qpsk::ChanState;
+using qpsk::fail;
+
+constexpr int kStreams = QPSK_CHANNEL_TILE_STREAMS;
+constexpr int kBlock = QPSK_CHANNEL_BLOCK_SAMPLES;
+constexpr int kThreads = 256;
+constexpr int kTrigWaves = kThreads / 64 - 1;
+constexpr int kPitch = kBlock + 1;           // doubles a row of phases takes: the scan lanes' stores spread over the banks
+static_assert(2 * kStreams <= 64, "one scan lane per oscillator, in one wave");
+static_assert(kBlock == 64, "a trig lane takes one sample of a block");
+
+struct ChanArgs {
+    ChanNcoConst tx, rx;
+    double noise_rms;
+    uint64_t noise_seed;
+    uint64_t first_stream;
+    const void *in;
+    void *out;
+    int64_t in_stride, out_stride;   // elements
+    float scale_in, scale_out;
+    int fmt_in, fmt_out;
+    int in_pair, out_pair;           // CF32 rows 8-byte aligned: one access a sample
+    const int64_t *lengths;          // device, checked; nullptr: n for every stream
+    int64_t n;
+    ChanState *state;
+    int S;
+};
+
+// sample i of a row of fmt as the demodulator reads it
+__device__ __forceinline__ float2 load_sample(const void *row, int fmt, int pair, int64_t i, float scale) {
+    switch (fmt) {
+    case QPSK_FMT_CF32: {
+        const float *r = static_cast<const float *>(row) + 2 * i;
+        if (pair) return *reinterpret_cast<const float2 *>(r);
+        return make_float2(r[0], r[1]);
+    }
+    case QPSK_FMT_CS16: {
+        const short2 v = *reinterpret_cast<const short2 *>(static_cast<const int16_t *>(row) + 2 * i);
+        return make_float2(static_cast<float>(v.x) * scale, static_cast<float>(v.y) * scale);
+    }
+    case QPSK_FMT_CS8: {
+        const char2 v = *reinterpret_cast<const char2 *>(static_cast<const int8_t *>(row) + 2 * i);
+        return make_float2(static_cast<float>(v.x) * scale, static_cast<float>(v.y) * scale);
+    }
+    default: {
+        const uchar2 v = *reinterpret_cast<const uchar2 *>(static_cast<const uint8_t *>(row) + 2 * i);
+        return make_float2(static_cast<float>(static_cast<int>(v.x) - 128) * scale,
+                           static_cast<float>(static_cast<int>(v.y) - 128) * scale);
+    }
+    }
+}
+
+__device__ __forceinline__ void store_sample(void *row, int fmt, int pair, int64_t i, float2 y, float scale) {
+    switch (fmt) {
+    case QPSK_FMT_CF32: {
+        float *r = static_cast<float *>(row) + 2 * i;
+        const float2 v = make_float2(qpsk::quant_scaled(y.x, scale), qpsk::quant_scaled(y.y, scale));
+        if (pair) *reinterpret_cast<float2 *>(r) = v;
+        else r[0] = v.x, r[1] = v.y;
+        return;
+    }
+    case QPSK_FMT_CS16:
+        *reinterpret_cast<short2 *>(static_cast<int16_t *>(row) + 2 * i) =
+            make_short2(static_cast<short>(qpsk::quant_fixed(QPSK_FMT_CS16, y.x, scale)),
+                        static_cast<short>(qpsk::quant_fixed(QPSK_FMT_CS16, y.y, scale)));
+        return;
+    case QPSK_FMT_CS8:
+        *reinterpret_cast<char2 *>(static_cast<int8_t *>(row) + 2 * i) =
+            make_char2(static_cast<signed char>(qpsk::quant_fixed(QPSK_FMT_CS8, y.x, scale)),
+                       static_cast<signed char>(qpsk::quant_fixed(QPSK_FMT_CS8, y.y, scale)));
+        return;
+    default:
+        *reinterpret_cast<uchar2 *>(static_cast<uint8_t *>(row) + 2 * i) =
+            make_uchar2(static_cast<unsigned char>(qpsk::quant_fixed(QPSK_FMT_CU8, y.x, scale)),
+                        static_cast<unsigned char>(qpsk::quant_fixed(QPSK_FMT_CU8, y.y, scale)));
+        return;
+    }
+}
+
+// Math.Clamp(v, -1.0f, 1.0f): a NaN stays
+__device__ __forceinline__ float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
+
+__device__ __forceinline__ int64_t row_length(const ChanArgs &a, int s) { return a.lengths ? a.lengths[s] : a.n; }
+
+__global__ __launch_bounds__(kThreads) void channel_kernel(ChanArgs a) {
+    __shared__ double tab[440];
+    __shared__ double ph[2][2 * kStreams][kPitch];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int s0 = blockIdx.x * kStreams;
+    for (int k = tid; k < 440; k += kThreads) tab[k] = qpsk_gl_sincostab_dev[k];
+
+    // the longest row of this workgroup's streams: the same in every lane
+    int64_t n_wg = 0;
+    for (int k = 0; k < kStreams && s0 + k < a.S; ++k) {
+        const int64_t len = row_length(a, s0 + k);
+        n_wg = len > n_wg ? len : n_wg;
+    }
+    const int64_t blocks = (n_wg + kBlock - 1) / kBlock;
+
+    // scan lanes: wave 0, one per oscillator of a stream that exists
+    const int ss = s0 + (lane >> 1);
+    const bool scan = wave == 0 && lane < 2 * kStreams && ss < a.S;
+    const bool is_rx = lane & 1;
+    const ChanNcoConst c = is_rx ? a.rx : a.tx;
+    ChanNco nco{};
+    double inc = 0.0;
+    int64_t scan_len = 0;
+    if (scan) {
+        nco = is_rx ? a.state[ss].rx : a.state[ss].tx;
+        inc = qpsk::chan_inc(c, nco.cur_hz);
+        scan_len = row_length(a, ss);
+    }
+    __syncthreads();   // the table
+
+    const int64_t in_eb = a.fmt_in == QPSK_FMT_CF32 ? 4 : (a.fmt_in == QPSK_FMT_CS16 ? 2 : 1);
+    const int64_t out_eb = a.fmt_out == QPSK_FMT_CF32 ? 4 : (a.fmt_out == QPSK_FMT_CS16 ? 2 : 1);
+    for (int64_t b = 0; b <= blocks; ++b) {
+        if (wave == 0) {
+            if (scan && b < blocks) {
+                const int64_t left = scan_len - b * kBlock;
+                const int m = left < kBlock ? static_cast<int>(left > 0 ? left : 0) : kBlock;
+                double *row = ph[b & 1][lane];
+                for (int i = 0; i < m; ++i) row[i] = qpsk::chan_nco_step(c, nco, inc);
+            }
+        } else if (b > 0) {
+            const int64_t i = (b - 1) * kBlock + lane;
+            for (int r = wave - 1; r < kStreams && s0 + r < a.S; r += kTrigWaves) {
+                const int s = s0 + r;
+                if (i >= row_length(a, s)) continue;
+                const double pt = ph[(b - 1) & 1][2 * r][lane], pr = ph[(b - 1) & 1][2 * r + 1][lane];
+                double ar, ai, br, bi;
+                qpsk_glibc_sincos_bf_k(pt, tab, &ai, &ar, 0);   // both phases lie in [0, 2 pi]
+                qpsk_glibc_sincos_bf_k(pr, tab, &bi, &br, 0);
+                bi = -bi;                                       // Conjugate
+                const double lr = (ar * br) - (ai * bi);        // System.Numerics.Complex *
+                const double li = (ai * br) + (ar * bi);
+                const char *irow = static_cast<const char *>(a.in) + static_cast<int64_t>(s) * a.in_stride * in_eb;
+                const float2 x = load_sample(irow, a.fmt_in, a.in_pair, i, a.scale_in);
+                double xr = x.x, xi = x.y;
+                if (a.noise_rms > 0.0) {
+                    double u1, u2, sn, cs;
+                    qpsk::chan_noise_uniforms(a.noise_seed, a.first_stream + static_cast<uint64_t>(s),
+                                              a.state[s].pos + i, &u1, &u2);
+                    const double mag = sqrt(-2.0 * log(u1)) * a.noise_rms;
+                    qpsk_glibc_sincos_bf_k(qpsk::kChanTwoPi * u2, tab, &sn, &cs, 0);   // (0, 2 pi]
+                    xr += static_cast<double>(clamp1(static_cast<float>(mag * cs)));
+                    xi += static_cast<double>(clamp1(static_cast<float>(mag * sn)));
+                }
+                const double yr = (xr * lr) - (xi * li);
+                const double yi = (xi * lr) + (xr * li);
+                char *orow = static_cast<char *>(a.out) + static_cast<int64_t>(s) * a.out_stride * out_eb;
+                store_sample(orow, a.fmt_out, a.out_pair, i, make_float2(static_cast<float>(yr), static_cast<float>(yi)),
+                             a.scale_out);
+            }
+        }
+        __syncthreads();
+    }
+    // every read of pos lies in front of the last barrier
+    if (scan) {
+        if (is_rx) {
+            a.state[ss].rx = nco;
+        } else {
+            a.state[ss].tx = nco;
+            a.state[ss].pos += scan_len;
+        }
+    }
+}
+
+// the caller's current device, put back when a call returns
+struct DeviceGuard {
+    int prev = -1;
+    DeviceGuard() {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+int staged(hipError_t e) { return e == hipSuccess ? QPSK_OK : fail(QPSK_ERR_DEVICE, "hipMalloc (channel staging)"); }
+
+int64_t elem_bytes(int fmt) { return qpsk_fmt_sample_bytes(fmt) / 2; }
+
+// what device rows of fmt must satisfy (qpsk_demod_process_fmt's rules)
+int check_device_rows(const char *what, int fmt, const void *rows, int64_t stride) {
+    if (stride & 1) return fail(QPSK_ERR_ARGUMENT, std::string("device ") + what + " stride must be even");
+    const uintptr_t align = fmt == QPSK_FMT_CS8 || fmt == QPSK_FMT_CU8 ? 2 : 4;
+    if (reinterpret_cast<uintptr_t>(rows) % align)
+        return fail(QPSK_ERR_ARGUMENT, std::string("device ") + what + " rows must be " + std::to_string(align) +
+                                           "-byte aligned");
+    return QPSK_OK;
+}
+
+bool pair_rows(int fmt, const void *rows, int64_t stride) {
+    return fmt != QPSK_FMT_CF32 || (reinterpret_cast<uintptr_t>(rows) % 8 == 0 && stride % 2 == 0);
+}
+
+ChanArgs base_args(const qpsk_channel *ch) {
+    ChanArgs a{};
+    a.tx = qpsk::chan_nco_const(ch->p.lo_hz, ch->p.sample_rate, ch->p.tx_ppm);
+    a.rx = qpsk::chan_nco_const(ch->p.lo_hz, ch->p.sample_rate, ch->p.rx_ppm);
+    a.noise_rms = ch->p.noise_rms;
+    a.noise_seed = ch->p.noise_seed;
+    a.first_stream = static_cast<uint64_t>(ch->p.first_stream);
+    a.state = ch->d_state;
+    a.S = ch->S;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qpsk_channel_create(const qpsk_channel_params *p, int32_t n_streams, qpsk_channel **out) {
+    if (!out) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    *out = nullptr;
+    int rc;
+    if ((rc = qpsk::chan_check_params(p, n_streams))) return rc;
+    DeviceGuard guard;
+    auto *ch = new qpsk_channel();
+    ch->p = *p;
+    ch->S = n_streams;
+    std::vector<ChanState> st(n_streams);
+    for (int32_t s = 0; s < n_streams; ++s) st[s] = qpsk::chan_state_new(*p, s);
+    if (hipSetDevice(p->device) != hipSuccess || ch->stream.create(hipStreamNonBlocking) != hipSuccess ||
+        ch->d_state.alloc(n_streams) != hipSuccess || ch->d_len.alloc(n_streams) != hipSuccess ||
+        hipMemcpy(ch->d_state, st.data(), st.size() * sizeof(ChanState), hipMemcpyHostToDevice) != hipSuccess) {
+        delete ch;
+        return fail(QPSK_ERR_DEVICE, "channel device set-up failed (no GPU?)");
+    }
+    *out = ch;
+    return QPSK_OK;
+}
+
+int qpsk_channel_destroy(qpsk_channel *ch) {
+    if (!ch) return QPSK_OK;
+    DeviceGuard guard;
+    (void)hipSetDevice(ch->p.device);
+    if (ch->stream) (void)hipStreamSynchronize(ch->stream);
+    delete ch;
+    return QPSK_OK;
+}
+
+int qpsk_channel_set_stream(qpsk_channel *ch, void *hip_stream) {
+    if (!ch) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    DeviceGuard guard;
+    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
+    QPSK_HIP_TRY(hipStreamSynchronize(ch->stream));
+    QPSK_HIP_TRY(ch->stream.rebind(hip_stream));
+    return QPSK_OK;
+}
+
+int qpsk_channel_apply_fmt(qpsk_channel *ch, int32_t fmt_in, const void *in, int64_t stride_in, float scale_in,
+                           int32_t fmt_out, int32_t norm_out, void *out, int64_t stride_out, float scale_out,
+                           int64_t n_samples, const int64_t *lengths, int32_t mem) {
+    if (!ch) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    if (!qpsk::quant_fmt_known(fmt_in) || !qpsk::quant_fmt_known(fmt_out))
+        return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
+    if (norm_out != QPSK_MOD_NORM_FIXED)
+        return fail(QPSK_ERR_ARGUMENT, norm_out == QPSK_MOD_NORM_PEAK
+                                           ? "the channel does not normalise rows to their peak (a second pass): "
+                                             "QPSK_MOD_NORM_FIXED only"
+                                           : "unknown norm");
+    if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
+    if (fmt_in != QPSK_FMT_CF32 && !qpsk::quant_scale_ok(scale_in))
+        return fail(QPSK_ERR_OUT_OF_RANGE, "scale_in must be finite and > 0");
+    if (!qpsk::quant_scale_ok(scale_out)) return fail(QPSK_ERR_OUT_OF_RANGE, "scale_out must be finite and > 0");
+    if (n_samples < 0) return fail(QPSK_ERR_ARGUMENT, "n_samples must not be negative");
+    const int S = ch->S;
+    int64_t n_call = lengths ? 0 : n_samples;
+    if (lengths)
+        for (int s = 0; s < S; ++s) {
+            if (lengths[s] < 0 || lengths[s] > n_samples)
+                return fail(QPSK_ERR_ARGUMENT, "lengths[" + std::to_string(s) + "] = " + std::to_string(lengths[s]) +
+                                                   " outside [0, n_samples]");
+            n_call = std::max(n_call, lengths[s]);
+        }
+    if (n_call == 0) return QPSK_OK;
+    if (!in || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "in or out is null");
+    if (n_samples > (INT64_MAX >> 4) || stride_in < 2 * n_samples || stride_out < 2 * n_samples)
+        return fail(QPSK_ERR_ARGUMENT, "stride too small");
+    if (in == out && (fmt_in != fmt_out || stride_in != stride_out))
+        return fail(QPSK_ERR_ARGUMENT, "in place needs one format and one stride");
+    const bool host = mem == QPSK_MEM_HOST;
+    int rc;
+    if (!host && ((rc = check_device_rows("input", fmt_in, in, stride_in)) ||
+                  (rc = check_device_rows("output", fmt_out, out, stride_out))))
+        return rc;
+
+    DeviceGuard guard;
+    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
+    hipStream_t st = ch->stream;
+    ChanArgs a = base_args(ch);
+    a.in = in;
+    a.out = out;
+    a.in_stride = stride_in;
+    a.out_stride = stride_out;
+    a.scale_in = scale_in;
+    a.scale_out = scale_out;
+    a.fmt_in = fmt_in;
+    a.fmt_out = fmt_out;
+    a.n = n_samples;
+    const int64_t ieb = elem_bytes(fmt_in), oeb = elem_bytes(fmt_out);
+    if (lengths) {
+        // the kernel reads the lengths the host checked
+        QPSK_HIP_TRY(hipMemcpyAsync(ch->d_len, lengths, S * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        a.lengths = ch->d_len;
+    }
+    const int64_t ipitch = (2 * n_call * ieb + 15) / 16 * 16, opitch = (2 * n_call * oeb + 15) / 16 * 16;
+    if (host) {
+        if ((rc = staged(ch->d_in.grow(static_cast<size_t>(S) * ipitch)))) return rc;
+        if ((rc = staged(ch->d_out.grow(static_cast<size_t>(S) * opitch)))) return rc;
+        QPSK_HIP_TRY(hipMemcpy2DAsync(ch->d_in, ipitch, in, stride_in * ieb, 2 * n_call * ieb, S, hipMemcpyHostToDevice, st));
+        // what lies past a row's length comes back as it was
+        if (lengths)
+            QPSK_HIP_TRY(hipMemcpy2DAsync(ch->d_out, opitch, out, stride_out * oeb, 2 * n_call * oeb, S,
+                                          hipMemcpyHostToDevice, st));
+        a.in = ch->d_in;
+        a.out = ch->d_out;
+        a.in_stride = ipitch / ieb;
+        a.out_stride = opitch / oeb;
+    }
+    a.in_pair = pair_rows(fmt_in, a.in, a.in_stride);
+    a.out_pair = pair_rows(fmt_out, a.out, a.out_stride);
+    hipLaunchKernelGGL(channel_kernel, dim3((S + kStreams - 1) / kStreams), dim3(kThreads), 0, st, a);
+    QPSK_HIP_TRY(hipGetLastError());
+    if (host)
+        QPSK_HIP_TRY(hipMemcpy2DAsync(out, stride_out * oeb, ch->d_out, opitch, 2 * n_call * oeb, S, hipMemcpyDeviceToHost,
+                                      st));
+    if (host || lengths) QPSK_HIP_TRY(hipStreamSynchronize(st));
+    return QPSK_OK;
+}
+
+int qpsk_channel_get_state(qpsk_channel *ch, void *host_buf, int64_t buf_bytes) {
+    if (!ch || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    const int64_t want = static_cast<int64_t>(ch->S) * static_cast<int64_t>(sizeof(ChanState));
+    if (buf_bytes != want)
+        return fail(QPSK_ERR_ARGUMENT, "channel state length does not match this handle (" + std::to_string(buf_bytes) +
+                                           " vs " + std::to_string(want) + " bytes)");
+    DeviceGuard guard;
+    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
+    QPSK_HIP_TRY(hipMemcpyAsync(host_buf, ch->d_state, want, hipMemcpyDeviceToHost, ch->stream));
+    QPSK_HIP_TRY(hipStreamSynchronize(ch->stream));
+    return QPSK_OK;
+}
+
+int qpsk_channel_set_state(qpsk_channel *ch, const void *host_buf, int64_t buf_bytes) {
+    if (!ch) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    int rc;
+    if ((rc = qpsk_channel_state_check(&ch->p, ch->S, host_buf, buf_bytes))) return rc;
+    DeviceGuard guard;
+    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
+    QPSK_HIP_TRY(hipMemcpyAsync(ch->d_state, host_buf, buf_bytes, hipMemcpyHostToDevice, ch->stream));
+    QPSK_HIP_TRY(hipStreamSynchronize(ch->stream));
+    return QPSK_OK;
+}
+
+int qpsk_channel_reset_streams(qpsk_channel *ch, const int32_t *streams, int32_t n) {
+    if (!ch) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
+    int rc;
+    if ((rc = qpsk_stream_list_check(ch->S, streams, n))) return rc;
+    DeviceGuard guard;
+    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
+    std::vector<ChanState> st(n);   // lives until the synchronise below
+    for (int32_t k = 0; k < n; ++k) {
+        st[k] = qpsk::chan_state_new(ch->p, streams[k]);
+        QPSK_HIP_TRY(hipMemcpyAsync(ch->d_state.get() + streams[k], &st[k], sizeof(ChanState), hipMemcpyHostToDevice,
+                                    ch->stream));
+    }
+    QPSK_HIP_TRY(hipStreamSynchronize(ch->stream));
+    return QPSK_OK;
+}
+
+}  // extern "C"

@@ -168,6 +168,14 @@ class BerParams(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class ChannelParams(C.Structure):
+    """qpsk_channel_params: the LO pair and the noise of the test bench's channel."""
+    _fields_ = [("sample_rate", C.c_double), ("lo_hz", C.c_double), ("tx_ppm", C.c_double), ("rx_ppm", C.c_double),
+                ("tx_phase0", C.c_double), ("rx_phase0", C.c_double), ("tx_seed", C.c_uint64), ("rx_seed", C.c_uint64),
+                ("noise_rms", C.c_double), ("noise_seed", C.c_uint64), ("first_stream", C.c_int64),
+                ("device", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 class LoopShape(C.Structure):
     """qpsk_loop_shape (include/qpsk_demod.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -373,6 +381,19 @@ def lib():
     L.qpsk_ber_row_size.restype = C.c_int
     L.qpsk_ber_count.argtypes = ber
     L.qpsk_ber_count_device.argtypes = ber + [C.c_void_p]
+    # the test bench's channel: LO pair and noise on rows of any format
+    L.qpsk_channel_params_init.argtypes = [C.POINTER(ChannelParams), C.c_double]
+    L.qpsk_channel_params_init.restype = None
+    L.qpsk_channel_create.argtypes = [C.POINTER(ChannelParams), C.c_int32, C.POINTER(C.c_void_p)]
+    L.qpsk_channel_destroy.argtypes = [C.c_void_p]
+    L.qpsk_channel_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.qpsk_channel_apply_fmt.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_int64, C.c_float, C.c_int64, _i64p, C.c_int32]
+    L.qpsk_channel_state_size.restype = C.c_int
+    L.qpsk_channel_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_channel_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_channel_reset_streams.argtypes = [C.c_void_p, _i32p, C.c_int32]
+    L.qpsk_channel_state_check.argtypes = [C.POINTER(ChannelParams), C.c_int32, C.c_void_p, C.c_int64]
     _lib = real
     return real
 
@@ -415,6 +436,9 @@ EXPORTED_SYMBOLS = [
     "qpsk_rx_frames_bytes", "qpsk_rx_collect_frames", "qpsk_rx_reset_streams",
     "qpsk_quantise_iq", "qpsk_mod_modulate_fmt", "qpsk_mod_modulate_bytes_fmt",
     "qpsk_ber_params_init", "qpsk_ber_row_size", "qpsk_ber_count", "qpsk_ber_count_device",
+    "qpsk_channel_params_init", "qpsk_channel_create", "qpsk_channel_destroy", "qpsk_channel_set_stream",
+    "qpsk_channel_apply_fmt", "qpsk_channel_state_size", "qpsk_channel_get_state", "qpsk_channel_set_state",
+    "qpsk_channel_reset_streams", "qpsk_channel_state_check",
 ]
 
 _EXC = {
@@ -1690,6 +1714,163 @@ class QPSKModulator:
             self._h, tag, _norm(norm), sc, n_payload_dev.numel(), rows, rstride, cnt, st.ctypes.data, st.size,
             en.ctypes.data, en.size, 1 if pulse_shaping else 0, MEM_DEVICE, out, ostride, nout, peak),
             payload_dev, n_payload_dev, out_dev, n_out_dev, fmt, norm, peak_dev)
+
+
+# one oscillator of a channel stream's state, and the 128-byte record
+_CHANNEL_NCO = [("static_ppm", "f8"), ("drift_ppm", "f8"), ("total_ppm", "f8"), ("cur_hz", "f8"), ("phase", "f8"),
+                ("counter", "i8"), ("rng", "u8")]
+CHANNEL_STATE_DTYPE = np.dtype([("tx", _CHANNEL_NCO), ("rx", _CHANNEL_NCO), ("pos", "i8"), ("reserved", "i8")])
+CHANNEL_TILE_STREAMS = 16     # QPSK_CHANNEL_TILE_STREAMS
+CHANNEL_BLOCK_SAMPLES = 64    # QPSK_CHANNEL_BLOCK_SAMPLES
+# the default scale of a format's samples, in and out (full scale 1.0)
+_CHANNEL_SCALE_IN = {FMT_CF32: 1.0, FMT_CS16: 1.0 / 32768, FMT_CS8: 1.0 / 128, FMT_CU8: 1.0 / 128}
+_CHANNEL_SCALE_OUT = {FMT_CF32: 1.0, FMT_CS16: 32767.0, FMT_CS8: 127.0, FMT_CU8: 127.0}
+
+
+def channel_state_size() -> int:
+    """qpsk_channel_state_size(): 128 (needs no device)."""
+    return int(lib().qpsk_channel_state_size())
+
+
+def channel_params(sample_rate, lo_hz=None, tx_ppm=None, rx_ppm=None, tx_phase0=None, rx_phase0=None, tx_seed=None,
+                   rx_seed=None, noise_rms=None, noise_seed=None, first_stream=None, device=None) -> ChannelParams:
+    """qpsk_channel_params_init's defaults (100 MHz, 1 ppm and 1 ppm, no noise)
+    with the given fields replaced."""
+    p = ChannelParams()
+    lib().qpsk_channel_params_init(C.byref(p), float(sample_rate))
+    for name, v in (("lo_hz", lo_hz), ("tx_ppm", tx_ppm), ("rx_ppm", rx_ppm), ("tx_phase0", tx_phase0),
+                    ("rx_phase0", rx_phase0), ("noise_rms", noise_rms)):
+        if v is not None:
+            setattr(p, name, float(v))
+    for name, v in (("tx_seed", tx_seed), ("rx_seed", rx_seed), ("noise_seed", noise_seed)):
+        if v is not None:
+            setattr(p, name, int(v) & (2 ** 64 - 1))
+    for name, v in (("first_stream", first_stream), ("device", device)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def channel_state_check(p: ChannelParams, n_streams: int, blob):
+    """qpsk_channel_state_check: raises ValueError naming stream, oscillator and
+    field when blob is no state of a handle (p, n_streams).  Needs no device."""
+    b = bytes(blob)
+    _check(lib().qpsk_channel_state_check(C.byref(p), int(n_streams), b, len(b)))
+
+
+class Channel:
+    """The reference test bench's channel on S streams (qpsk_channel_*): every
+    sample times txNCO.NextSample() * conj(rxNCO.NextSample())
+    (testAtDataLevel.cs:39-42), optionally with GenerateIqNoise's samples
+    added first (testFullDemodChain.cs:73).  Rows of any format in, rows of
+    any format out, host or device memory; the state carries over calls."""
+
+    def __init__(self, n_streams: int, p: ChannelParams | None = None, **fields):
+        self.p = p if p is not None else channel_params(**fields)
+        self.n_streams = int(n_streams)
+        h = C.c_void_p()
+        _check(lib().qpsk_channel_create(C.byref(self.p), self.n_streams, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().qpsk_channel_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream_ptr: int | None):
+        """Order the handle's calls on a caller's stream (torch's); None goes
+        back to the handle's own."""
+        _check(lib().qpsk_channel_set_stream(self._h, C.c_void_p(hip_stream_ptr or 0)))
+        self._bound = bool(hip_stream_ptr)
+
+    @staticmethod
+    def _scales(tag_in, tag_out, scale_in, scale_out):
+        si = _CHANNEL_SCALE_IN[tag_in] if scale_in is None else scale_in
+        so = _CHANNEL_SCALE_OUT[tag_out] if scale_out is None else scale_out
+        return C.c_float(float(np.float32(si))), C.c_float(float(np.float32(so)))
+
+    @staticmethod
+    def _lengths(lengths, S):
+        if lengths is None:
+            return None, None
+        ln = np.ascontiguousarray(lengths, dtype=np.int64)
+        if ln.shape != (S,):
+            raise ValueError("lengths must hold one count a stream")
+        return ln, ln.ctypes.data_as(_i64p)
+
+    def apply(self, rows: np.ndarray, fmt="cf32", out_fmt=None, lengths=None, scale_in=None, scale_out=None,
+              norm="fixed", out: np.ndarray | None = None, n: int | None = None) -> np.ndarray:
+        """One host-memory call on rows [S, 2 n] of fmt; returns rows of out_fmt
+        (default fmt), written into out where given (out may be rows itself
+        for one format).  Default scales: full scale 1.0 both ways."""
+        tag_in, dt_in, _ = _format(fmt)
+        tag_out, dt_out, _ = _format(fmt if out_fmt is None else out_fmt)
+        if rows.dtype != dt_in or rows.ndim != 2 or rows.shape[0] != self.n_streams or rows.strides[1] != rows.itemsize:
+            raise ValueError(f"rows must be [n_streams, 2 n] of {np.dtype(dt_in).name} with contiguous rows")
+        n = rows.shape[1] // 2 if n is None else int(n)
+        if out is None:
+            out = np.zeros((self.n_streams, max(2 * n, 2)), dtype=dt_out)
+        if out.dtype != dt_out or out.ndim != 2 or out.shape[0] != self.n_streams or out.strides[1] != out.itemsize:
+            raise ValueError(f"out must be [n_streams, 2 n] of {np.dtype(dt_out).name} with contiguous rows")
+        keep, lp = self._lengths(lengths, self.n_streams)
+        si, so = self._scales(tag_in, tag_out, scale_in, scale_out)
+        _check(lib().qpsk_channel_apply_fmt(self._h, tag_in, rows.ctypes.data, rows.strides[0] // rows.itemsize, si,
+                                            tag_out, _norm(norm), out.ctypes.data, out.strides[0] // out.itemsize, so,
+                                            n, lp, MEM_HOST))
+        return out
+
+    def apply_device(self, in_dev, n: int, out_dev=None, fmt="cf32", out_fmt=None, lengths=None, scale_in=None,
+                     scale_out=None, norm="fixed"):
+        """One device-memory call: in_dev [S, >= 2 n] of fmt, out_dev likewise
+        of out_fmt (default: in place).  lengths is a host array.  Ordered on
+        the handle's stream; without set_stream the caller's torch stream is
+        drained first and the call is waited for."""
+        import torch
+        tag_in = _format(fmt)[0]
+        tag_out = _format(fmt if out_fmt is None else out_fmt)[0]
+        out_dev = in_dev if out_dev is None else out_dev
+        for t, f, what in ((in_dev, fmt, "in_dev"), (out_dev, fmt if out_fmt is None else out_fmt, "out_dev")):
+            if (not t.is_cuda or t.dtype != _torch_dtype(f) or t.dim() != 2 or t.shape[0] != self.n_streams or
+                    (t.shape[1] > 1 and t.stride(1) != 1) or t.shape[1] < 2 * n):
+                raise ValueError(f"{what} must be a contiguous-row [n_streams, >= 2 n] device tensor of its format")
+        keep, lp = self._lengths(lengths, self.n_streams)
+        si, so = self._scales(tag_in, tag_out, scale_in, scale_out)
+        bound = getattr(self, "_bound", False)
+        if not bound:   # the handle's own stream does not order against torch's
+            torch.cuda.current_stream(out_dev.device).synchronize()
+        _check(lib().qpsk_channel_apply_fmt(self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, tag_out,
+                                            _norm(norm), out_dev.data_ptr(), out_dev.stride(0), so, int(n), lp,
+                                            MEM_DEVICE))
+        if not bound:
+            self.sync()
+        return out_dev
+
+    def sync(self):
+        """Wait for the calls queued on the handle (reads its state)."""
+        self.get_state()
+
+    def get_state(self) -> bytes:
+        buf = C.create_string_buffer(channel_state_size() * self.n_streams)
+        _check(lib().qpsk_channel_get_state(self._h, buf, len(buf)))
+        return buf.raw
+
+    def states(self, blob: bytes | None = None) -> np.ndarray:
+        """The state as a CHANNEL_STATE_DTYPE array, one record a stream."""
+        return np.frombuffer(self.get_state() if blob is None else blob, dtype=CHANNEL_STATE_DTYPE).copy()
+
+    def set_state(self, blob):
+        b = bytes(blob)
+        _check(lib().qpsk_channel_set_state(self._h, b, len(b)))
+
+    def reset_streams(self, streams):
+        a, n = _stream_list(streams)
+        _check(lib().qpsk_channel_reset_streams(self._h, a, n))
 
 
 def _norm(norm):

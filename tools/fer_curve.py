@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Frame loss against noise and against LO instability from thousands of
+independent streams on one MI355X, with no sample leaving the device: the
+reference's end-to-end test (testAtDataLevel.cs:24-46, with
+testFullDemodChain.cs:73's noise) at batch size.
+
+Per point a fresh channel, demodulator state and framer; then --frames rounds
+in which every one of the C3 batch's 4096 streams (sps 4, 129 taps) sends one
+frame of its own random payload:
+
+    qpsk_mod_modulate_bytes_fmt   TSC | MESSAGE_START | payload | MESSAGE_STOP, device rows
+    qpsk_channel_apply_fmt        the LO pair (and the noise), in place
+    qpsk_demod_process_fmt        all loop state carried from frame to frame
+    qpsk_tsc_find_device, qpsk_framer_dev_push   DeModulateBytes' framer
+
+A frame counts as received when the framer returns exactly the payload sent in
+that round.  The comparison runs on the device; one count a round comes back.
+The first --skip rounds (acquisition) are reported apart.
+
+Two sweeps: frame loss against noise_rms at 1 ppm, and against ppm (both LOs)
+with no noise.  Writes one JSON file (--out, default profiles/fer_curve.json).
+The values are recorded as measured; nothing here asserts them.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (os.path.join(ROOT, "qpsk-modulator-demodulator_amd"), os.path.join(ROOT, "oracle")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+FS = 10_000_000
+ALPHA = 0.4000000059604645
+C3 = dict(streams=4096, sps=4, span=32)
+TSC = "11001010011101100100100110101100" + "01110100111001011010001101101001"
+START, STOP = b"MESSAGE_START", b"MESSAGE_STOP"
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fer_curve.json"))
+    ap.add_argument("--streams", type=int, default=C3["streams"])
+    ap.add_argument("--payload-bytes", type=int, default=48)
+    ap.add_argument("--frames", type=int, default=24)
+    ap.add_argument("--skip", type=int, default=4)
+    ap.add_argument("--noise-rms", default="0,0.05,0.1,0.15,0.2,0.25,0.3,0.4,0.5")
+    ap.add_argument("--ppm", default="0,1,2,5,10,20,50,100")
+    ap.add_argument("--fmt", default="cf32", choices=["cf32", "cs16", "cs8"])
+    args = ap.parse_args()
+
+    import torch
+    import qpsk_amd as Q
+    torch.cuda.init()
+    dev = torch.device("cuda", 0)
+    S, P, sps, span = args.streams, args.payload_bytes, C3["sps"], C3["span"]
+    rs = FS // sps
+    full = {"cf32": 1.0, "cs16": 32767.0, "cs8": 127.0}[args.fmt]
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    m = Q.QPSKModulator(FS, rs, ALPHA, span, tsc=TSC, device=dev.index)
+    n = m.output_floats(8 * (len(START) + P + len(STOP))) // 2
+    pitch = (n + 7) // 8 * 8
+    d = Q.BatchDemodulator(S, Q.params(FS, rs, ALPHA, span, device=dev.index, max_samples_per_call=pitch))
+    fr = Q.DeviceFramer(S, START, STOP, ring_capacity=1 << 16, device=dev.index)
+    for h in (m, d, fr):
+        h.set_stream(stream.cuda_stream)
+    fresh = d.get_state()
+    rows = torch.zeros((S, 2 * pitch), dtype=Q._torch_dtype(args.fmt), device=dev)
+    n_out = torch.zeros(S, dtype=torch.int64, device=dev)
+    plen = torch.full((S,), P, dtype=torch.int64, device=dev)
+    ms = d.max_symbols(pitch)
+    bits = torch.zeros((S, (2 * ms + 7) // 8 + 8), dtype=torch.uint8, device=dev)
+    nbits = torch.zeros(S, dtype=torch.int64, device=dev)
+    offs = torch.zeros(S, dtype=torch.int64, device=dev)
+    pay = torch.zeros((S, 256), dtype=torch.uint8, device=dev)
+    npay = torch.zeros(S, dtype=torch.int64, device=dev)
+    gen = torch.Generator(device=dev)
+    rec = {"device": torch.cuda.get_device_name(dev), "streams": S, "sps": sps, "taps": sps * span + 1, "fmt": args.fmt,
+           "payload_bytes": P, "samples_per_frame": n, "frames": args.frames, "skip": args.skip, "lo_hz": 100e6,
+           "noise_sweep": [], "ppm_sweep": []}
+
+    def point(ppm, rms):
+        d.set_state(fresh)
+        fr.reset_streams(range(S))
+        ch = Q.Channel(S, sample_rate=float(FS), tx_ppm=ppm, rx_ppm=ppm, noise_rms=rms, noise_seed=11, device=dev.index)
+        ch.set_stream(stream.cuda_stream)
+        gen.manual_seed(1234)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        good = []
+        for _ in range(args.frames):
+            sent = torch.randint(0, 256, (S, P), dtype=torch.uint8, device=dev, generator=gen)
+            m.modulate_bytes_device(sent, plen, START, STOP, rows, n_out, fmt=args.fmt, scale=full)
+            ch.apply_device(rows, n, fmt=args.fmt)
+            d.process_device_fmt(rows, n, bits, nbits, args.fmt)
+            Q.tsc_find_device(bits, nbits, TSC, offs, stream.cuda_stream)
+            fr.push(bits, nbits, pay, npay, offs)
+            good.append(((npay == P) & (pay[:, :P] == sent).all(dim=1)).sum())
+        e1.record(stream)
+        e1.synchronize()
+        good = [int(g) for g in good]
+        ch.close()
+        after = good[args.skip:]
+        return dict(ppm=ppm, noise_rms=rms, frames_received_per_round=good, frames_sent_after_skip=S * len(after),
+                    frames_lost_after_skip=S * len(after) - sum(after),
+                    frame_loss_after_skip=round(1.0 - sum(after) / (S * len(after)), 6),
+                    ms=round(e0.elapsed_time(e1), 1))
+
+    def save():
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+
+    for rms in (float(v) for v in args.noise_rms.split(",")):
+        rec["noise_sweep"].append(point(1.0, rms))
+        print(json.dumps(rec["noise_sweep"][-1]), flush=True)
+        save()
+    for ppm in (float(v) for v in args.ppm.split(",")):
+        rec["ppm_sweep"].append(point(ppm, 0.0))
+        print(json.dumps(rec["ppm_sweep"][-1]), flush=True)
+        save()
+    m.close()
+    d.close()
+
+
+if __name__ == "__main__":
+    main()
