@@ -128,6 +128,8 @@ def lib():
         L.or_demod_read_state.argtypes = [C.c_void_p, C.POINTER(DemodState), _f32p, C.c_long, _f32p, C.c_long,
                                           _f32p, C.c_long]
         L.or_demod_read_state.restype = C.c_int
+        L.or_demod_write_state.argtypes = [C.c_void_p, C.POINTER(DemodState)]
+        L.or_demod_write_state.restype = None
         L.or_demod_set_lanes.argtypes = [C.c_void_p, C.c_int]
         L.or_bits_to_bytes.argtypes = [C.c_char_p, C.c_long, C.c_int, _u8p, C.c_long]
         L.or_bits_to_bytes.restype = C.c_long
@@ -415,6 +417,33 @@ class OracleDemod:
             "fll_pos": int(st.fll_pos), "fll_delay": fd.reshape(-1, 2),
             "rrc_pos": int(st.rrc_pos), "rrc_taps": int(st.rrc_taps), "rrc_delay": rd.reshape(-1, 2),
         }
+
+    # write_state's fields: the loop state under read_state's names
+    LOOP_FIELDS = ("mm_base_index", "mm_has_prev", "mm_mu", "mm_nco_integral", "mm_prev_sample",
+                   "mm_prev_decision", "costas_theta", "costas_freq", "diff_have_prev", "diff_prev")
+
+    def write_state(self, **fields):
+        """Tests only (or_demod_write_state): set loop fields of the live
+        instance, named as read_state names them; the fields not given keep
+        their values.  Floats cross as bit patterns (numpy scalars of the
+        field's own type keep a NaN payload; a Python float is a double)."""
+        unknown = set(fields) - set(self.LOOP_FIELDS)
+        if unknown:
+            raise KeyError(f"not a loop field: {sorted(unknown)}")
+        st = DemodState()
+        lib().or_demod_read_state(self._h, C.byref(st), None, 0, None, 0, None, 0)
+        raw = np.frombuffer(st, dtype=np.uint8)   # a view of the struct's memory
+        for name, v in fields.items():
+            fld = getattr(DemodState, name)
+            if name in ("mm_base_index", "mm_has_prev", "diff_have_prev"):
+                setattr(st, name, int(v))
+                continue
+            pair = name in ("mm_prev_sample", "mm_prev_decision", "diff_prev")
+            a = np.asarray(v, dtype=np.float32 if pair else np.float64).reshape(-1)
+            if a.size != (2 if pair else 1):
+                raise ValueError(f"{name}: {a.size} values")
+            raw[fld.offset: fld.offset + fld.size] = a.view(np.uint8)
+        lib().or_demod_write_state(self._h, C.byref(st))
 
     def __del__(self):
         if getattr(self, "_h", None):

@@ -770,6 +770,22 @@ int or_demod_read_state(const or_demod *d, or_demod_state *st, float *mm_queue_i
     return 0;
 }
 
+/* Test infrastructure: see qpsk_oracle.h */
+void or_demod_write_state(or_demod *d, const or_demod_state *st)
+{
+    or_mm *m = d->mm;
+    m->base = st->mm_base_index;
+    m->has_prev = st->mm_has_prev;
+    m->mu = st->mm_mu;
+    m->integ = st->mm_nco_integral;
+    m->psi = st->mm_prev_sample[0]; m->psq = st->mm_prev_sample[1];
+    m->pdi = st->mm_prev_decision[0]; m->pdq = st->mm_prev_decision[1];
+    d->costas->theta = st->costas_theta;
+    d->costas->freq = st->costas_freq;
+    d->diff_have_prev = st->diff_have_prev;
+    d->prev_i = st->diff_prev[0]; d->prev_q = st->diff_prev[1];
+}
+
 /* Test infrastructure: the reference's Vector<float>.Count is fixed per machine;
  * this moves a running instance to another width, as a state blob restored
  * into a handle of another vector_lanes does (the delay lines stay). */

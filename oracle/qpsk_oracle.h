@@ -131,6 +131,13 @@ typedef struct or_demod_state {
 } or_demod_state;
 int or_demod_read_state(const or_demod *d, or_demod_state *st, float *mm_queue_iq, long mm_queue_cap,
                         float *fll_delay_iq, long fll_delay_cap, float *rrc_delay_iq, long rrc_delay_cap);
+/* Tests only, no reference counterpart: the loop fields of a live instance set
+ * from st, as a restored state blob sets the kernel's records.  Written: the
+ * M&M's baseIndex, mu, ncoIntegral, hasPrev, prevSample and prevDecision, the
+ * Costas loop's theta and freq, _diffHavePrev and the previous decision.
+ * Every other field of st (queue, filters, FLL, IQ balancer) is ignored.  The
+ * values cross in memory, so NaN payloads and -0 arrive as they are. */
+void or_demod_write_state(or_demod *d, const or_demod_state *st);
 /* tests only, no reference counterpart: Vector<float>.Count of every filter
  * from the next call on (a blob restored into a handle of another vector_lanes) */
 void or_demod_set_lanes(or_demod *d, int lanes);

@@ -240,6 +240,24 @@ def ragged_calls(T, S=6):
     return calls
 
 
+def ragged_loop_calls(S, n, seed, big=4096):
+    """Per-stream call sizes for the symbol loop: 0, 1, 2 and 3 samples, calls
+    longer than a round, and a different size per stream in every call, so
+    streams end in different rounds (the loader's slow path) with odd and even
+    carries; n samples a stream in all.  big: the longest of the first nine
+    sizes (rows much shorter than it would end in that call)."""
+    rng = np.random.default_rng(seed)
+    sizes = [1, 2, 3, 0, 777, 5, big, 130, 63]
+    calls, left, k = [], np.full(S, n), 0
+    while left.max() > 0:
+        c = [int(min(left[s], sizes[(k + s) % len(sizes)] if k < 9 else rng.integers(100, 3000)))
+             for s in range(S)]
+        calls.append(c)
+        left -= np.array(c)
+        k += 1
+    return calls
+
+
 def calls_for(T, S=6):
     """ragged_calls(T), then five calls in which every stream takes 2050 ... 2054
     samples once (row ends at 2 ... 6 mod 8)."""
@@ -252,12 +270,17 @@ def calls_for(T, S=6):
 # ---------------------------------------------------------------------------
 # the oracle over a call sequence
 # ---------------------------------------------------------------------------
-def oracle_run(iq, calls, rs, span, mode=None, after_call=None, **okw):
+def oracle_run(iq, calls, rs, span, mode=None, after_call=None, state0=None, **okw):
     """Per-stream OracleDemod instances (symbol rate rs in Hz, keywords okw) fed
     the same call sequence.  calls: per-call [S] lengths in complex samples;
-    mode per call; after_call(ci, instances) runs behind every call."""
+    mode per call; after_call(ci, instances) runs behind every call.  state0:
+    per stream a dict of loop fields (OracleDemod.write_state) set before the
+    first call."""
     S = iq.shape[0]
     dms = [O.OracleDemod(K.FS, rs, K.ALPHA, span, **okw) for _ in range(S)]
+    for dm, st in zip(dms, state0 or ()):
+        if st:
+            dm.write_state(**st)
     pos = np.zeros(S, dtype=np.int64)
     out = []
     for ci, lens in enumerate(calls):
@@ -377,17 +400,22 @@ def out_rows(S, ms, layout):
     return bits, sy
 
 
-def async_run(iq, calls, sps, span, sync_every=0, layout=None, **knobs):
+def async_run(iq, calls, sps, span, sync_every=0, layout=None, prepare=None, finish=None, want_syms=True, **knobs):
     """The float call sequence through process_device_async on a torch stream of
     its own (front stage of call k+1 overlapping the back stage of call k),
     every call's outputs in their own device rows, one pipeline_wait at the
     end.  sync_every > 0 makes every sync_every-th call a synchronous
     process_device (mixed ordering).  layout: None (rows as a caller would size
-    them), or out_rows' layouts.  Returns the decoded rows and pipeline_depth."""
+    them), or out_rows' layouts.  prepare(b) runs on the new handle before the
+    first call (a state to restore), finish(b) after the wait, before the
+    handle is closed.  want_syms=False passes no symbol rows (the bits-only
+    kernel); the rows then carry None for symbols.  Returns the decoded rows and pipeline_depth."""
     import torch
     S = iq.shape[0]
     nmax = max(max(c) for c in calls)
     b = make(S, sps, span, nmax + 8, **knobs)
+    if prepare:
+        prepare(b)
     stream = torch.cuda.Stream()
     b.set_stream(stream.cuda_stream)
     ms = max(b.max_symbols(nmax), 1)
@@ -406,18 +434,22 @@ def async_run(iq, calls, sps, span, sync_every=0, layout=None, **knobs):
                 sy = torch.zeros((S, 2 * ms), dtype=torch.float32, device="cuda")
             nb = torch.zeros(S, dtype=torch.int64, device="cuda")
             ns = torch.zeros(S, dtype=torch.int64, device="cuda")
+            out = dict(syms_dev=sy, n_syms_dev=ns) if want_syms else {}
             if sync_every and ci % sync_every == sync_every - 1:
                 assert lengths_of(lens) is None
-                b.process_device(xd, n, bits, nb, syms_dev=sy, n_syms_dev=ns)
+                b.process_device(xd, n, bits, nb, **out)
             else:
-                b.process_device_async(xd, n, bits, nb, syms_dev=sy, n_syms_dev=ns, lengths=lengths_of(lens))
+                b.process_device_async(xd, n, bits, nb, lengths=lengths_of(lens), **out)
             outs.append((xd, bits, nb, sy, ns))
             pos += np.array(lens)
     depth = b.pipeline_depth()
     b.pipeline_wait()
     torch.cuda.synchronize()
-    res = [decoded(DEMODULATE, bits.cpu().numpy(), nb.cpu().numpy(), sy.cpu().numpy(), ns.cpu().numpy())
+    res = [decoded(DEMODULATE, bits.cpu().numpy(), nb.cpu().numpy(), sy.cpu().numpy() if want_syms else None,
+                   ns.cpu().numpy())
            for _, bits, nb, sy, ns in outs]
+    if finish:
+        finish(b)
     b.close()
     return res, depth
 
@@ -462,10 +494,56 @@ def assert_rows(mfs, calls, refs):
 # ---------------------------------------------------------------------------
 # comparisons
 # ---------------------------------------------------------------------------
-def assert_same(got, want, exact=True, what=""):
+def same_bits(a, b, dtype, nan_any_payload=False):
+    return K.bitwise_equal(np.asarray(a, dtype=dtype).reshape(-1), np.asarray(b, dtype=dtype).reshape(-1),
+                           nan_any_payload=nan_any_payload)
+
+
+def assert_state(blob, ostates, sps, span, what, rows=None, nan_rows=(), taps=None):
+    """A state blob (qpsk_demod_get_state) against ostates[s] = the oracle's
+    read_state() of stream s, field by field as bit patterns: the record, the
+    carry, the filter history and the FLL delay line.  rows: the streams to
+    compare (default: all); nan_rows: streams whose floats compare under the
+    NaN rule (NaN where the reference has NaN, payloads aside); taps: the
+    filter's length where it is not sps * span + 1 (a non-integer sps)."""
+    S, T = len(ostates), taps or sps * span + 1
+    rec, carry, hist, dl = qpsk_amd.state_blob_parts(blob, S, T)
+    f4, f8 = np.float32, np.float64
+    for s in (range(S) if rows is None else rows):
+        o, r, nan_ok = ostates[s], rec[s], s in nan_rows
+        ints = [("base", o["mm_base_index"]), ("has_prev", o["mm_has_prev"]), ("carry_n", o["mm_buf_count"]),
+                ("diff_have", o["diff_have_prev"]), ("fll_pos", o["fll_pos"]), ("error", 0), ("tofs", 0)]
+        for name, want in ints:
+            assert int(r[name]) == int(want), f"{what} stream {s}: {name} {int(r[name])} vs {int(want)}"
+        floats = [("mu", o["mm_mu"], f8), ("integ", o["mm_nco_integral"], f8),
+                  ("theta", o["costas_theta"], f8), ("freq", o["costas_freq"], f8),
+                  ("psi", o["mm_prev_sample"][0], f4), ("psq", o["mm_prev_sample"][1], f4),
+                  ("pdi", o["mm_prev_decision"][0], f4), ("pdq", o["mm_prev_decision"][1], f4),
+                  ("diff_pi", o["diff_prev"][0], f4), ("diff_pq", o["diff_prev"][1], f4),
+                  ("fll_phase", o["fll_phase"], f4), ("fll_freq", o["fll_freq"], f4),
+                  ("iqb_re", o["iqb_avg_real"], f4), ("iqb_im", o["iqb_avg_img"], f4)]
+        for name, want, dt in floats:
+            assert same_bits(r[name], want, dt, nan_ok), f"{what} stream {s}: {name} {r[name]!r} vs {want!r}"
+        k = int(r["carry_n"])
+        assert same_bits(carry[s, :k], o["mm_queue"], f4), f"{what} stream {s}: carry ({k} samples)"
+        # the history, oldest first = the reference's delay line read from T - 1
+        # writes back up to the newest one, at _pos - 1
+        idx = (o["rrc_pos"] - (T - 1) + np.arange(T - 1)) % T
+        if not same_bits(hist[s], o["rrc_delay"][idx], f4):
+            bad = np.flatnonzero((hist[s].view(np.uint32) != o["rrc_delay"][idx].view(np.uint32)).any(axis=1))
+            pytest.fail(f"{what} stream {s}: {bad.size} history samples differ, first at {bad[0]} of {T - 1}")
+        assert same_bits(dl[s], o["fll_delay"], f4), f"{what} stream {s}: FLL delay line (pos {o['fll_pos']})"
+        # and as the FLL reads it: the 39 samples before the write position
+        pos = int(r["fll_pos"])
+        back = (pos - 1 - np.arange(qpsk_amd.STATE_FLL_TAPS - 1)) % qpsk_amd.STATE_FLL_TAPS
+        assert same_bits(dl[s][back], o["fll_delay"][(o["fll_pos"] - 1 - np.arange(39)) % 40], f4)
+
+
+def assert_same(got, want, exact=True, what="", nan_rows=()):
     """Two results call by call and stream by stream: equal bits, the same
     symbol count, symbols bit for bit (exact) or within SYM_TOL; rows without
-    symbols (None) compare their bits alone."""
+    symbols (None) compare their bits alone.  nan_rows: streams whose symbols
+    compare under the NaN rule (NaN where want has NaN, payloads aside)."""
     assert len(got) == len(want)
     for ci, (ra, rb) in enumerate(zip(got, want)):
         for s, ((ba, sa), (bb, sb)) in enumerate(zip(ra, rb)):
@@ -474,6 +552,7 @@ def assert_same(got, want, exact=True, what=""):
                 continue
             assert sa.shape == sb.shape, f"{what} call {ci} stream {s}: symbol count"
             if exact:
-                assert K.bitwise_equal(sa, sb), f"{what} call {ci} stream {s}: symbols differ (bitwise)"
+                assert K.bitwise_equal(sa, sb, nan_any_payload=s in nan_rows), \
+                    f"{what} call {ci} stream {s}: symbols differ (bitwise)"
             else:
                 assert np.max(np.abs(sa - sb), initial=0) <= SYM_TOL

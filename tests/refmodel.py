@@ -98,6 +98,11 @@ class MM:
         self.pd = (F(0), F(0))
         self.has_prev = False
         self.buf = np.zeros((0, 2), F)
+        # tests only: a list here receives, per interpolated symbol, (its first
+        # sample's index in the whole stream, the correction before the clamp or
+        # None for the first symbol, whether the symbol was put out)
+        self.trace = None
+        self.origin = 0              # samples dropped from the queue so far
 
     def process(self, x_iq, out_floats=None):
         x = np.asarray(x_iq, dtype=F).reshape(-1, 2)
@@ -122,14 +127,18 @@ class MM:
                 t2 = float(di) * float(self.ps[0]) + float(dq) * float(self.ps[1])
                 e = t1 - t2
                 self.integ += self.ki * e
-                corr = self.kp * e + self.integ
+                corr = raw = self.kp * e + self.integ
                 corr = min(corr, 0.1) if corr > 0.1 else corr
                 corr = -0.1 if corr < -0.1 else corr
                 adv = self.sps + corr
             else:
                 self.has_prev = True
                 adv = self.sps
-            if 2 * len(out) + 1 >= cap:
+                raw = None
+            full = 2 * len(out) + 1 >= cap
+            if self.trace is not None:
+                self.trace.append((self.origin + self.base, raw, not full))
+            if full:
                 break
             out.append((ci, cq))
             self.ps, self.pd = (ci, cq), (di, dq)
@@ -142,6 +151,7 @@ class MM:
         if consumed > 0:
             self.buf = self.buf[consumed:]
             self.base -= consumed
+            self.origin += consumed
         return np.array(out, dtype=F).reshape(-1)
 
 
@@ -217,6 +227,8 @@ class Costas:
     def process(self, i, q):
         if self.portable:
             s, c = portable_sincos(self.theta)
+        elif math.isinf(self.theta):     # libm returns NaN; Python's math raises
+            c = s = math.nan
         else:
             c, s = math.cos(self.theta), math.sin(self.theta)
         mi = float(i) * c + float(q) * s

@@ -18,7 +18,7 @@ import pytest
 import common as K
 import oracle as O
 import qpsk_amd as Q
-from gpu_harness import assert_same, dev, gpu_run, oracle_run
+from gpu_harness import assert_same, dev, gpu_run, oracle_run, ragged_loop_calls
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("dev")]
 
@@ -34,19 +34,8 @@ def signals(sps, span, differential=True, seed0=3000):
 
 
 def ragged_calls(n, seed):
-    """Per-stream call sizes: 0, 1, 2 and 3 samples, calls longer than a round,
-    and a different size per stream in every call, so streams end in different
-    rounds (the loader's slow path) with odd and even carries."""
-    rng = np.random.default_rng(seed)
-    sizes = [1, 2, 3, 0, 777, 5, 4096, 130, 63]
-    calls, left, k = [], np.full(S, n), 0
-    while left.max() > 0:
-        c = [int(min(left[s], sizes[(k + s) % len(sizes)] if k < 9 else rng.integers(100, 3000)))
-             for s in range(S)]
-        calls.append(c)
-        left -= np.array(c)
-        k += 1
-    return calls
+    """gpu_harness.ragged_loop_calls for this module's S streams."""
+    return ragged_loop_calls(S, n, seed)
 
 
 @functools.lru_cache(maxsize=None)
@@ -85,10 +74,15 @@ def test_internal_chunks_bit_exact(sps, span, variant):
 @pytest.mark.parametrize("variant", VARIANTS)
 @pytest.mark.parametrize("sps,span,off", [(5, 8, 1.02), (5, 8, 0.98), (8, 8, 0.98)])
 def test_backlog_at_its_bound_bit_exact(sps, span, off, variant):
-    """The demodulator's symbol rate 2 % above / below the signal's: the M&M
-    correction sits at its +-0.1 clamp for the whole stream, so the streams
-    drift through the rounds at different rates, read the prefix at its far
-    end and run the per-lane catch-up loop."""
+    """The demodulator's symbol rate 2 % above / below the signal's (4.90, 5.10
+    and 8.16 samples a symbol, none an integer): the loop cannot lock, so the
+    symbols are noise to the TED and the streams run through the rounds out of
+    step with the round size, read the prefix at its far end and run the
+    per-lane catch-up loop.  The correction does not reach its +-0.1 clamp
+    here: the loop filter is too narrow to get there within a row (no symbol
+    at the clamp, the largest correction 0.006, measured with tests/refmodel.py
+    and asserted by test_loop_cases.py::test_backlog_rows_stay_far_from_the_
+    clamp).  The clamp as a steady state is tests/test_gpu_loop_edges.py's."""
     rs = int(round(K.FS / sps * off))
     iq, calls, ref = single_call_ref(sps, span, rs)
     assert_same(gpu_run(iq, calls, rs, span, loop_variant=variant), ref)

@@ -37,7 +37,7 @@ import common as K
 import oracle as O
 import qpsk_amd as Q
 import gpu_harness as H
-from gpu_harness import as_fmt, call_rows, decoded, dev, oracle_run, quantised, widened
+from gpu_harness import as_fmt, assert_state, call_rows, decoded, dev, oracle_run, quantised, widened
 from state_blobs import bad_blob
 
 gpu = pytest.mark.gpu
@@ -201,47 +201,6 @@ def run_a(cfg, sps, span, upto=None, knobs=()):
         blobs.append(b.get_state())
     b.close()
     return outs, blobs
-
-
-# ---------------------------------------------------------------------------
-# the blob against the reference's fields
-# ---------------------------------------------------------------------------
-def same_bits(a, b, dtype):
-    return K.bitwise_equal(np.asarray(a, dtype=dtype).reshape(-1), np.asarray(b, dtype=dtype).reshape(-1))
-
-
-def assert_state(blob, ostates, sps, span, what):
-    T = taps_of(sps, span)
-    rec, carry, hist, dl = Q.state_blob_parts(blob, S, T)
-    f4, f8 = np.float32, np.float64
-    for s in range(S):
-        o, r = ostates[s], rec[s]
-        ints = [("base", o["mm_base_index"]), ("has_prev", o["mm_has_prev"]), ("carry_n", o["mm_buf_count"]),
-                ("diff_have", o["diff_have_prev"]), ("fll_pos", o["fll_pos"]), ("error", 0), ("tofs", 0)]
-        for name, want in ints:
-            assert int(r[name]) == int(want), f"{what} stream {s}: {name} {int(r[name])} vs {int(want)}"
-        floats = [("mu", o["mm_mu"], f8), ("integ", o["mm_nco_integral"], f8),
-                  ("theta", o["costas_theta"], f8), ("freq", o["costas_freq"], f8),
-                  ("psi", o["mm_prev_sample"][0], f4), ("psq", o["mm_prev_sample"][1], f4),
-                  ("pdi", o["mm_prev_decision"][0], f4), ("pdq", o["mm_prev_decision"][1], f4),
-                  ("diff_pi", o["diff_prev"][0], f4), ("diff_pq", o["diff_prev"][1], f4),
-                  ("fll_phase", o["fll_phase"], f4), ("fll_freq", o["fll_freq"], f4),
-                  ("iqb_re", o["iqb_avg_real"], f4), ("iqb_im", o["iqb_avg_img"], f4)]
-        for name, want, dt in floats:
-            assert same_bits(r[name], want, dt), f"{what} stream {s}: {name} {r[name]!r} vs {want!r}"
-        k = int(r["carry_n"])
-        assert same_bits(carry[s, :k], o["mm_queue"], f4), f"{what} stream {s}: carry ({k} samples)"
-        # the history, oldest first = the reference's delay line read from T - 1
-        # writes back up to the newest one, at _pos - 1
-        idx = (o["rrc_pos"] - (T - 1) + np.arange(T - 1)) % T
-        if not same_bits(hist[s], o["rrc_delay"][idx], f4):
-            bad = np.flatnonzero((hist[s].view(np.uint32) != o["rrc_delay"][idx].view(np.uint32)).any(axis=1))
-            pytest.fail(f"{what} stream {s}: {bad.size} history samples differ, first at {bad[0]} of {T - 1}")
-        assert same_bits(dl[s], o["fll_delay"], f4), f"{what} stream {s}: FLL delay line (pos {o['fll_pos']})"
-        # and as the FLL reads it: the 39 samples before the write position
-        pos = int(r["fll_pos"])
-        back = (pos - 1 - np.arange(Q.STATE_FLL_TAPS - 1)) % Q.STATE_FLL_TAPS
-        assert same_bits(dl[s][back], o["fll_delay"][(o["fll_pos"] - 1 - np.arange(39)) % 40], f4)
 
 
 # ---------------------------------------------------------------------------

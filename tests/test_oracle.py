@@ -248,3 +248,36 @@ def test_iq_balancer_restatement():
     y1, y2 = b.process(x[:20]), b.process(x[20:])
     full, _, _ = model(x, x.size, np.float32(0), np.float32(0))
     assert np.array_equal(np.concatenate([y1, y2]), full)
+
+
+def test_write_state_read_state_round_trip():
+    """or_demod_write_state sets the loop fields of a live instance as bit
+    patterns (NaN payloads, -0 and Inf included) and leaves the others."""
+    u32 = lambda v: np.array([v], np.uint32).view(np.float32)[0]
+    u64 = lambda v: np.array([v], np.uint64).view(np.float64)[0]
+    fields = {
+        "mm_base_index": 3, "mm_has_prev": 1, "mm_mu": math.nextafter(1.0, 0.0), "mm_nco_integral": -math.inf,
+        "mm_prev_sample": (u32(0x7FC01234), np.float32(-0.0)), "mm_prev_decision": (np.float32(-1), np.float32(1)),
+        "costas_theta": u64(0x7FF8000000ABCDEF), "costas_freq": -0.0,
+        "diff_have_prev": 1, "diff_prev": (np.float32(1), np.float32(-1)),
+    }
+    dm = K.oracle_for(4, 8)
+    x = K.stream_signal(5, sps=4, span=8, n_bits=400)
+    dm.demodulate_ex(x[:600])
+    before = dm.read_state()
+    dm.write_state(**fields)
+    after = dm.read_state()
+    assert set(fields) == set(O.OracleDemod.LOOP_FIELDS)
+    for name, v in fields.items():
+        dt = type(before[name]) if np.isscalar(before[name]) else before[name].dtype
+        assert K.bitwise_equal(np.asarray(after[name], dtype=dt).reshape(-1), np.asarray(v, dtype=dt).reshape(-1)), name
+    for name in set(before) - set(fields):
+        assert K.bitwise_equal(np.asarray(after[name]), np.asarray(before[name])), name
+    # a subset leaves the rest of the loop fields alone
+    dm.write_state(costas_freq=1.5)
+    again = dm.read_state()
+    assert again["costas_freq"] == 1.5
+    for name in set(after) - {"costas_freq"}:
+        assert K.bitwise_equal(np.asarray(again[name]), np.asarray(after[name])), name
+    with pytest.raises(KeyError):
+        dm.write_state(fll_phase=0.0)
