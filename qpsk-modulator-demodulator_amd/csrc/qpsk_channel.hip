@@ -168,8 +168,7 @@ __global__ __launch_bounds__(kThreads) void channel_kernel(ChanArgs a) {
     }
     __syncthreads();   // the table
 
-    const int64_t in_eb = a.fmt_in == QPSK_FMT_CF32 ? 4 : (a.fmt_in == QPSK_FMT_CS16 ? 2 : 1);
-    const int64_t out_eb = a.fmt_out == QPSK_FMT_CF32 ? 4 : (a.fmt_out == QPSK_FMT_CS16 ? 2 : 1);
+    const int64_t in_eb = qpsk::fmt_elem_bytes(a.fmt_in), out_eb = qpsk::fmt_elem_bytes(a.fmt_out);
     for (int64_t b = 0; b <= blocks; ++b) {
         if (wave == 0) {
             if (scan && b < blocks) {
@@ -233,9 +232,8 @@ struct DeviceGuard {
     }
 };
 
-int staged(hipError_t e) { return e == hipSuccess ? QPSK_OK : fail(QPSK_ERR_DEVICE, "hipMalloc (channel staging)"); }
-
-int64_t elem_bytes(int fmt) { return qpsk_fmt_sample_bytes(fmt) / 2; }
+// what a failed grow of a staging buffer names (alloc_status)
+constexpr const char *kStaging = "channel staging";
 
 // what device rows of fmt must satisfy (qpsk_demod_process_fmt's rules)
 int check_device_rows(const char *what, int fmt, const void *rows, int64_t stride) {
@@ -310,7 +308,7 @@ int qpsk_channel_apply_fmt(qpsk_channel *ch, int32_t fmt_in, const void *in, int
                            int32_t fmt_out, int32_t norm_out, void *out, int64_t stride_out, float scale_out,
                            int64_t n_samples, const int64_t *lengths, int32_t mem) {
     if (!ch) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    if (!qpsk::quant_fmt_known(fmt_in) || !qpsk::quant_fmt_known(fmt_out))
+    if (!qpsk::fmt_known(fmt_in) || !qpsk::fmt_known(fmt_out))
         return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
     if (norm_out != QPSK_MOD_NORM_FIXED)
         return fail(QPSK_ERR_ARGUMENT, norm_out == QPSK_MOD_NORM_PEAK
@@ -356,7 +354,7 @@ int qpsk_channel_apply_fmt(qpsk_channel *ch, int32_t fmt_in, const void *in, int
     a.fmt_in = fmt_in;
     a.fmt_out = fmt_out;
     a.n = n_samples;
-    const int64_t ieb = elem_bytes(fmt_in), oeb = elem_bytes(fmt_out);
+    const int64_t ieb = qpsk::fmt_elem_bytes(fmt_in), oeb = qpsk::fmt_elem_bytes(fmt_out);
     if (lengths) {
         // the kernel reads the lengths the host checked
         QPSK_HIP_TRY(hipMemcpyAsync(ch->d_len, lengths, S * sizeof(int64_t), hipMemcpyHostToDevice, st));
@@ -364,8 +362,8 @@ int qpsk_channel_apply_fmt(qpsk_channel *ch, int32_t fmt_in, const void *in, int
     }
     const int64_t ipitch = (2 * n_call * ieb + 15) / 16 * 16, opitch = (2 * n_call * oeb + 15) / 16 * 16;
     if (host) {
-        if ((rc = staged(ch->d_in.grow(static_cast<size_t>(S) * ipitch)))) return rc;
-        if ((rc = staged(ch->d_out.grow(static_cast<size_t>(S) * opitch)))) return rc;
+        if ((rc = qpsk::alloc_status(ch->d_in.grow(static_cast<size_t>(S) * ipitch), kStaging))) return rc;
+        if ((rc = qpsk::alloc_status(ch->d_out.grow(static_cast<size_t>(S) * opitch), kStaging))) return rc;
         QPSK_HIP_TRY(hipMemcpy2DAsync(ch->d_in, ipitch, in, stride_in * ieb, 2 * n_call * ieb, S, hipMemcpyHostToDevice, st));
         // what lies past a row's length comes back as it was
         if (lengths)

@@ -3,8 +3,11 @@
 #include "qpsk_design.h"
 
 #include <cmath>
+#include <cstring>
 
 #include "qpsk_demod.h"
+#include "qpsk_internal.h"
+#include "qpsk_state.h"
 
 namespace qpsk {
 
@@ -138,3 +141,31 @@ int design_loops(int sample_rate, int symbol_rate, float rrc_alpha, int rrc_span
 }
 
 }  // namespace qpsk
+
+// the design of a handle with these parameters, without making one (no device)
+extern "C" {
+
+int qpsk_demod_design(const qpsk_demod_params *p, float *rrc_taps, int32_t cap, double *gains,
+                      float *fll_lower_iq, float *fll_upper_iq) {
+    if (!p) return qpsk::fail(QPSK_ERR_ARGUMENT_NULL, "null params");
+    qpsk::LoopDesign d;
+    std::string err;
+    int rc = qpsk::design_loops(p->sample_rate, p->symbol_rate, p->rrc_alpha, p->rrc_span,
+                          p->symbol_sync_bandwidth, p->costas_loop_bandwidth, p->cfo_loop_bandwidth,
+                          &d, &err);
+    if (rc != QPSK_OK) return qpsk::fail(rc, err);
+    const int T = static_cast<int>(d.rrc_f32.size());
+    if (rrc_taps) {
+        if (cap < T) return qpsk::fail(QPSK_ERR_ARGUMENT, "cap too small");
+        std::memcpy(rrc_taps, d.rrc_f32.data(), T * sizeof(float));
+    }
+    if (gains) {
+        gains[0] = d.mm_sps; gains[1] = d.kp; gains[2] = d.ki;
+        gains[3] = d.costas_alpha; gains[4] = d.costas_beta;
+    }
+    if (fll_lower_iq) std::memcpy(fll_lower_iq, d.fll_lower_iq.data(), 2 * qpsk::kFllTaps * sizeof(float));
+    if (fll_upper_iq) std::memcpy(fll_upper_iq, d.fll_upper_iq.data(), 2 * qpsk::kFllTaps * sizeof(float));
+    return T;
+}
+
+}  // extern "C"

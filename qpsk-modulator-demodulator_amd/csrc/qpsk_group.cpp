@@ -27,6 +27,7 @@
 
 #include "qpsk_demod.h"
 #include "qpsk_internal.h"
+#include "qpsk_quantise.h"
 #include "qpsk_state_blob.h"
 
 namespace {
@@ -212,9 +213,8 @@ int qpsk_demod_group_process_fmt(qpsk_demod_group *g, int32_t fmt, int32_t mode,
                                  uint8_t *bits, int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
                                  int64_t syms_stride_floats, int64_t *n_syms) {
     if (!g) return fail(QPSK_ERR_ARGUMENT_NULL, "null group");
-    const int sample_bytes = qpsk_fmt_sample_bytes(fmt);
-    if (sample_bytes < 0) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
-    const int64_t elem = sample_bytes / 2;   // bytes of one of a row's stride_elems elements
+    if (!qpsk::fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
+    const int64_t elem = qpsk::fmt_elem_bytes(fmt);   // bytes of one of a row's stride_elems elements
     const char *iq = static_cast<const char *>(iq_rows);
     // the check every shard would make, made once on the whole batch first, so
     // a bad argument fails the call before any shard's state moves

@@ -1,8 +1,9 @@
 // qpsk_internal.h -- what the host code behind the C ABI shares between its
 // translation units: the error channel, the per-call argument check and the
-// few things the ring (qpsk_rx.hip) and the group (qpsk_group.cpp) need from a
-// handle.  Private and host-only; the error channel is defined in
-// qpsk_error.cpp (no HIP), the rest in qpsk_runtime.hip.
+// two things the plain-C++ group (qpsk_group.cpp) needs from a handle it
+// cannot see (HIP files include qpsk_handle.h and read the members).  Private
+// and host-only; the error channel is defined in qpsk_error.cpp (no HIP), the
+// rest in qpsk_runtime.hip.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -28,7 +29,7 @@ struct CallArgs {
     float *syms;
     int64_t syms_stride_floats;
     int64_t *n_syms;
-    int32_t fmt = 0;         // QPSK_FMT_* (= kFmt*, qpsk_kernels.h)
+    int32_t fmt = 0;         // QPSK_FMT_*
     int64_t n_call = 0;      // derived by check_call: the longest row, and
     int64_t max_sym = 0;     // qpsk_demod_max_symbols of it
 };
@@ -43,9 +44,6 @@ int call_length(int S, int64_t n_samples, const int64_t *lengths, int64_t *n_cal
 // bound (a group's shards share it).  Fills c.n_call and c.max_sym.
 int check_call(const qpsk_demod *h, int S, CallArgs &c);
 
-int handle_streams(const qpsk_demod *h);
-int64_t handle_max_samples(const qpsk_demod *h);
-int handle_device(const qpsk_demod *h);
 int handle_taps(const qpsk_demod *h);   // of the matched filter
 // the host waits for every call queued on the handle, pipelined or stream-ordered
 int handle_sync(qpsk_demod *h);
@@ -55,30 +53,15 @@ int handle_sync(qpsk_demod *h);
 #ifdef __HIP__   // qpsk_group.cpp is plain C++
 #include <hip/hip_runtime.h>
 
-#include "qpsk_device.h"
-
 namespace qpsk {
-// the pipelined path's front-stage stream (qpsk_rx.hip records "input consumed"
-// on it); nullptr before the first pipelined call
-hipStream_t pipe_front_stream(const qpsk_demod *h);
-
-// What the rows of selected streams (qpsk_stream_state.hip) need from a handle:
-// its shape and stream, the four per-stream arrays of a state blob (hist: the
-// current one of the ping-pong pair, good until the next call is issued), the
-// link sums (nullptr until first enabled) and the staging buffer it keeps for
-// them, a member of the handle like its other buffers.
-struct StreamState;
-struct LinkAcc;
-struct StreamRows {
-    const qpsk_demod_params *p;
-    int S, T;
-    hipStream_t stream;
-    StreamState *state;
-    float *carry, *hist, *fll_delay;
-    LinkAcc *link;
-    DevBuf<char> *staging;
-};
-StreamRows handle_rows(qpsk_demod *h);
+// The status of a device allocation (a DevBuf's alloc or grow).  Without a
+// label the text carries HIP's own: "hipMalloc: <error>"; with one it names
+// what was being made: "hipMalloc (<label>)".
+inline int alloc_status(hipError_t e, const char *label = nullptr) {
+    if (e == hipSuccess) return QPSK_OK;
+    return fail(QPSK_ERR_DEVICE, label ? std::string("hipMalloc (") + label + ")"
+                                       : std::string("hipMalloc: ") + hipGetErrorString(e));
+}
 }  // namespace qpsk
 
 #define QPSK_HIP_TRY(expr)                                                                    \

@@ -4,9 +4,8 @@
 
 #include <cstdint>
 
+#include "qpsk_demod.h"
 #include "qpsk_state.h"
-
-struct qpsk_loop_shape;   // include/qpsk_demod.h
 
 namespace qpsk {
 
@@ -60,18 +59,14 @@ constexpr int kFirPhaseWords = 16;
 // Input element format of the matched filter's rows (QPSK_FMT_*).  x_stride
 // counts samples whatever the format, and a row's samples are widened to
 // float2 by the kernel that loads them:
-//   kFmtCf32  float pairs, read as they stand;
-//   kFmtCs16  int16 pairs, (float)v * x_scale;
-//   kFmtCs8 / kFmtCu8  byte pairs, ((float)(uint8)(v ^ x_flip) - 128) * x_scale:
+//   QPSK_FMT_CF32  float pairs, read as they stand;
+//   QPSK_FMT_CS16  int16 pairs, (float)v * x_scale;
+//   QPSK_FMT_CS8 / QPSK_FMT_CU8  byte pairs, ((float)(uint8)(v ^ x_flip) - 128) * x_scale:
 //             x_flip = 0x80 in every byte for CS8 (an int8 x is
 //             (uint8)(x ^ 0x80) - 128), 0 for CU8, so one set of kernels serves both.
 // The launchers fill x_scale and x_flip from their x_fmt and x_scale
 // arguments.  Both sit behind the members the float kernels read, whose
 // offsets (and so the float kernels' code) stay as they were.
-constexpr int32_t kFmtCf32 = 0;
-constexpr int32_t kFmtCs16 = 1;
-constexpr int32_t kFmtCs8 = 2;
-constexpr int32_t kFmtCu8 = 3;
 struct FirArgs {
     const float *x;        // [S][x_stride] input samples (float2, int16 pairs or byte pairs)
     int64_t x_stride;      // in samples
@@ -221,10 +216,10 @@ struct IqbArgs {
 // Returns true when a specialised tile kernel was used.
 // hrev_dev: the reversed RRC taps (ComplexFIRFilter._tapsIRev) in device memory.
 bool launch_fir(const FirArgs &a, const float *hrev_dev, int T, int W, int S,
-                int64_t n_max, hipStream_t stream, int32_t x_fmt = kFmtCf32, float x_scale = 0.0f);
+                int64_t n_max, hipStream_t stream, int32_t x_fmt = QPSK_FMT_CF32, float x_scale = 0.0f);
 void launch_fir_hist(const FirArgs &a, float *hist_new, int H, int S, hipStream_t stream,
-                     int32_t x_fmt = kFmtCf32, float x_scale = 0.0f);
-void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream, int32_t x_fmt = kFmtCs16);
+                     int32_t x_fmt = QPSK_FMT_CF32, float x_scale = 0.0f);
+void launch_widen(const WidenArgs &a, int S, int64_t n_max, hipStream_t stream, int32_t x_fmt = QPSK_FMT_CS16);
 // carry kernel + loop kernel; returns the loop kernel's workgroup count
 // variant = the requested qpsk_demod_params.loop_variant; cus = the device's CU
 // count, taps = the matched filter's (0: unknown), for the automatic shape

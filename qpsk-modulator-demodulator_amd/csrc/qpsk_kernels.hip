@@ -139,13 +139,13 @@ template <> struct Sample<b2> {
 };
 // f(XT{}) for the element type of QPSK_FMT_* x_fmt; CS8 and CU8 differ only in
 // the flip mask their argument block carries
-static unsigned flip_of(int32_t fmt) { return fmt == kFmtCs8 ? 0x80808080u : 0u; }
+static unsigned flip_of(int32_t fmt) { return fmt == QPSK_FMT_CS8 ? 0x80808080u : 0u; }
 template <typename F>
 static void with_format(int32_t x_fmt, F f) {
     switch (x_fmt) {
-    case kFmtCs16: return f(s2{});
-    case kFmtCs8:
-    case kFmtCu8: return f(b2{});
+    case QPSK_FMT_CS16: return f(s2{});
+    case QPSK_FMT_CS8:
+    case QPSK_FMT_CU8: return f(b2{});
     default: return f(f2{});
     }
 }
@@ -648,35 +648,6 @@ __global__ __launch_bounds__(256) void append_rows_kernel(AppendArgs a) {
 
 void launch_append(const AppendArgs &a, hipStream_t stream) {
     hipLaunchKernelGGL(append_rows_kernel, dim3(a.S), dim3(256), 0, stream, a);
-}
-
-// ---------------------------------------------------------------------------
-// Link statistics (qpsk_demod_link_stats): one qpsk_link_stats row per stream,
-// the three running sums from the accumulators and a copy of the loop state
-// from the stream record.  One lane per stream; reset zeroes the sums behind
-// the read (the lane that read them, so nothing is lost in between).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void link_stats_gather_kernel(LinkGatherArgs a) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= a.S) return;
-    const LinkAcc acc = a.acc[s];
-    const StreamState &st = a.state[s];
-    qpsk_link_stats r;
-    r.n_symbols = acc.n;
-    r.sum_dist2 = acc.sum_dist2;
-    r.sum_power = acc.sum_power;
-    r.costas_freq = st.freq;
-    r.costas_theta = st.theta;
-    r.mm_mu = st.mu;
-    r.mm_rate = st.integ;
-    r.fll_freq = a.fll ? st.fll_freq : 0.0f;
-    r.error = st.error;
-    static_cast<qpsk_link_stats *>(a.out)[s] = r;
-    if (a.reset) a.acc[s] = LinkAcc{0.0, 0.0, 0};
-}
-
-void launch_link_gather(const LinkGatherArgs &a, hipStream_t stream) {
-    hipLaunchKernelGGL(link_stats_gather_kernel, dim3((a.S + 255) / 256), dim3(256), 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------

@@ -41,6 +41,7 @@
 
 #include "qpsk_demod.h"
 #include "qpsk_glibc_trig.h"
+#include "qpsk_internal.h"
 #include "qpsk_kernels.h"
 #include "qpsk_sincos.h"
 
@@ -1312,3 +1313,16 @@ void loop_shape_info(int variant, int S, double sps, int cus, int taps, int trig
 }
 
 }  // namespace qpsk
+
+extern "C" {
+
+int qpsk_demod_loop_shape(int32_t requested, int32_t n_streams, double sps, int32_t cus, int32_t rrc_taps,
+                          int32_t costas_trig, int32_t want_syms, qpsk_loop_shape *out) {
+    if (!out) return qpsk::fail(QPSK_ERR_ARGUMENT_NULL, "out is NULL");
+    if (requested < 0 || requested > 7 || n_streams <= 0 || !(sps > 0.0) || costas_trig < 0 || costas_trig > 1)
+        return qpsk::fail(QPSK_ERR_ARGUMENT, "loop shape arguments");
+    qpsk::loop_shape_info(requested, n_streams, sps, cus, rrc_taps, costas_trig, want_syms, out);
+    return QPSK_OK;
+}
+
+}  // extern "C"

@@ -320,8 +320,8 @@ void launch_samples(int fmt, const SampArgs &a, dim3 grid, size_t lds, hipStream
     }
 }
 
-// the status of a staging buffer's grow
-int staged(hipError_t e) { return e == hipSuccess ? QPSK_OK : fail(QPSK_ERR_DEVICE, "hipMalloc (modulator staging)"); }
+// what a failed grow of a staging buffer names (alloc_status)
+constexpr const char *kStaging = "modulator staging";
 
 bool blank(const char *s) {
     if (!s) return true;
@@ -361,7 +361,7 @@ struct Call {
 
 // the checks that need no handle and no device, in one order for both entry points
 int check_format(const Call &c) {
-    if (!qpsk::quant_fmt_known(c.fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
+    if (!qpsk::fmt_known(c.fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
     if (c.norm != QPSK_MOD_NORM_FIXED && c.norm != QPSK_MOD_NORM_PEAK) return fail(QPSK_ERR_ARGUMENT, "unknown norm");
     if (c.norm == QPSK_MOD_NORM_PEAK && c.fmt == QPSK_FMT_CF32)
         return fail(QPSK_ERR_ARGUMENT, "QPSK_MOD_NORM_PEAK needs an integer format");
@@ -381,7 +381,7 @@ int modulate(qpsk_mod *m, const Call &c) {
     const int S = c.S;
     const bool host = c.mem == QPSK_MEM_HOST, peak_norm = c.norm == QPSK_MOD_NORM_PEAK;
     const int pulse = c.pulse != 0;
-    const int64_t elem = qpsk_fmt_sample_bytes(c.fmt) / 2;
+    const int64_t elem = qpsk::fmt_elem_bytes(c.fmt);
     std::vector<int64_t> cnt(S);
     if (host) std::memcpy(cnt.data(), c.counts, S * sizeof(int64_t));
     else QPSK_HIP_TRY(hipMemcpy(cnt.data(), c.counts, S * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -420,14 +420,14 @@ int modulate(qpsk_mod *m, const Call &c) {
     str.rows = c.rows;
     str.row_stride = c.row_stride;
     // the kernels read the counts the host checked, never the caller's device copy
-    if ((rc = staged(m->d_counts.grow(S * sizeof(int64_t))))) return rc;
+    if ((rc = qpsk::alloc_status(m->d_counts.grow(S * sizeof(int64_t)), kStaging))) return rc;
     QPSK_HIP_TRY(hipMemcpyAsync(m->d_counts, cnt.data(), S * sizeof(int64_t), hipMemcpyHostToDevice, st));
     str.counts = m->d_counts;
     std::vector<uint8_t> marks(static_cast<size_t>(c.n_start) + c.n_end);   // lives until the call's synchronise
     if (!marks.empty()) {
         std::memcpy(marks.data(), c.start, c.n_start);
         std::memcpy(marks.data() + c.n_start, c.end, c.n_end);
-        if ((rc = staged(m->d_marks.grow(marks.size())))) return rc;
+        if ((rc = qpsk::alloc_status(m->d_marks.grow(marks.size()), kStaging))) return rc;
         QPSK_HIP_TRY(hipMemcpyAsync(m->d_marks, marks.data(), marks.size(), hipMemcpyHostToDevice, st));
     }
     str.marks = m->d_marks;
@@ -436,24 +436,24 @@ int modulate(qpsk_mod *m, const Call &c) {
     a.peak = c.peak;
     if (host) {
         const size_t brow = static_cast<size_t>(row_bytes + 1);
-        if ((rc = staged(m->d_rows.grow(S * brow)))) return rc;
+        if ((rc = qpsk::alloc_status(m->d_rows.grow(S * brow), kStaging))) return rc;
         if (cnt_max > 0)
             QPSK_HIP_TRY(hipMemcpy2DAsync(m->d_rows, brow, c.rows, c.row_stride, row_bytes, S, hipMemcpyHostToDevice, st));
         str.rows = m->d_rows;
         str.row_stride = static_cast<int64_t>(brow);
         // 16-byte-pitched rows: the wide stores
         const int64_t pitch = (2 * std::max<int64_t>(tot_max, 1) * elem + 15) / 16 * 16;
-        if ((rc = staged(m->d_out.grow(static_cast<size_t>(S) * pitch)))) return rc;
+        if ((rc = qpsk::alloc_status(m->d_out.grow(static_cast<size_t>(S) * pitch), kStaging))) return rc;
         a.out = m->d_out;
         a.out_stride = pitch / elem;
         if (peak_norm) {
-            if ((rc = staged(m->d_peak.grow(S * sizeof(float))))) return rc;
+            if ((rc = qpsk::alloc_status(m->d_peak.grow(S * sizeof(float)), kStaging))) return rc;
             a.peak = m->d_peak;
         }
     }
     a.vec = reinterpret_cast<uintptr_t>(a.out) % 16 == 0 && (a.out_stride * elem) % 16 == 0;
     const int64_t quad_stride = (std::max<int64_t>(nd_max, 1) + 3) / 4 * 4;
-    if ((rc = staged(m->d_quad.grow(static_cast<size_t>(S) * quad_stride)))) return rc;
+    if ((rc = qpsk::alloc_status(m->d_quad.grow(static_cast<size_t>(S) * quad_stride), kStaging))) return rc;
     a.quad = m->d_quad;
     a.quad_stride = quad_stride;
     a.hs = m->d_hs;

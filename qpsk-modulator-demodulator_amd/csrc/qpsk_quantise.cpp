@@ -31,7 +31,7 @@ void store_int(int fmt, const float *iq, int64_t n, void *out, Fn value) {
 
 extern "C" int qpsk_quantise_iq(int32_t fmt, int32_t norm, float scale, const float *iq, int64_t n_floats, void *out,
                                 float *peak) {
-    if (!qpsk::quant_fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
+    if (!qpsk::fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
     if (norm != QPSK_MOD_NORM_FIXED && norm != QPSK_MOD_NORM_PEAK) return fail(QPSK_ERR_ARGUMENT, "unknown norm");
     if (norm == QPSK_MOD_NORM_PEAK && fmt == QPSK_FMT_CF32)
         return fail(QPSK_ERR_ARGUMENT, "QPSK_MOD_NORM_PEAK needs an integer format");

@@ -1,8 +1,9 @@
 // qpsk_quantise.h -- the one definition of how a float component of the
 // modulator's output becomes a CS16 / CS8 / CU8 (or scaled CF32) element.  The
 // sample kernel (qpsk_mod.hip) and the host function (qpsk_quantise.cpp) both
-// include it, so the device path and its reference cannot drift apart.  No HIP
-// header: plain C++ sees plain inline functions.
+// include it, so the device path and its reference cannot drift apart.  It also
+// holds the two facts every file asks of a sample format (fmt_known,
+// fmt_elem_bytes).  No HIP header: plain C++ sees plain inline functions.
 //
 //   FIXED  v = x * scale, one float multiply rounded once; clamp to [lo, hi];
 //          truncate toward zero -- the reference's
@@ -32,9 +33,14 @@ QPSK_HD int quant_lo(int fmt) { return fmt == QPSK_FMT_CS16 ? -32768 : -128; }
 // what is added to the clamped, truncated value before it is stored
 QPSK_HD int quant_zero(int fmt) { return fmt == QPSK_FMT_CU8 ? 128 : 0; }
 
-QPSK_HD bool quant_fmt_known(int fmt) {
-    return fmt == QPSK_FMT_CF32 || fmt == QPSK_FMT_CS16 || fmt == QPSK_FMT_CS8 || fmt == QPSK_FMT_CU8;
-}
+// The sample formats (QPSK_FMT_*), for every file that takes one, host or
+// device: whether a tag is one, and the bytes of one element of a row (two
+// elements a sample).
+constexpr int kFmts = 4;
+static_assert(QPSK_FMT_CF32 == 0 && QPSK_FMT_CS16 == 1 && QPSK_FMT_CS8 == 2 && QPSK_FMT_CU8 == kFmts - 1,
+              "the format tags count from 0 (CallArgs.fmt defaults to CF32)");
+QPSK_HD bool fmt_known(int fmt) { return fmt >= 0 && fmt < kFmts; }
+QPSK_HD int fmt_elem_bytes(int fmt) { return fmt == QPSK_FMT_CF32 ? 4 : (fmt == QPSK_FMT_CS16 ? 2 : 1); }
 
 // finite and > 0 (NaN fails both comparisons)
 QPSK_HD bool quant_scale_ok(float scale) { return scale > 0.0f && scale <= 3.4028234663852886e38f; }

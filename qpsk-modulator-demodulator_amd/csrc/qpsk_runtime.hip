@@ -20,33 +20,12 @@
 //
 // Every buffer, event and stream is a member that releases itself
 // (qpsk_device.h); the handle's destructor only waits for the queued work.
-//
-// Device layout (HBM, stream-major so every stage reads/writes each stream's
-// time axis contiguously):
-//   in      [S][n_max]              float2  staging for host input (CS16 calls:
-//                                           int16 pairs, rows of n_max rounded up to
-//                                           4 samples so they take 16-B loads;
-//                                           CS8 / CU8 calls: byte pairs, rows
-//                                           rounded up to 8 samples)
-//   fll_out [S][n_max]              float2  (FLL mode)
-//   hist    2 x [S][T-1]            float2  FIR delay line (ping-pong)
-//   mf      [2][S][256 + n_max]     float2  matched-filter output; the 256-slot
-//                                           prefix receives the M&M carry (the
-//                                           2nd only when pipelined)
-//   carry   [S][256]                float2  M&M retained samples
-//   state   [S]                     StreamState
-//   bits    [S][words]              uint32  MSB-first packed bits
-//   syms    [S][syms_cap]           float2  rotated symbols (on request)
-//   link    [S]                     LinkAcc link statistics' running sums (once enabled)
-//   rows    blob of n streams + [n] int32   staging of selected streams' rows (qpsk_stream_state.hip)
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -54,205 +33,31 @@
 #include <utility>
 #include <vector>
 
-#include "qpsk_demod.h"
-#include "qpsk_design.h"
-#include "qpsk_device.h"
-#include "qpsk_internal.h"
-#include "qpsk_kernels.h"
-#include "qpsk_state_blob.h"
+#include "qpsk_handle.h"
 
 using namespace qpsk;
 
 namespace {
-// the status of a DevBuf's alloc or grow
-int dev(hipError_t e) {
-    return e == hipSuccess ? QPSK_OK : fail(QPSK_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-}
-
-// launch-timestamp slots of one timed call, a pair per kernel: its (start, end)
-// span, then its clock sample (shader ticks, wall ticks); each list in the
-// order FLL, FIR, loop kernel.  qpsk_demod_enable_timing records the first
-// kKtCalls calls
-constexpr int kKtSpan[3] = {0, 2, 4};
-constexpr int kKtClk[3] = {8, 6, 10};
-constexpr int kKtFll = 0, kKtFir = 1, kKtLoop = 2;
-constexpr int kKtSpanSlots = 6;   // the slots below this hold spans
-constexpr int kKtPerCall = 12;
-constexpr int kKtCalls = 4096;
-constexpr int64_t kMaxSamplesPerCall = int64_t(1) << 30;
-// the symbol loop keeps sample indices of one call in 32-bit integers
-constexpr int64_t kMaxCallSamples = (int64_t(1) << 31) - 129;
-static_assert(kFmtCf32 == 0, "CallArgs.fmt defaults to CF32");
-static_assert(QPSK_FMT_CF32 == kFmtCf32 && QPSK_FMT_CS16 == kFmtCs16 && QPSK_FMT_CS8 == kFmtCs8 &&
-                  QPSK_FMT_CU8 == kFmtCu8,
-              "the ABI's format tags are the kernels'");
-constexpr int kFmts = 4;
-static_assert(sizeof(qpsk_link_stats) == 64 && offsetof(qpsk_link_stats, fll_freq) == 56 &&
-                  offsetof(qpsk_link_stats, error) == 60,
-              "qpsk_link_stats is 64 bytes without padding");
-
-struct Call : CallArgs {
-    // internal chunk of a longer call: outputs appended to dst_* at the running
-    // offsets d_acc (first chunk: from 0), totals to n_bits / n_syms after the last
-    bool append = false, first = false, last = false;
-    uint8_t *dst_bits = nullptr;
-    int64_t dst_bits_stride = 0;
-    float *dst_syms = nullptr;
-    int64_t dst_syms_stride = 0;
-    int64_t *dst_n_bits = nullptr;   // device; written after the last chunk
-    int64_t *dst_n_syms = nullptr;
-    // an integer-format call: the handle's scale of that format when the call was issued
-    float scale = 0.0f;
-};
-
-bool fmt_known(int32_t fmt) { return fmt >= 0 && fmt < kFmts; }
-bool fmt_8bit(int32_t fmt) { return fmt == kFmtCs8 || fmt == kFmtCu8; }
-// bytes of one element of a row (two elements a sample)
-size_t elem_bytes(int32_t fmt) { return fmt == kFmtCf32 ? sizeof(float) : fmt == kFmtCs16 ? sizeof(int16_t) : 1; }
+bool fmt_8bit(int32_t fmt) { return fmt == QPSK_FMT_CS8 || fmt == QPSK_FMT_CU8; }
 // samples a staged host row's pitch is a multiple of, so that the staged rows
 // take the format's 16-byte loads whatever max_samples_per_call is
 int64_t stage_pitch(int32_t fmt, int64_t n_max) {
-    const int64_t m = fmt == kFmtCf32 ? 1 : fmt == kFmtCs16 ? 4 : 8;
+    const int64_t m = fmt == QPSK_FMT_CF32 ? 1 : fmt == QPSK_FMT_CS16 ? 4 : 8;
     return (n_max + m - 1) / m * m;
 }
 const char *fmt_name(int32_t fmt) {
-    return fmt == kFmtCs16 ? "CS16" : fmt == kFmtCs8 ? "CS8" : fmt == kFmtCu8 ? "CU8" : "CF32";
+    return fmt == QPSK_FMT_CS16 ? "CS16" : fmt == QPSK_FMT_CS8 ? "CS8" : fmt == QPSK_FMT_CU8 ? "CU8" : "CF32";
 }
-
-// The first stage's input rows: the caller's (or the staged) rows in the
-// call's own format, until a pre-stage has rewritten them as float rows.
-struct InRows {
-    const void *x;
-    int64_t stride;   // samples
-    int32_t fmt;
-    float scale;
-};
 }  // namespace
 
-struct qpsk_demod {
-    qpsk_demod_params p{};
-    int S = 0;
-    int T = 0;
-    int W = 8;
-    LoopDesign d;
-    LoopParams lp{};
-    int loop_variant = 0;
-    FllParams fp{};
-    // the streams in front of every buffer and event: members go in reverse
-    // order of declaration, so what a stream's work used is released first
-    Stream stream;                   // the handle's own or its caller's (qpsk_demod_set_stream)
-    Stream s_front, s_back;          // pipelined calls
-    int64_t n_max = 0;
-    int64_t mf_stride = 0;       // float2
-    int64_t bits_words = 0;      // per stream
-    int64_t syms_cap = 0;        // per stream
-    DevBuf<float> d_hrev;
-    DevBuf<char> d_in;               // host-input staging, in the call's format
-    // per input format (CF32 has none): CS16 (float)int16 * scale, SoapySDR's
-    // CS16 -> CF32 convention; CS8 / CU8 full scale 128 (S8toF32, U8toS8)
-    float in_scale[kFmts] = {0.0f, 1.0f / 32768, 1.0f / 128, 1.0f / 128};
-    DevBuf<float> d_fll_out;         // [S][n_max] float2, FLL output (enable_fll only)
-    DevBuf<float> d_iqb;             // [S][n_max] float2, IQ_Balancer output (iq_balance only)
-    DevBuf<float> d_hist[2];
-    int hist_cur = 0;
-    DevBuf<float> d_mf[2];
-    DevBuf<float> d_carry;
-    DevBuf<StreamState> d_state;
-    DevBuf<float> d_fll_delay;
-    DevBuf<uint32_t> d_bits;
-    DevBuf<float> d_syms;
-    DevBuf<int64_t> d_counts;        // [2][S]: n_bits, n_syms
-    DevBuf<int64_t> d_lengths[2];
-    PinnedBuf<int64_t> h_counts;
-    // status flags (QPSK_STATUS_*): [0] = raised by device-memory calls since the
-    // last qpsk_demod_status, [1] = raised by the current host-memory call
-    DevBuf<uint32_t> d_flags;
-    PinnedBuf<uint32_t> h_flags;
-    uint32_t status_host = 0;        // raised by host-memory calls since the last status
-    // chunked calls (longer than max_samples_per_call): running per-stream
-    // output offsets [2][S] and, for host-memory calls, device staging of the
-    // whole call's output rows
-    DevBuf<int64_t> d_acc;
-    DevBuf<uint8_t> d_xbits;
-    DevBuf<float> d_xsyms;
-    // link statistics (qpsk_demod_link_stats): the per-stream running sums the
-    // loop kernel's decode wave continues while link_on, and the rows a
-    // host-memory read is gathered into (both made by the first enable)
-    bool link_on = false;
-    DevBuf<LinkAcc> d_link;
-    DevBuf<qpsk_link_stats> d_link_rows;
-    // rows of selected streams (qpsk_stream_state.hip): the packed sub-blob and
-    // the index list behind it, grown on demand
-    DevBuf<char> d_rows;
-    bool timing = false;
-    // launch timestamps of the timed calls ([call][kKtPerCall] wall-clock ticks,
-    // written by the kernels themselves: qpsk_kernels.h kt_start / kt_end)
-    DevBuf<unsigned long long> d_kt;
-    int kt_used = 0;
-    // FIR phase sample (qpsk_demod_enable_fir_phases): per-phase cycle sums
-    // [2][8] and the map of CUs a loop workgroup holds [kCuKeys]
-    bool fir_phases = false;
-    DevBuf<unsigned long long> d_phases;
-    DevBuf<unsigned> d_cu_map;
-    int wall_khz = 100000;
-    int cus = 0;
-    // ---- pipelined calls (qpsk_demod_process_async) ----------------------
-    bool pipe_ready = false;
-    int pipe_bufs = 0;               // 2 = double-buffered stage boundary, 1 = no room for it
-    int pipe_cur = 0;
-    Event e_in;
-    Event e_front[2], e_back[2];
-    // FLL off: residency counter (signal memory) the loop kernel's workgroups
-    // increment as they start; the next call's FIR waits for it to reach
-    // resident_gate (see process_async_one)
-    DevBuf<unsigned long long> d_resident;
-    uint64_t resident_issued = 0;    // workgroups of every gated loop launch so far
-    uint64_t resident_gate = 0;      // what the newest gated loop launch brings it to, at least
-    bool gate_pending = false;       // the next FIR has a loop launch to wait for
-    // off under a profiler's counter collection (rocprofv3 --pmc serialises
-    // every dispatch, so the wait would run to its cap on every call) or with
-    // QPSK_PIPELINE_GATE=0
-    bool use_gate = true;
-    // the wait is bounded (gate_wait_kernel): at most gate_cap_ticks of the
-    // wall clock (QPSK_GATE_TIMEOUT_MS, default 2000 ms), counted in d_gate[0]
-    // when it runs out; gate_publish = false (QPSK_GATE_NO_PUBLISH=1 together
-    // with QPSK_PIPELINE_GATE=1, tests only) keeps the loop workgroups from
-    // counting, so every wait runs out
-    DevBuf<unsigned> d_gate;
-    unsigned long long gate_cap_ticks = 0;
-    bool gate_publish = true;
-    int last_back = -1;              // boundary buffer of the newest back stage, -1 = none
-    PinnedBuf<int64_t> h_len[2];     // staging of per-call lengths
-    // FLL on: the back stage (loop kernel) of the newest call is issued by the
-    // next call, after that call's FLL, or by a flush (see process_async_one)
-    Event e_fll;
-    bool deferred = false;
-    Call dcall{};
-    int dbuf = 0;
-    const int64_t *dlen = nullptr;
-    unsigned long long *dkt = nullptr;
-
-    ~qpsk_demod();
-};
-
-namespace qpsk {
-// the pipelined path's front-stage stream (qpsk_rx.hip records "input consumed"
-// on it); nullptr before the first pipelined call
-hipStream_t pipe_front_stream(const qpsk_demod *h) { return h->s_front; }
-int handle_streams(const qpsk_demod *h) { return h->S; }
-int64_t handle_max_samples(const qpsk_demod *h) { return h->n_max; }
-int handle_device(const qpsk_demod *h) { return h->p.device; }
-int handle_taps(const qpsk_demod *h) { return h->T; }
-StreamRows handle_rows(qpsk_demod *h) {
-    return StreamRows{&h->p,      h->S,       h->T,      h->stream,  h->d_state, h->d_carry, h->d_hist[h->hist_cur],
-                      h->d_fll_delay, h->d_link, &h->d_rows};
-}
-}  // namespace qpsk
+int qpsk::handle_taps(const qpsk_demod *h) { return h->T; }
 
 namespace {
 
 // The newest pipelined call's back stage, or nullptr.
-const Event *last_async(const qpsk_demod *h) { return h->last_back >= 0 ? &h->e_back[h->last_back] : nullptr; }
+const Event *last_async(const qpsk_demod *h) {
+    return h->pipe.last_back >= 0 ? &h->pipe.e_back[h->pipe.last_back] : nullptr;
+}
 
 int flush_deferred(qpsk_demod *h);   // issues a deferred back stage (with the stage runners)
 
@@ -271,7 +76,7 @@ int ensure_syms(qpsk_demod *h) {
     // on the handle's device whatever the calling thread's current one is
     // (a group's worker threads, qpsk_group.cpp)
     QPSK_HIP_TRY(hipSetDevice(h->p.device));
-    return dev(h->d_syms.alloc(static_cast<size_t>(2 * h->S * h->syms_cap)));
+    return alloc_status(h->d_syms.alloc(static_cast<size_t>(2 * h->S * h->syms_cap)));
 }
 
 }  // namespace
@@ -328,10 +133,10 @@ int qpsk::check_call(const qpsk_demod *h, int S, CallArgs &c) {
     if (c.syms && c.syms_stride_floats < 2 * max_sym)
         return fail(QPSK_ERR_ARGUMENT, "syms_stride_floats smaller than 2*max_symbols");
     if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && (c.stride_floats & 1))
-        return fail(QPSK_ERR_ARGUMENT, c.fmt == kFmtCs16   ? "device stride_i16 must be even"
+        return fail(QPSK_ERR_ARGUMENT, c.fmt == QPSK_FMT_CS16   ? "device stride_i16 must be even"
                                        : fmt_8bit(c.fmt) ? "device stride_elems of 8-bit rows must be even"
                                                          : "device stride_floats must be even");
-    if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && c.fmt == kFmtCs16 && (reinterpret_cast<uintptr_t>(c.iq) & 3))
+    if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && c.fmt == QPSK_FMT_CS16 && (reinterpret_cast<uintptr_t>(c.iq) & 3))
         return fail(QPSK_ERR_ARGUMENT, "device CS16 rows must be 4-byte aligned");
     if (n_call > 0 && c.mem == QPSK_MEM_DEVICE && fmt_8bit(c.fmt) && (reinterpret_cast<uintptr_t>(c.iq) & 1))
         return fail(QPSK_ERR_ARGUMENT, "device CS8 / CU8 rows must be 2-byte aligned");
@@ -344,8 +149,8 @@ namespace {
 
 // the launch-timestamp slots of the next timed call, or nullptr
 unsigned long long *next_kt(qpsk_demod *h) {
-    if (!h->timing || !h->d_kt || h->kt_used >= kKtCalls) return nullptr;
-    return h->d_kt + static_cast<size_t>(kKtPerCall) * h->kt_used++;
+    if (!h->probe.timing || !h->probe.d_kt || h->probe.kt_used >= kKtCalls) return nullptr;
+    return h->probe.d_kt + static_cast<size_t>(kKtPerCall) * h->probe.kt_used++;
 }
 
 // optional IQ_Balancer pre-stage (IQ Balancer.cs:15-25) into d_iqb
@@ -379,14 +184,14 @@ void run_fll(qpsk_demod *h, const float *x, int64_t x_stride, const int64_t *d_l
 // Float rows pass through.
 const float *float_rows(qpsk_demod *h, InRows *in, const int64_t *d_len, int64_t n_call, float *mf,
                         hipStream_t st) {
-    if (in->fmt != kFmtCf32) {
+    if (in->fmt != QPSK_FMT_CF32) {
         WidenArgs wa{};
         wa.x = in->x; wa.x_stride = in->stride;
         wa.y = mf; wa.y_stride = h->mf_stride; wa.y_offset = kMfPrefix;
         wa.lengths = d_len; wa.n = n_call;
         wa.x_scale = in->scale;
         launch_widen(wa, h->S, n_call, st, in->fmt);
-        *in = InRows{mf + 2 * kMfPrefix, h->mf_stride, kFmtCf32, 0.0f};
+        *in = InRows{mf + 2 * kMfPrefix, h->mf_stride, QPSK_FMT_CF32, 0.0f};
     }
     return static_cast<const float *>(in->x);
 }
@@ -400,12 +205,12 @@ void pre_stages(qpsk_demod *h, InRows *in, const int64_t *d_len, int64_t n_call,
     if (h->p.iq_balance) {
         const float *x = float_rows(h, in, d_len, n_call, mf, st);
         run_iqb(h, x, in->stride, d_len, n_call, st);
-        *in = InRows{h->d_iqb, h->n_max, kFmtCf32, 0.0f};
+        *in = InRows{h->d_iqb, h->n_max, QPSK_FMT_CF32, 0.0f};
     }
     if (h->p.enable_fll) {
         const float *x = float_rows(h, in, d_len, n_call, mf, st);
         run_fll(h, x, in->stride, d_len, n_call, h->d_fll_out, st, kt);
-        *in = InRows{h->d_fll_out, h->n_max, kFmtCf32, 0.0f};
+        *in = InRows{h->d_fll_out, h->n_max, QPSK_FMT_CF32, 0.0f};
     }
 }
 
@@ -419,9 +224,9 @@ int run_fir(qpsk_demod *h, const InRows &in, const int64_t *d_len, int64_t n_cal
     fa.y = mf; fa.y_stride = h->mf_stride; fa.y_offset = kMfPrefix;
     fa.kt = kt ? kt + kKtSpan[kKtFir] : nullptr;
     fa.clk = kt ? kt + kKtClk[kKtFir] : nullptr;
-    if (h->fir_phases) {
-        fa.phases = h->d_phases;
-        fa.cu_map = h->d_cu_map;
+    if (h->probe.fir_phases) {
+        fa.phases = h->probe.d_phases;
+        fa.cu_map = h->probe.d_cu_map;
     }
     if (n_call > 0) {
         launch_fir(fa, h->d_hrev, h->T, h->W, h->S, n_call, st, in.fmt, in.scale);
@@ -456,10 +261,10 @@ __global__ void gate_wait_kernel(const unsigned long long *resident, unsigned lo
 }
 
 int gate_wait(qpsk_demod *h, hipStream_t st) {
-    if (!h->gate_pending) return QPSK_OK;
-    h->gate_pending = false;
-    hipLaunchKernelGGL(gate_wait_kernel, dim3(1), dim3(64), 0, st, h->d_resident,
-                       static_cast<unsigned long long>(h->resident_gate), h->gate_cap_ticks, h->d_gate);
+    if (!h->pipe.gate_pending) return QPSK_OK;
+    h->pipe.gate_pending = false;
+    hipLaunchKernelGGL(gate_wait_kernel, dim3(1), dim3(64), 0, st, h->pipe.d_resident,
+                       static_cast<unsigned long long>(h->pipe.resident_gate), h->pipe.gate_cap_ticks, h->pipe.d_gate);
     QPSK_HIP_TRY(hipGetLastError());
     return QPSK_OK;
 }
@@ -480,7 +285,7 @@ int host_epilogue(qpsk_demod *h, const Call &c, const int64_t *counts, hipStream
 
 // symbol sync + Costas + decode (QPSKDeModulator.cs:364-408) and the output copies
 // resident: the pipelined path's residency counter (nullptr otherwise); the
-// launch's workgroup count is added to h->resident_issued
+// launch's workgroup count is added to h->pipe.resident_issued
 int run_loop(qpsk_demod *h, const Call &c, const int64_t *d_len, float *mf, hipStream_t st,
              unsigned long long *kt, unsigned long long *resident = nullptr) {
     const int S = h->S;
@@ -497,7 +302,7 @@ int run_loop(qpsk_demod *h, const Call &c, const int64_t *d_len, float *mf, hipS
     la.syms_stride = h->syms_cap;
     la.syms_cap = h->syms_cap;
     la.n_syms = h->d_counts + S;
-    la.set_link(h->link_on ? h->d_link : nullptr);
+    la.set_link(h->link.on ? h->link.d_link : nullptr);
     // device-memory outputs whose rows the kernel can address as its own (4-B
     // aligned word rows holding every word a row can take; float2-aligned
     // symbol rows): written in place, no staging copy behind the kernel
@@ -529,17 +334,17 @@ int run_loop(qpsk_demod *h, const Call &c, const int64_t *d_len, float *mf, hipS
     la.chunked = c.append ? 1 : 0;
     la.kt = kt ? kt + kKtSpan[kKtLoop] : nullptr;
     la.clk = kt ? kt + kKtClk[kKtLoop] : nullptr;
-    la.cu_map = h->fir_phases ? h->d_cu_map : nullptr;
-    la.resident = h->gate_publish ? resident : nullptr;
+    la.cu_map = h->probe.fir_phases ? h->probe.d_cu_map : nullptr;
+    la.resident = h->pipe.gate_publish ? resident : nullptr;
     const int grid = launch_loop(la, h->lp, c.mode, h->loop_variant, st, h->cus, h->T);
     QPSK_HIP_TRY(hipGetLastError());
     if (resident) {
         // the next FIR may start once min(grid, CUs) workgroups hold their CUs:
         // at most one 104-147 KB loop workgroup fits a CU, and those are the
         // first ones dispatched (never more than there are)
-        h->resident_gate = h->resident_issued + static_cast<uint64_t>(std::min(grid, std::max(h->cus, 1)));
-        h->resident_issued += static_cast<uint64_t>(grid);
-        h->gate_pending = true;
+        h->pipe.resident_gate = h->pipe.resident_issued + static_cast<uint64_t>(std::min(grid, std::max(h->cus, 1)));
+        h->pipe.resident_issued += static_cast<uint64_t>(grid);
+        h->pipe.gate_pending = true;
     }
     if (c.append) {
         AppendArgs aa{};
@@ -589,8 +394,8 @@ int issue_back(qpsk_demod *h, const Call &c, const int64_t *d_len, int buf, unsi
                unsigned long long *resident) {
     int rc;
     if ((rc = run_loop(h, c, d_len, h->d_mf[buf], h->s_back, kt, resident))) return rc;
-    QPSK_HIP_TRY(h->e_back[buf].record(h->s_back));
-    h->last_back = buf;
+    QPSK_HIP_TRY(h->pipe.e_back[buf].record(h->s_back));
+    h->pipe.last_back = buf;
     return QPSK_OK;
 }
 
@@ -602,7 +407,7 @@ namespace {
 // The back stream gets the device's highest priority: its loop kernel is the
 // latency-bound stage, the front stage fills the CUs it leaves idle.
 int pipe_setup(qpsk_demod *h) {
-    if (h->pipe_ready) return QPSK_OK;
+    if (h->pipe.ready) return QPSK_OK;
     // every step makes what is missing and keeps what is there: a set-up that
     // failed part way runs again on the next pipelined call and completes,
     // without re-zeroing the counters it already made
@@ -610,26 +415,26 @@ int pipe_setup(qpsk_demod *h) {
     QPSK_HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
     QPSK_HIP_TRY(h->s_front.create(hipStreamNonBlocking, least));
     QPSK_HIP_TRY(h->s_back.create(hipStreamNonBlocking, greatest));
-    QPSK_HIP_TRY(h->e_in.ensure());
+    QPSK_HIP_TRY(h->pipe.e_in.ensure());
     for (int b = 0; b < 2; ++b) {
-        QPSK_HIP_TRY(h->e_front[b].ensure());
-        QPSK_HIP_TRY(h->e_back[b].ensure());
-        QPSK_HIP_TRY(h->h_len[b].alloc(h->S));
+        QPSK_HIP_TRY(h->pipe.e_front[b].ensure());
+        QPSK_HIP_TRY(h->pipe.e_back[b].ensure());
+        QPSK_HIP_TRY(h->pipe.h_len[b].alloc(h->S));
     }
-    QPSK_HIP_TRY(h->e_fll.ensure());
-    if (!h->d_resident) {
+    QPSK_HIP_TRY(h->pipe.e_fll.ensure());
+    if (!h->pipe.d_resident) {
         // signal memory: the one allocation made here, released like any other
         unsigned long long *r = nullptr;
         QPSK_HIP_TRY(hipExtMallocWithFlags(reinterpret_cast<void **>(&r), sizeof(*r), hipMallocSignalMemory));
-        h->d_resident.adopt(r, sizeof(*r));
-        QPSK_HIP_TRY(hipMemset(h->d_resident, 0, sizeof(unsigned long long)));
+        h->pipe.d_resident.adopt(r, sizeof(*r));
+        QPSK_HIP_TRY(hipMemset(h->pipe.d_resident, 0, sizeof(unsigned long long)));
     }
     int rc;
-    if (!h->d_gate) {
-        if ((rc = dev(h->d_gate.alloc(1)))) return rc;
-        QPSK_HIP_TRY(hipMemset(h->d_gate, 0, sizeof(unsigned)));
+    if (!h->pipe.d_gate) {
+        if ((rc = alloc_status(h->pipe.d_gate.alloc(1)))) return rc;
+        QPSK_HIP_TRY(hipMemset(h->pipe.d_gate, 0, sizeof(unsigned)));
     }
-    if ((rc = dev(h->d_lengths[1].alloc(h->S)))) return rc;
+    if ((rc = alloc_status(h->d_lengths[1].alloc(h->S)))) return rc;
     // the second boundary buffer: MF rows (the FIR of one call writes one while
     // the loop kernel of the previous call reads the other).  No room for it
     // (batches near the 288 GB) -> calls still queue back to back, but each
@@ -642,8 +447,8 @@ int pipe_setup(qpsk_demod *h) {
     // as at creation: the memsets above (counter, gate, MF rows) ran on the null
     // stream and are done before any pipelined call uses what they cleared
     QPSK_HIP_TRY(hipStreamSynchronize(nullptr));
-    h->pipe_bufs = h->d_mf[1] ? 2 : 1;
-    h->pipe_ready = true;
+    h->pipe.bufs = h->d_mf[1] ? 2 : 1;
+    h->pipe.ready = true;
     return QPSK_OK;
 }
 
@@ -747,17 +552,17 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
     if (hipDeviceGetAttribute(&h->wall_khz, hipDeviceAttributeWallClockRate, p->device) != hipSuccess ||
         h->wall_khz <= 0)
         h->wall_khz = 100000;
-    h->use_gate = qpsk_pipeline_gate_enabled() == 1;
+    h->pipe.use_gate = qpsk_pipeline_gate_enabled() == 1;
     {
         const char *v = std::getenv("QPSK_GATE_TIMEOUT_MS");
         const long ms = v && *v ? std::strtol(v, nullptr, 10) : 2000;
-        h->gate_cap_ticks = static_cast<unsigned long long>(ms > 0 ? ms : 1) * static_cast<unsigned>(h->wall_khz);
+        h->pipe.gate_cap_ticks = static_cast<unsigned long long>(ms > 0 ? ms : 1) * static_cast<unsigned>(h->wall_khz);
         // test hook, honoured only beside an explicit QPSK_PIPELINE_GATE=1: a
         // stray QPSK_GATE_NO_PUBLISH alone must not make every call wait out the cap
         const char *np = std::getenv("QPSK_GATE_NO_PUBLISH");
         const char *force = std::getenv("QPSK_PIPELINE_GATE");
         const bool forced = force && std::strcmp(force, "1") == 0;
-        h->gate_publish = !(forced && np && *np && std::strcmp(np, "0") != 0);
+        h->pipe.gate_publish = !(forced && np && *np && std::strcmp(np, "0") != 0);
     }
     if (h->stream.create(hipStreamNonBlocking) != hipSuccess) return fail(QPSK_ERR_DEVICE, "hipStreamCreate failed");
 
@@ -776,20 +581,14 @@ int qpsk_demod_create(const qpsk_demod_params *p, int32_t n_streams, qpsk_demod 
         (e = h->d_lengths[0].alloc(S)) ||
         (p->enable_fll && (e = h->d_fll_out.alloc(static_cast<size_t>(2 * S * h->n_max)))) ||
         (p->iq_balance && (e = h->d_iqb.alloc(static_cast<size_t>(2 * S * h->n_max)))))
-        return dev(e);
+        return alloc_status(e);
     if (h->h_counts.alloc(2 * S) != hipSuccess || h->h_flags.alloc(1) != hipSuccess)
         return fail(QPSK_ERR_DEVICE, "hipHostMalloc");
-    if ((rc = dev(h->d_flags.alloc(2))) || hipMemset(h->d_flags, 0, 2 * sizeof(uint32_t)) != hipSuccess)
+    if ((rc = alloc_status(h->d_flags.alloc(2))) || hipMemset(h->d_flags, 0, 2 * sizeof(uint32_t)) != hipSuccess)
         return rc ? rc : fail(QPSK_ERR_DEVICE, "hipMemset");
     std::vector<float> hrev(h->T);
     for (int k = 0; k < h->T; ++k) hrev[k] = h->d.rrc_f32[h->T - 1 - k];
-    // Fresh instances: zero delay lines (FIRFilter.cs:50-51), M&M baseIndex = 1
-    // (MuellerMuller.cs:44), everything else zero.
-    std::vector<StreamState> st(S);
-    for (auto &x : st) {
-        std::memset(&x, 0, sizeof(x));
-        x.base = 1;
-    }
+    std::vector<StreamState> st(S, fresh_stream_state());
     if (hipMemcpy(h->d_hrev, hrev.data(), h->T * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->d_state, st.data(), S * sizeof(StreamState), hipMemcpyHostToDevice) != hipSuccess ||
         (H > 0 && hipMemset(h->d_hist[0], 0, 2 * S * H * sizeof(float)) != hipSuccess) ||
@@ -819,139 +618,6 @@ int qpsk_demod_set_stream(qpsk_demod *h, void *hip_stream) {
     return QPSK_OK;
 }
 
-int qpsk_demod_enable_timing(qpsk_demod *h, int32_t on) {
-    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    h->kt_used = 0;
-    h->timing = on != 0;
-    if (!h->timing) return QPSK_OK;
-    QPSK_HIP_TRY(hipSetDevice(h->p.device));
-    int rc;
-    const size_t n = static_cast<size_t>(kKtCalls) * kKtPerCall;
-    if ((rc = dev(h->d_kt.alloc(n)))) return rc;
-    // spans: start = +inf for the atomic minimum, end = 0 for the maximum;
-    // clock sums = 0
-    std::vector<unsigned long long> init(n, 0ull);
-    for (size_t i = 0; i < n; i += 2)
-        if (i % kKtPerCall < kKtSpanSlots) init[i] = ~0ull;
-    if ((rc = handle_sync(h))) return rc;
-    QPSK_HIP_TRY(hipMemcpy(h->d_kt, init.data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    return QPSK_OK;
-}
-
-int qpsk_demod_enable_fir_phases(qpsk_demod *h, int32_t on) {
-    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    int rc;
-    if ((rc = handle_sync(h))) return rc;
-    if (on && (!h->d_phases || !h->d_cu_map)) {
-        // both or neither: a half-allocated pair would let the sampled FIR
-        // workgroups read a null cu_map
-        if ((rc = dev(h->d_phases.alloc(kFirPhaseWords))) || (rc = dev(h->d_cu_map.alloc(kCuKeys)))) {
-            h->d_phases.reset();
-            h->d_cu_map.reset();
-            return rc;
-        }
-        QPSK_HIP_TRY(hipMemset(h->d_cu_map, 0, kCuKeys * sizeof(unsigned)));
-    }
-    if (on) QPSK_HIP_TRY(hipMemset(h->d_phases, 0, kFirPhaseWords * sizeof(unsigned long long)));
-    h->fir_phases = on != 0;
-    return QPSK_OK;
-}
-
-int qpsk_demod_fir_phases(qpsk_demod *h, uint64_t *out, int32_t n) {
-    if (!h || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    if (n < kFirPhaseWords) return fail(QPSK_ERR_ARGUMENT, "n < 16");
-    if (!h->d_phases) {
-        std::memset(out, 0, kFirPhaseWords * sizeof(uint64_t));
-        return kFirPhaseWords;
-    }
-    int rc;
-    if ((rc = handle_sync(h))) return rc;
-    QPSK_HIP_TRY(hipMemcpy(out, h->d_phases, kFirPhaseWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    QPSK_HIP_TRY(hipMemset(h->d_phases, 0, kFirPhaseWords * sizeof(unsigned long long)));
-    return kFirPhaseWords;
-}
-
-// the timestamp slots of the timed calls so far, once every one of them has run
-static int read_kt(qpsk_demod *h, std::vector<unsigned long long> *t) {
-    int rc;
-    if ((rc = handle_sync(h))) return rc;
-    if (h->s_front) QPSK_HIP_TRY(hipStreamSynchronize(h->s_front));
-    if (h->s_back) QPSK_HIP_TRY(hipStreamSynchronize(h->s_back));
-    t->resize(static_cast<size_t>(h->kt_used) * kKtPerCall);
-    QPSK_HIP_TRY(hipMemcpy(t->data(), h->d_kt, t->size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return QPSK_OK;
-}
-
-// per timed call: FLL, FIR and loop kernel durations and the call's kernel
-// span (earliest start to latest end), ms; 0 for a kernel that did not run
-static int read_launch_times(qpsk_demod *h, std::vector<float> *out) {
-    out->assign(static_cast<size_t>(h->kt_used) * 4, 0.f);
-    if (!h->kt_used) return QPSK_OK;
-    int rc;
-    std::vector<unsigned long long> t;
-    if ((rc = read_kt(h, &t))) return rc;
-    const double ms_per_tick = 1.0 / h->wall_khz;
-    for (int c = 0; c < h->kt_used; ++c) {
-        const unsigned long long *k = t.data() + static_cast<size_t>(kKtPerCall) * c;
-        unsigned long long lo = ~0ull, hi = 0;
-        for (int j = 0; j < 3; ++j) {
-            const unsigned long long s0 = k[kKtSpan[j]], e0 = k[kKtSpan[j] + 1];
-            if (s0 == ~0ull || e0 < s0) continue;   // did not run
-            (*out)[4 * c + j] = static_cast<float>((e0 - s0) * ms_per_tick);
-            lo = std::min(lo, s0);
-            hi = std::max(hi, e0);
-        }
-        if (hi >= lo && lo != ~0ull) (*out)[4 * c + 3] = static_cast<float>((hi - lo) * ms_per_tick);
-    }
-    return QPSK_OK;
-}
-
-int qpsk_demod_stage_times(qpsk_demod *h, float *ms, int32_t n) {
-    if (!h || !ms) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    std::vector<float> t;
-    int rc;
-    if ((rc = read_launch_times(h, &t))) return rc;
-    const int k = std::min<int32_t>(n, 4);
-    for (int i = 0; i < k; ++i) {
-        double sum = 0;
-        int cnt = 0;
-        for (int c = 0; c < h->kt_used; ++c)
-            if (t[4 * c + i] > 0.f) {
-                sum += t[4 * c + i];
-                ++cnt;
-            }
-        ms[i] = cnt ? static_cast<float>(sum / cnt) : 0.f;
-    }
-    return k;
-}
-
-int qpsk_demod_kernel_clocks(qpsk_demod *h, float *ghz, int32_t max_calls) {
-    if (!h || !ghz) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    if (!h->kt_used) return 0;
-    int rc;
-    std::vector<unsigned long long> t;
-    if ((rc = read_kt(h, &t))) return rc;
-    const int k = std::min<int32_t>(max_calls, h->kt_used);
-    for (int c = 0; c < k; ++c) {
-        const unsigned long long *s = t.data() + static_cast<size_t>(kKtPerCall) * c;
-        for (int j = 0; j < 3; ++j) {
-            const unsigned long long cy = s[kKtClk[j]], wt = s[kKtClk[j] + 1];
-            ghz[3 * c + j] = wt ? static_cast<float>(static_cast<double>(cy) / wt * h->wall_khz * 1e-6) : 0.f;
-        }
-    }
-    return k;
-}
-
-int qpsk_demod_launch_times(qpsk_demod *h, float *ms, int32_t max_calls) {
-    if (!h || !ms) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    std::vector<float> t;
-    int rc;
-    if ((rc = read_launch_times(h, &t))) return rc;
-    const int k = std::min<int32_t>(max_calls, h->kt_used);
-    std::memcpy(ms, t.data(), static_cast<size_t>(k) * 4 * sizeof(float));
-    return k;
-}
-
 }  // extern "C"
 
 namespace {
@@ -977,10 +643,10 @@ int process_one(qpsk_demod *h, const Call &c) {
     if (n_call > 0 && mem == QPSK_MEM_HOST) {
         // staged in the call's own format: a CS16 call uploads 4 bytes a
         // sample, a CS8 / CU8 call 2
-        const size_t eb = elem_bytes(c.fmt);
+        const size_t eb = fmt_elem_bytes(c.fmt);
         const int64_t pitch = stage_pitch(c.fmt, h->n_max);   // samples
         // the last host-memory call has returned, so nothing reads d_in
-        if ((rc = dev(h->d_in.grow(static_cast<size_t>(S) * pitch * 2 * eb)))) return rc;
+        if ((rc = alloc_status(h->d_in.grow(static_cast<size_t>(S) * pitch * 2 * eb)))) return rc;
         QPSK_HIP_TRY(hipMemcpy2DAsync(h->d_in, 2 * pitch * eb, c.iq, stride_floats * eb, 2 * n_call * eb, S,
                                       hipMemcpyHostToDevice, st));
         in.x = h->d_in;
@@ -1005,24 +671,24 @@ int process_async_one(qpsk_demod *h, const Call &c) {
     if ((rc = pipe_setup(h))) return rc;
     const int S = h->S;
     const int64_t n_call = c.n_call;
-    const int b = h->pipe_bufs == 2 ? h->pipe_cur : 0;
-    h->pipe_cur ^= 1;
+    const int b = h->pipe.bufs == 2 ? h->pipe.cur : 0;
+    h->pipe.cur ^= 1;
     hipStream_t F = h->s_front, B = h->s_back;
 
     // the front stage starts after the work already on the handle's stream
     // (the producer of iq, earlier synchronous calls) and after the back stage
     // that last used boundary buffer b
-    QPSK_HIP_TRY(h->e_in.record(h->stream));
-    QPSK_HIP_TRY(h->e_in.wait(F));
-    const int prev = h->pipe_bufs == 2 ? b : h->last_back;
-    if (prev >= 0) QPSK_HIP_TRY(h->e_back[prev].wait(F));
+    QPSK_HIP_TRY(h->pipe.e_in.record(h->stream));
+    QPSK_HIP_TRY(h->pipe.e_in.wait(F));
+    const int prev = h->pipe.bufs == 2 ? b : h->pipe.last_back;
+    if (prev >= 0) QPSK_HIP_TRY(h->pipe.e_back[prev].wait(F));
     unsigned long long *kt = next_kt(h);
     const int64_t *d_len = nullptr;
     if (lengths) {
         // pinned staging row b is free once the front stage that last read it ran
-        QPSK_HIP_TRY(h->e_front[b].sync());
-        std::memcpy(h->h_len[b], lengths, S * sizeof(int64_t));
-        QPSK_HIP_TRY(hipMemcpyAsync(h->d_lengths[b], h->h_len[b], S * sizeof(int64_t), hipMemcpyHostToDevice, F));
+        QPSK_HIP_TRY(h->pipe.e_front[b].sync());
+        std::memcpy(h->pipe.h_len[b], lengths, S * sizeof(int64_t));
+        QPSK_HIP_TRY(hipMemcpyAsync(h->d_lengths[b], h->pipe.h_len[b], S * sizeof(int64_t), hipMemcpyHostToDevice, F));
         d_len = h->d_lengths[b];
     }
     InRows in{c.iq, stride_floats / 2, c.fmt, c.scale};
@@ -1031,7 +697,7 @@ int process_async_one(qpsk_demod *h, const Call &c) {
     // IQ balancer's rows are read only by this call's own front stage (FLL or
     // FIR on F).
     float *mf = h->d_mf[b];
-    unsigned long long *resident = h->use_gate ? h->d_resident : nullptr;
+    unsigned long long *resident = h->pipe.use_gate ? h->pipe.d_resident : nullptr;
     pre_stages(h, &in, d_len, n_call, mf, F, kt);
     if (h->p.enable_fll) {
         // FLL on (C5): the FLL keeps every SIMD's VALU busy with one wave each
@@ -1044,22 +710,22 @@ int process_async_one(qpsk_demod *h, const Call &c) {
         // a flush (pipeline_wait, a synchronous call, state access, destroy).
         // FLL(k) waited above for loop(k-2), the last reader of MF rows b, and
         // follows FIR(k-1) on F, so it runs alone.
-        QPSK_HIP_TRY(h->e_fll.record(F));
-        if (h->deferred) {
-            QPSK_HIP_TRY(h->e_fll.wait(B));
-            h->deferred = false;
-            if ((rc = issue_back(h, h->dcall, h->dlen, h->dbuf, h->dkt, resident))) return rc;
+        QPSK_HIP_TRY(h->pipe.e_fll.record(F));
+        if (h->pipe.deferred) {
+            QPSK_HIP_TRY(h->pipe.e_fll.wait(B));
+            h->pipe.deferred = false;
+            if ((rc = issue_back(h, h->pipe.dcall, h->pipe.dlen, h->pipe.dbuf, h->pipe.dkt, resident))) return rc;
         }
         if ((rc = gate_wait(h, F))) return rc;
         if ((rc = run_fir(h, in, d_len, n_call, mf, F, kt))) return rc;
-        QPSK_HIP_TRY(h->e_front[b].record(F));
-        h->dcall = c;
-        h->dbuf = b;
-        h->dlen = d_len;
-        h->dkt = kt;
-        h->deferred = true;
+        QPSK_HIP_TRY(h->pipe.e_front[b].record(F));
+        h->pipe.dcall = c;
+        h->pipe.dbuf = b;
+        h->pipe.dlen = d_len;
+        h->pipe.dkt = kt;
+        h->pipe.deferred = true;
         // one MF buffer only: nothing can overlap, issue the back stage now
-        return h->pipe_bufs == 2 ? QPSK_OK : flush_deferred(h);
+        return h->pipe.bufs == 2 ? QPSK_OK : flush_deferred(h);
     } else {
         // front = FIR into MF rows b; back = loop.  FIR(k+1) and loop(k) both
         // become ready when a stage of call k-1 or k ends, and whichever is
@@ -1077,19 +743,19 @@ int process_async_one(qpsk_demod *h, const Call &c) {
         // workgroups run, and every one of those was dispatched before it.
         if ((rc = gate_wait(h, F))) return rc;
         if ((rc = run_fir(h, in, d_len, n_call, mf, F, kt))) return rc;
-        QPSK_HIP_TRY(h->e_front[b].record(F));
-        QPSK_HIP_TRY(h->e_front[b].wait(B));
+        QPSK_HIP_TRY(h->pipe.e_front[b].record(F));
+        QPSK_HIP_TRY(h->pipe.e_front[b].wait(B));
     }
     return issue_back(h, c, d_len, b, kt, resident);
 }
 
 // The deferred back stage (FLL on) after its own FIR only: nothing follows it.
 int flush_deferred(qpsk_demod *h) {
-    if (!h->deferred) return QPSK_OK;
+    if (!h->pipe.deferred) return QPSK_OK;
     QPSK_HIP_TRY(hipSetDevice(h->p.device));
-    h->deferred = false;
-    QPSK_HIP_TRY(h->e_front[h->dbuf].wait(h->s_back));
-    return issue_back(h, h->dcall, h->dlen, h->dbuf, h->dkt, nullptr);
+    h->pipe.deferred = false;
+    QPSK_HIP_TRY(h->pipe.e_front[h->pipe.dbuf].wait(h->s_back));
+    return issue_back(h, h->pipe.dcall, h->pipe.dlen, h->pipe.dbuf, h->pipe.dkt, nullptr);
 }
 
 // QPSK_STATUS_* raised by the host-memory call that just finished -> status
@@ -1114,7 +780,7 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
     const int64_t N = h->n_max;
     int rc;
     QPSK_HIP_TRY(hipSetDevice(h->p.device));
-    if ((rc = dev(h->d_acc.alloc(2 * static_cast<size_t>(S))))) return rc;
+    if ((rc = alloc_status(h->d_acc.alloc(2 * static_cast<size_t>(S))))) return rc;
     const bool host = c.mem == QPSK_MEM_HOST;   // synchronous calls only: pipelined ones take device memory
     const int64_t bytes_row = (2 * c.max_sym + 7) / 8;
     uint8_t *dbits = c.bits;
@@ -1123,13 +789,13 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
     int64_t dsyms_stride = c.syms_stride_floats;
     if (host) {
         if (c.bits) {
-            if ((rc = dev(h->d_xbits.grow(static_cast<size_t>(S) * bytes_row)))) return rc;
+            if ((rc = alloc_status(h->d_xbits.grow(static_cast<size_t>(S) * bytes_row)))) return rc;
             dbits = h->d_xbits;
             dbits_stride = bytes_row;
         }
         if (c.syms) {
             const size_t need = static_cast<size_t>(S) * 2 * c.max_sym * sizeof(float);
-            if ((rc = dev(h->d_xsyms.grow(need)))) return rc;
+            if ((rc = alloc_status(h->d_xsyms.grow(need)))) return rc;
             dsyms = h->d_xsyms;
             dsyms_stride = 2 * c.max_sym;
         }
@@ -1140,7 +806,7 @@ int process_chunked(qpsk_demod *h, const Call &c, bool async) {
     for (int64_t k = 0; k < K; ++k) {
         const int64_t off = k * N;
         Call sub = c;
-        sub.iq = static_cast<const char *>(c.iq) + 2 * off * static_cast<int64_t>(elem_bytes(c.fmt));
+        sub.iq = static_cast<const char *>(c.iq) + 2 * off * static_cast<int64_t>(fmt_elem_bytes(c.fmt));
         if (c.lengths) {
             int64_t m = 0;
             for (int s = 0; s < S; ++s) {
@@ -1234,7 +900,7 @@ int qpsk_demod_process_async(qpsk_demod *h, int32_t mode, const float *iq, int64
 int qpsk_demod_set_input_scale(qpsk_demod *h, int32_t fmt, float scale) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     if (!fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
-    if (fmt == kFmtCf32) return fail(QPSK_ERR_ARGUMENT, "CF32 input has no scale");
+    if (fmt == QPSK_FMT_CF32) return fail(QPSK_ERR_ARGUMENT, "CF32 input has no scale");
     if (!std::isfinite(scale) || !(scale > 0.0f))
         return fail(QPSK_ERR_OUT_OF_RANGE, std::string("the ") + fmt_name(fmt) + " scale must be finite and > 0");
     h->in_scale[fmt] = scale;   // calls issued from now on; queued ones carry their own
@@ -1244,19 +910,21 @@ int qpsk_demod_set_input_scale(qpsk_demod *h, int32_t fmt, float scale) {
 int qpsk_demod_get_input_scale(const qpsk_demod *h, int32_t fmt, float *scale) {
     if (!h || !scale) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     if (!fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
-    if (fmt == kFmtCf32) return fail(QPSK_ERR_ARGUMENT, "CF32 input has no scale");
+    if (fmt == QPSK_FMT_CF32) return fail(QPSK_ERR_ARGUMENT, "CF32 input has no scale");
     *scale = h->in_scale[fmt];
     return QPSK_OK;
 }
 
-int qpsk_demod_set_cs16_scale(qpsk_demod *h, float scale) { return qpsk_demod_set_input_scale(h, kFmtCs16, scale); }
+int qpsk_demod_set_cs16_scale(qpsk_demod *h, float scale) {
+    return qpsk_demod_set_input_scale(h, QPSK_FMT_CS16, scale);
+}
 
 int qpsk_demod_get_cs16_scale(const qpsk_demod *h, float *scale) {
-    return qpsk_demod_get_input_scale(h, kFmtCs16, scale);
+    return qpsk_demod_get_input_scale(h, QPSK_FMT_CS16, scale);
 }
 
 int qpsk_fmt_sample_bytes(int32_t fmt) {
-    return fmt_known(fmt) ? static_cast<int>(2 * elem_bytes(fmt)) : QPSK_ERR_ARGUMENT;
+    return fmt_known(fmt) ? static_cast<int>(2 * fmt_elem_bytes(fmt)) : QPSK_ERR_ARGUMENT;
 }
 
 int qpsk_demod_process_fmt(qpsk_demod *h, int32_t fmt, int32_t mode, const void *iq, int64_t stride_elems,
@@ -1282,7 +950,7 @@ int qpsk_demod_process_cs16(qpsk_demod *h, int32_t mode, const int16_t *iq, int6
                             int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
                             int64_t syms_stride_floats, int64_t *n_syms) {
     Call c{{mode, iq, stride_i16, n_samples, lengths, mem, bits, bits_stride_bytes, n_bits, syms,
-            syms_stride_floats, n_syms, kFmtCs16}};
+            syms_stride_floats, n_syms, QPSK_FMT_CS16}};
     return submit(h, c, false);
 }
 
@@ -1291,7 +959,7 @@ int qpsk_demod_process_async_cs16(qpsk_demod *h, int32_t mode, const int16_t *iq
                                   int64_t bits_stride_bytes, int64_t *n_bits, float *syms,
                                   int64_t syms_stride_floats, int64_t *n_syms) {
     Call c{{mode, iq, stride_i16, n_samples, lengths, QPSK_MEM_DEVICE, bits, bits_stride_bytes, n_bits, syms,
-            syms_stride_floats, n_syms, kFmtCs16}};
+            syms_stride_floats, n_syms, QPSK_FMT_CS16}};
     return submit(h, c, true);
 }
 
@@ -1320,51 +988,6 @@ int qpsk_demod_status(qpsk_demod *h, uint32_t *flags) {
     return QPSK_OK;
 }
 
-int qpsk_link_stats_size(void) { return static_cast<int>(sizeof(qpsk_link_stats)); }
-
-int qpsk_demod_enable_link_stats(qpsk_demod *h, int32_t on) {
-    if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    int rc;
-    if ((rc = handle_sync(h))) return rc;
-    if (on) {
-        const size_t S = static_cast<size_t>(h->S);
-        if ((rc = dev(h->d_link.alloc(S))) || (rc = dev(h->d_link_rows.alloc(S)))) return rc;
-        // +0.0, +0.0, 0; on the handle's stream, which every later call and
-        // read is ordered behind (a null-stream memset is not: the handle's
-        // streams do not synchronise with it)
-        QPSK_HIP_TRY(hipMemsetAsync(h->d_link, 0, S * sizeof(LinkAcc), h->stream));
-    }
-    h->link_on = on != 0;
-    return QPSK_OK;
-}
-
-int qpsk_demod_link_stats(qpsk_demod *h, qpsk_link_stats *out, int32_t mem, int32_t reset) {
-    if (!h || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
-    if (mem == QPSK_MEM_DEVICE && (reinterpret_cast<uintptr_t>(out) & 7))
-        return fail(QPSK_ERR_ARGUMENT, "device link-statistics rows must be 8-byte aligned");
-    if (!h->link_on) return fail(QPSK_ERR_STATE, "link statistics are not enabled (qpsk_demod_enable_link_stats)");
-    int rc;
-    // every queued call has run: the loop kernels of pipelined calls add to the
-    // sums on the back stream, the gather reads them on the handle's
-    if ((rc = handle_sync(h))) return rc;
-    LinkGatherArgs ga{};
-    ga.state = h->d_state;
-    ga.acc = h->d_link;
-    ga.out = mem == QPSK_MEM_HOST ? h->d_link_rows : out;
-    ga.S = h->S;
-    ga.fll = h->p.enable_fll ? 1 : 0;
-    ga.reset = reset ? 1 : 0;
-    launch_link_gather(ga, h->stream);
-    QPSK_HIP_TRY(hipGetLastError());
-    if (mem == QPSK_MEM_HOST) {
-        QPSK_HIP_TRY(hipMemcpyAsync(out, h->d_link_rows, static_cast<size_t>(h->S) * sizeof(qpsk_link_stats),
-                                    hipMemcpyDeviceToHost, h->stream));
-        QPSK_HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return QPSK_OK;
-}
-
 int qpsk_demod_pipeline_wait(qpsk_demod *h, void *hip_stream) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     int rc;
@@ -1379,19 +1002,19 @@ int qpsk_demod_pipeline_wait(qpsk_demod *h, void *hip_stream) {
 int qpsk_demod_gate_timeouts(qpsk_demod *h, uint64_t *count) {
     if (!h || !count) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     *count = 0;
-    if (!h->d_gate) return QPSK_OK;
+    if (!h->pipe.d_gate) return QPSK_OK;
     int rc;
     if ((rc = drain_async(h))) return rc;
     QPSK_HIP_TRY(hipSetDevice(h->p.device));
     unsigned v = 0;
-    QPSK_HIP_TRY(hipMemcpy(&v, h->d_gate, sizeof(unsigned), hipMemcpyDeviceToHost));
+    QPSK_HIP_TRY(hipMemcpy(&v, h->pipe.d_gate, sizeof(unsigned), hipMemcpyDeviceToHost));
     *count = v;
     return QPSK_OK;
 }
 
 int qpsk_demod_pipeline_depth(const qpsk_demod *h) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    return h->pipe_ready ? h->pipe_bufs : 0;
+    return h->pipe.ready ? h->pipe.bufs : 0;
 }
 
 int qpsk_demod_rrc_taps(const qpsk_demod *h, float *taps, int32_t cap) {
@@ -1419,84 +1042,6 @@ int qpsk_demod_fll_taps(const qpsk_demod *h, float *lower_iq, float *upper_iq, i
     std::memcpy(lower_iq, h->d.fll_lower_iq.data(), n * sizeof(float));
     std::memcpy(upper_iq, h->d.fll_upper_iq.data(), n * sizeof(float));
     return n;
-}
-
-int qpsk_demod_design(const qpsk_demod_params *p, float *rrc_taps, int32_t cap, double *gains,
-                      float *fll_lower_iq, float *fll_upper_iq) {
-    if (!p) return fail(QPSK_ERR_ARGUMENT_NULL, "null params");
-    LoopDesign d;
-    std::string err;
-    int rc = design_loops(p->sample_rate, p->symbol_rate, p->rrc_alpha, p->rrc_span,
-                          p->symbol_sync_bandwidth, p->costas_loop_bandwidth, p->cfo_loop_bandwidth,
-                          &d, &err);
-    if (rc != QPSK_OK) return fail(rc, err);
-    const int T = static_cast<int>(d.rrc_f32.size());
-    if (rrc_taps) {
-        if (cap < T) return fail(QPSK_ERR_ARGUMENT, "cap too small");
-        std::memcpy(rrc_taps, d.rrc_f32.data(), T * sizeof(float));
-    }
-    if (gains) {
-        gains[0] = d.mm_sps; gains[1] = d.kp; gains[2] = d.ki;
-        gains[3] = d.costas_alpha; gains[4] = d.costas_beta;
-    }
-    if (fll_lower_iq) std::memcpy(fll_lower_iq, d.fll_lower_iq.data(), 2 * kFllTaps * sizeof(float));
-    if (fll_upper_iq) std::memcpy(fll_upper_iq, d.fll_upper_iq.data(), 2 * kFllTaps * sizeof(float));
-    return T;
-}
-
-// State blob (qpsk_state_blob.h): set_state rejects, before it touches the
-// handle, any blob whose length or header does not match this handle or whose
-// records hold a value a kernel would misuse as an address
-// (qpsk_state_blob_check, qpsk_state_blob.cpp).
-int64_t qpsk_demod_state_bytes(const qpsk_demod *h) {
-    if (!h) return 0;
-    return state_blob_bytes(h->S, h->T);
-}
-
-// The four sections of a blob behind its header, in the blob's order, each
-// against the array of the handle that holds it (handle_rows).
-static int copy_state(qpsk_demod *h, char *blob, hipMemcpyKind kind) {
-    const StreamRows v = handle_rows(h);
-    void *const rows[kStateSections] = {v.state, v.carry, v.hist, v.fll_delay};
-    int64_t words[kStateSections];
-    state_row_words(v.T, words);
-    char *p = blob + sizeof(StateHeader);
-    for (int k = 0; k < kStateSections; ++k) {
-        const size_t n = static_cast<size_t>(v.S) * 8 * words[k];
-        const bool out = kind == hipMemcpyDeviceToHost;
-        if (n) QPSK_HIP_TRY(hipMemcpy(out ? p : rows[k], out ? rows[k] : p, n, kind));
-        p += n;
-    }
-    return QPSK_OK;
-}
-
-int qpsk_demod_get_state(qpsk_demod *h, void *host_buf, int64_t buf_bytes) {
-    if (!h || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    if (buf_bytes < qpsk_demod_state_bytes(h)) return fail(QPSK_ERR_ARGUMENT, "state buffer too small");
-    int rc;
-    if ((rc = handle_sync(h))) return rc;
-    const StateHeader hd = state_header(h->S, h->T);
-    std::memcpy(host_buf, &hd, sizeof(hd));
-    return copy_state(h, static_cast<char *>(host_buf), hipMemcpyDeviceToHost);
-}
-
-int qpsk_demod_set_state(qpsk_demod *h, const void *host_buf, int64_t buf_bytes) {
-    if (!h || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    int rc;
-    // on the host, before the handle is waited for or a byte is copied: a
-    // rejected blob leaves the handle as it was
-    if ((rc = qpsk_state_blob_check(&h->p, h->S, host_buf, buf_bytes))) return rc;
-    if ((rc = handle_sync(h))) return rc;
-    return copy_state(h, static_cast<char *>(const_cast<void *>(host_buf)), hipMemcpyHostToDevice);
-}
-
-int qpsk_demod_loop_shape(int32_t requested, int32_t n_streams, double sps, int32_t cus, int32_t rrc_taps,
-                          int32_t costas_trig, int32_t want_syms, qpsk_loop_shape *out) {
-    if (!out) return fail(QPSK_ERR_ARGUMENT_NULL, "out is NULL");
-    if (requested < 0 || requested > 7 || n_streams <= 0 || !(sps > 0.0) || costas_trig < 0 || costas_trig > 1)
-        return fail(QPSK_ERR_ARGUMENT, "loop shape arguments");
-    loop_shape_info(requested, n_streams, sps, cus, rrc_taps, costas_trig, want_syms, out);
-    return QPSK_OK;
 }
 
 // Residency gate default (process_async_one).  The wait is bounded

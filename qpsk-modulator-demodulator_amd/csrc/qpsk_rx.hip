@@ -42,9 +42,7 @@
 #include <string>
 #include <vector>
 
-#include "qpsk_demod.h"
-#include "qpsk_device.h"
-#include "qpsk_internal.h"
+#include "qpsk_handle.h"
 
 namespace {
 using qpsk::fail;
@@ -141,18 +139,17 @@ void copy_bits(const qpsk_rx *r, const Slot &sl, uint8_t *bits, int64_t bits_str
 int create(qpsk_demod *h, int32_t depth, int32_t fmt, qpsk_rx **out) {
     if (!h || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     *out = nullptr;
-    const int sample_bytes = qpsk_fmt_sample_bytes(fmt);
-    if (sample_bytes < 0) return fail(QPSK_ERR_ARGUMENT, kUnknownFormat);
+    if (!qpsk::fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, kUnknownFormat);
     if (depth < 2 || depth > 8) return fail(QPSK_ERR_ARGUMENT, "depth must be 2..8");
     qpsk_rx *r = new qpsk_rx;
     r->h = h;
     r->depth = depth;
-    r->S = qpsk::handle_streams(h);
-    r->n_max = qpsk::handle_max_samples(h);
-    r->device = qpsk::handle_device(h);
+    r->S = h->S;
+    r->n_max = h->n_max;
+    r->device = h->p.device;
     r->in_stride = 2 * r->n_max;
     r->fmt = fmt;
-    r->elem = static_cast<size_t>(sample_bytes) / 2;
+    r->elem = static_cast<size_t>(qpsk::fmt_elem_bytes(fmt));
     r->dev_stride = r->elem == 1 ? 2 * ((r->n_max + 7) / 8 * 8) : r->in_stride;
     r->bits_stride = ((2 * qpsk_demod_max_symbols(h, r->n_max) + 7) / 8 + 15) / 16 * 16;
     int rc = setup(r);
@@ -175,7 +172,7 @@ int wrong_format(int32_t ring_fmt, int32_t fmt) {
 
 int next_slot(qpsk_rx *r, int32_t fmt, void **iq, int64_t *stride_floats) {
     if (!r || !iq) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    if (qpsk_fmt_sample_bytes(fmt) < 0) return fail(QPSK_ERR_ARGUMENT, kUnknownFormat);
+    if (!qpsk::fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, kUnknownFormat);
     if (r->fmt != fmt) return wrong_format(r->fmt, fmt);
     if (r->submitted - r->collected >= r->depth)
         return fail(QPSK_ERR_STATE, "every ring slot holds an uncollected chunk");
@@ -190,7 +187,7 @@ int next_slot(qpsk_rx *r, int32_t fmt, void **iq, int64_t *stride_floats) {
 int submit(qpsk_rx *r, int32_t fmt, const void *iq, int64_t stride_floats, int64_t n_samples,
            const int64_t *lengths, int64_t *ticket) {
     if (!r) return fail(QPSK_ERR_ARGUMENT_NULL, "null ring");
-    if (qpsk_fmt_sample_bytes(fmt) < 0) return fail(QPSK_ERR_ARGUMENT, kUnknownFormat);
+    if (!qpsk::fmt_known(fmt)) return fail(QPSK_ERR_ARGUMENT, kUnknownFormat);
     if (r->fmt != fmt) return wrong_format(r->fmt, fmt);
     if (r->submitted - r->collected >= r->depth)
         return fail(QPSK_ERR_STATE, "every ring slot holds an uncollected chunk");
@@ -229,7 +226,7 @@ int submit(qpsk_rx *r, int32_t fmt, const void *iq, int64_t stride_floats, int64
     rc = qpsk_demod_process_async_fmt(r->h, fmt, QPSK_MODE_DEMODULATE, sl.d_in, r->dev_stride, n_samples, lengths,
                                       sl.d_bits, r->bits_stride, sl.d_nb, nullptr, 0, nullptr);
     if (rc != QPSK_OK) return rc;
-    QPSK_HIP_TRY(sl.in_free.record(qpsk::pipe_front_stream(r->h)));
+    QPSK_HIP_TRY(sl.in_free.record(r->h->s_front));   // "input consumed": behind the front stage
     if ((rc = qpsk_demod_pipeline_wait(r->h, r->down)) != QPSK_OK) return rc;
     sl.row_bytes = (2 * qpsk_demod_max_symbols(r->h, n_call) + 7) / 8;
     if (Framed *f = r->fr.get()) {

@@ -1,5 +1,7 @@
-// qpsk_stream_state.hip -- reset, read and write the state of selected streams
-// of a batch (include/qpsk_demod.h "Selected streams").
+// qpsk_stream_state.hip -- read and write a handle's state: the whole batch as
+// one blob (qpsk_demod_get_state / _set_state, qpsk_state_blob.h), and reset,
+// read and write the state of selected streams of it (include/qpsk_demod.h
+// "Selected streams").
 //
 // A reference receiver is constructed and dropped on its own
 // (QPSKDeModulator.cs:11-56).  A handle's rows are made together; these calls
@@ -27,9 +29,7 @@
 #include <cstring>
 #include <string>
 
-#include "qpsk_demod.h"
-#include "qpsk_internal.h"
-#include "qpsk_kernels.h"
+#include "qpsk_handle.h"
 #include "qpsk_state_blob.h"
 
 using namespace qpsk;
@@ -43,6 +43,20 @@ static_assert(sizeof(LinkAcc) % 8 == 0, "the link sums are cleared in 8-byte wor
 static_assert(sizeof(StateHeader) % 8 == 0, "the staged sections start on 8-byte words");
 
 enum RowsMode { kGather = 0, kScatter = 1, kReset = 2 };
+
+// The four per-stream arrays behind a blob's header, in the blob's order:
+// records, M&M carries, FIR histories (the current one of the ping-pong pair,
+// good until the next call is issued) and FLL delay lines, with the 8-byte
+// words of one stream's row in each.
+struct Sections {
+    void *rows[kStateSections];
+    int64_t words[kStateSections];
+};
+Sections sections(qpsk_demod *h) {
+    Sections t{{h->d_state.get(), h->d_carry.get(), h->d_hist[h->hist_cur].get(), h->d_fll_delay.get()}, {}};
+    state_row_words(h->T, t.words);
+    return t;
+}
 
 struct RowsArgs {
     uint2 *rows[kStateSections];        // the handle's arrays: records, carries, histories, delay lines
@@ -85,34 +99,28 @@ __global__ __launch_bounds__(kRowsThreads) void stream_rows_kernel(const RowsArg
 int move_rows(qpsk_demod *h, int mode, const int32_t *streams, int32_t n, void *host, int64_t bytes) {
     int rc;
     if ((rc = handle_sync(h))) return rc;   // also makes the handle's device current
-    const StreamRows v = handle_rows(h);
+    const Sections sec = sections(h);
     const size_t blob = mode == kReset ? 0 : static_cast<size_t>(bytes);
     const size_t list_bytes = static_cast<size_t>(n) * sizeof(int32_t);
     // what the staging buffer held is dropped: every user of it has returned
-    const hipError_t e = v.staging->grow(blob + list_bytes);
-    if (e != hipSuccess) return fail(QPSK_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    char *stage = *v.staging;
+    if ((rc = alloc_status(h->d_rows.grow(blob + list_bytes)))) return rc;
+    char *stage = h->d_rows;
 
     RowsArgs a{};
-    a.rows[0] = reinterpret_cast<uint2 *>(v.state);
-    a.rows[1] = reinterpret_cast<uint2 *>(v.carry);
-    a.rows[2] = reinterpret_cast<uint2 *>(v.hist);
-    a.rows[3] = reinterpret_cast<uint2 *>(v.fll_delay);
-    state_row_words(v.T, a.words);
     int64_t at = sizeof(StateHeader) / 8;
     for (int k = 0; k < kStateSections; ++k) {
+        a.rows[k] = static_cast<uint2 *>(sec.rows[k]);
+        a.words[k] = sec.words[k];
         a.staged[k] = at;
         at += a.words[k] * n;
     }
     a.staging = reinterpret_cast<uint2 *>(stage);
     a.list = reinterpret_cast<const int32_t *>(stage + blob);   // blob bytes are a multiple of 8
-    a.link = reinterpret_cast<uint2 *>(v.link);
-    StreamState fresh;
-    std::memset(&fresh, 0, sizeof(fresh));   // zero delay lines and loops (FIRFilter.cs:50-51),
-    fresh.base = 1;                          // M&M baseIndex = 1 (MuellerMuller.cs:44)
+    a.link = reinterpret_cast<uint2 *>(h->link.d_link.get());   // nullptr until first enabled
+    const StreamState fresh = fresh_stream_state();
     std::memcpy(a.fresh, &fresh, sizeof(fresh));
 
-    hipStream_t st = v.stream;
+    hipStream_t st = h->stream;
     QPSK_HIP_TRY(hipMemcpyAsync(stage + blob, streams, list_bytes, hipMemcpyHostToDevice, st));
     if (mode == kScatter) QPSK_HIP_TRY(hipMemcpyAsync(stage, host, blob, hipMemcpyHostToDevice, st));
     const dim3 grid(static_cast<unsigned>(n)), block(kRowsThreads);
@@ -123,8 +131,22 @@ int move_rows(qpsk_demod *h, int mode, const int32_t *streams, int32_t n, void *
     if (mode == kGather) QPSK_HIP_TRY(hipMemcpyAsync(host, stage, blob, hipMemcpyDeviceToHost, st));
     QPSK_HIP_TRY(hipStreamSynchronize(st));
     if (mode == kGather) {
-        const StateHeader hd = state_header(n, v.T);
+        const StateHeader hd = state_header(n, h->T);
         std::memcpy(host, &hd, sizeof(hd));
+    }
+    return QPSK_OK;
+}
+
+// The four sections of a whole-batch blob behind its header, each against the
+// array of the handle that holds it.
+int copy_state(qpsk_demod *h, char *blob, hipMemcpyKind kind) {
+    const Sections sec = sections(h);
+    char *p = blob + sizeof(StateHeader);
+    for (int k = 0; k < kStateSections; ++k) {
+        const size_t n = static_cast<size_t>(h->S) * 8 * sec.words[k];
+        const bool out = kind == hipMemcpyDeviceToHost;
+        if (n) QPSK_HIP_TRY(hipMemcpy(out ? p : sec.rows[k], out ? sec.rows[k] : p, n, kind));
+        p += n;
     }
     return QPSK_OK;
 }
@@ -133,25 +155,54 @@ int move_rows(qpsk_demod *h, int mode, const int32_t *streams, int32_t n, void *
 
 extern "C" {
 
+// State blob (qpsk_state_blob.h): set_state rejects, before it touches the
+// handle, any blob whose length or header does not match this handle or whose
+// records hold a value a kernel would misuse as an address
+// (qpsk_state_blob_check, qpsk_state_blob.cpp).
+int64_t qpsk_demod_state_bytes(const qpsk_demod *h) {
+    if (!h) return 0;
+    return state_blob_bytes(h->S, h->T);
+}
+
+int qpsk_demod_get_state(qpsk_demod *h, void *host_buf, int64_t buf_bytes) {
+    if (!h || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    if (buf_bytes < qpsk_demod_state_bytes(h)) return fail(QPSK_ERR_ARGUMENT, "state buffer too small");
+    int rc;
+    if ((rc = handle_sync(h))) return rc;
+    const StateHeader hd = state_header(h->S, h->T);
+    std::memcpy(host_buf, &hd, sizeof(hd));
+    return copy_state(h, static_cast<char *>(host_buf), hipMemcpyDeviceToHost);
+}
+
+int qpsk_demod_set_state(qpsk_demod *h, const void *host_buf, int64_t buf_bytes) {
+    if (!h || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
+    int rc;
+    // on the host, before the handle is waited for or a byte is copied: a
+    // rejected blob leaves the handle as it was
+    if ((rc = qpsk_state_blob_check(&h->p, h->S, host_buf, buf_bytes))) return rc;
+    if ((rc = handle_sync(h))) return rc;
+    return copy_state(h, static_cast<char *>(const_cast<void *>(host_buf)), hipMemcpyHostToDevice);
+}
+
 int qpsk_demod_reset_streams(qpsk_demod *h, const int32_t *streams, int32_t n) {
     if (!h) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     if (n == 0) return QPSK_OK;
     int rc;
-    if ((rc = stream_list_check(handle_streams(h), streams, n))) return rc;
+    if ((rc = stream_list_check(h->S, streams, n))) return rc;
     return move_rows(h, kReset, streams, n, nullptr, 0);
 }
 
 int64_t qpsk_demod_streams_state_bytes(const qpsk_demod *h, int32_t n) {
-    if (!h || n < 1 || n > handle_streams(h)) return 0;
-    return state_blob_bytes(n, handle_taps(h));
+    if (!h || n < 1 || n > h->S) return 0;
+    return state_blob_bytes(n, h->T);
 }
 
 int qpsk_demod_get_streams_state(qpsk_demod *h, const int32_t *streams, int32_t n, void *host_buf,
                                  int64_t buf_bytes) {
     if (!h || !streams || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     int rc;
-    if ((rc = stream_list_check(handle_streams(h), streams, n))) return rc;
-    const int64_t want = state_blob_bytes(n, handle_taps(h));
+    if ((rc = stream_list_check(h->S, streams, n))) return rc;
+    const int64_t want = state_blob_bytes(n, h->T);
     if (buf_bytes != want)
         return fail(QPSK_ERR_ARGUMENT, "the state buffer holds " + std::to_string(buf_bytes) + " bytes, " +
                                            std::to_string(n) + " streams take " + std::to_string(want));
@@ -163,8 +214,8 @@ int qpsk_demod_set_streams_state(qpsk_demod *h, const int32_t *streams, int32_t 
     if (!h || !streams || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     int rc;
     // on the host, before the handle is waited for or a byte is copied
-    if ((rc = stream_list_check(handle_streams(h), streams, n)) ||
-        (rc = qpsk_state_blob_check(handle_rows(h).p, n, host_buf, buf_bytes)))
+    if ((rc = stream_list_check(h->S, streams, n)) ||
+        (rc = qpsk_state_blob_check(&h->p, n, host_buf, buf_bytes)))
         return rc;
     return move_rows(h, kScatter, streams, n, const_cast<void *>(host_buf), buf_bytes);
 }

@@ -400,7 +400,8 @@ def out_rows(S, ms, layout):
     return bits, sy
 
 
-def async_run(iq, calls, sps, span, sync_every=0, layout=None, prepare=None, finish=None, want_syms=True, **knobs):
+def async_run(iq, calls, sps, span, sync_every=0, layout=None, prepare=None, finish=None, want_syms=True,
+              max_samples=None, close_unwaited=False, **knobs):
     """The float call sequence through process_device_async on a torch stream of
     its own (front stage of call k+1 overlapping the back stage of call k),
     every call's outputs in their own device rows, one pipeline_wait at the
@@ -409,11 +410,14 @@ def async_run(iq, calls, sps, span, sync_every=0, layout=None, prepare=None, fin
     them), or out_rows' layouts.  prepare(b) runs on the new handle before the
     first call (a state to restore), finish(b) after the wait, before the
     handle is closed.  want_syms=False passes no symbol rows (the bits-only
-    kernel); the rows then carry None for symbols.  Returns the decoded rows and pipeline_depth."""
+    kernel); the rows then carry None for symbols.  max_samples: the internal
+    chunk size (default the longest call + 8).  close_unwaited: the handle is
+    closed with the calls still queued, no pipeline_wait, and the rows are read
+    after that (finish does not run).  Returns the decoded rows and pipeline_depth."""
     import torch
     S = iq.shape[0]
     nmax = max(max(c) for c in calls)
-    b = make(S, sps, span, nmax + 8, **knobs)
+    b = make(S, sps, span, max_samples or nmax + 8, **knobs)
     if prepare:
         prepare(b)
     stream = torch.cuda.Stream()
@@ -443,12 +447,15 @@ def async_run(iq, calls, sps, span, sync_every=0, layout=None, prepare=None, fin
             outs.append((xd, bits, nb, sy, ns))
             pos += np.array(lens)
     depth = b.pipeline_depth()
-    b.pipeline_wait()
+    if close_unwaited:
+        b.close()
+    else:
+        b.pipeline_wait()
     torch.cuda.synchronize()
     res = [decoded(DEMODULATE, bits.cpu().numpy(), nb.cpu().numpy(), sy.cpu().numpy() if want_syms else None,
                    ns.cpu().numpy())
            for _, bits, nb, sy, ns in outs]
-    if finish:
+    if finish and not close_unwaited:
         finish(b)
     b.close()
     return res, depth
