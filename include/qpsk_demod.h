@@ -1203,6 +1203,156 @@ int qpsk_channel_state_check(const qpsk_channel_params *p, int32_t n_streams, co
 #define QPSK_CHANNEL_TILE_STREAMS 16
 #define QPSK_CHANNEL_BLOCK_SAMPLES 64
 
+/* ---------------------------------------------------------------------------
+ * The propagation path on the device: multipath taps and a sample-clock
+ * offset, batched.  (Added within ABI version 3: no existing entry point,
+ * kernel or layout changed.)
+ *
+ * What the channel above leaves out.  The test bench chain is modulator ->
+ * path -> channel -> demodulator, every hop on rows of any QPSK_FMT_*.  One
+ * call takes n_in samples a stream, passes them through the stream's
+ * multipath taps, resamples the result onto the receiver's sample clock and
+ * writes the samples that are now computable; it reports how many that was
+ * for each stream.  Nothing contracts to an FMA.
+ *
+ * Clock.  Stream g = first_stream + row draws u1, u2, the first and second
+ * draws of splitmix64 seeded with clock_seed + g, u = (z >> 11) * 2^-53 (as
+ * the channel's oscillators draw):
+ *   ppm = clock_ppm + (clock_spread > 0 ? (u1 * 2 - 1) * clock_spread : 0)
+ *   r   = 1.0 + ppm * 1e-6        input samples per output sample; ppm > 0 is
+ *                                 a slow receiver clock.  Constant: no drift.
+ *   tau = tau_random ? u2 : tau0  the position of output 0, in [0, 1)
+ *
+ * Multipath.  A stream has L complex float taps h[0..L-1], 1 <= L <= 8.  With
+ * x[i] the widened input sample at the stream's absolute index i and x[i] = +0
+ * for i < 0, all float, one rounding an operation:
+ *   z[i].re = acc, acc = +0.0f, then for j = 0 .. L-1 in order
+ *             acc = acc + (h[j].re * x[i-j].re - h[j].im * x[i-j].im)
+ *   z[i].im   likewise with (h[j].re * x[i-j].im + h[j].im * x[i-j].re)
+ * multipath = 0: L = 1, h = [(1, 0)].  multipath = 1: the project's four taps
+ * [1, .25 e^{j.7}, .1 e^{-j1.9}, .05] (qpsk_synth_generate's), formed in double
+ * and rounded to float once.
+ *
+ * Resampler.  Output k, the stream's absolute output index from 0, sits at
+ *   p_k = tau + (double)k * r     (two double roundings, closed form: the
+ *                                 result does not depend on how calls cut the
+ *                                 stream)
+ *   n = floor(p_k) as int64, mu = p_k - (double)n, t = (float)mu
+ * and its value is MuellerMuller.CubicLagrange4 (MuellerMuller.cs:160-190) on
+ * z[n-1], z[n], z[n+1], z[n+2], in float, I and Q separately:
+ *   tm1 = t - 1, tm2 = t - 2, tp1 = t + 1
+ *   c_m1 = -(t * tm1 * tm2) * (1f / 6f)     c_0 = (tp1 * tm1 * tm2) * (1f / 2f)
+ *   c_1 = -(tp1 * t * tm2) * (1f / 2f)      c_2 = (tp1 * t * tm1) * (1f / 6f)
+ *   y = c_m1 * z[n-1] + c_0 * z[n] + c_1 * z[n+1] + c_2 * z[n+2], left to right
+ * The position is double at every k: at k = 2^40 the ulp of p_k is 2^-12
+ * sample, which is the resolution of mu there.  Input positions are held to
+ * 2^50 (output positions then stay below 2^51).
+ *
+ * What a call emits.  After a call the stream has taken inputs 0 .. in_end-1;
+ * the call emits every not yet emitted k with floor(p_k) <= in_end - 3 (the
+ * interpolator looks two samples ahead: the first call of N samples at r = 1,
+ * tau = 0 emits N - 2).  There is no flush: append zeros for the tail.
+ * With L = 1, h = (1, 0), r = 1, tau = 0 a finite row comes back bit for bit,
+ * two samples short, except that -0 becomes +0.
+ *
+ * Formats as the channel's: input values as qpsk_demod_process_fmt reads them
+ * (scale_in; CU8 zero at 128), the float result through QPSK_MOD_NORM_FIXED of
+ * qpsk_quantise_iq with scale_out; QPSK_MOD_NORM_PEAK is QPSK_ERR_ARGUMENT.
+ * Not modelled: a time-varying r (clock drift), fractional-delay taps. */
+typedef struct qpsk_path_params {
+    double clock_ppm;           /* sample-clock offset of every stream, ppm: 0            */
+    double clock_spread;        /* + uniform(-spread, spread) per stream, ppm, >= 0: 0    */
+    uint64_t clock_seed;        /* stream g draws from clock_seed + g: 3000               */
+    double tau0;                /* position of output 0 when tau_random = 0, [0, 1): 0    */
+    int32_t tau_random;         /* 1: tau = the stream's second draw                      */
+    int32_t multipath;          /* 0: one unit tap; 1: the project's four taps            */
+    int64_t first_stream;       /* global id of row 0                                     */
+    int32_t device;             /* HIP device ordinal                                     */
+    int32_t reserved[7];
+} qpsk_path_params;
+typedef struct qpsk_path qpsk_path;
+#define QPSK_PATH_MAX_TAPS 8
+#define QPSK_PATH_HIST 16
+#define QPSK_PATH_MAX_PPM 1000.0
+/* The outputs one workgroup of the path kernel covers: the per-call output
+ * counts at which the kernel changes tiles (tests/test_gpu_path.py spans them). */
+#define QPSK_PATH_TILE_OUTPUTS 1024
+/* All 0 but clock_seed = 3000. */
+void qpsk_path_params_init(qpsk_path_params *p);
+/* |clock_ppm| + clock_spread > 1000, clock_spread < 0, tau0 outside [0, 1), any
+ * of them not finite, or first_stream < 0: QPSK_ERR_OUT_OF_RANGE; n_streams < 1:
+ * QPSK_ERR_ARGUMENT; all before a device is touched. */
+int qpsk_path_create(const qpsk_path_params *p, int32_t n_streams, qpsk_path **out);
+int qpsk_path_destroy(qpsk_path *pa);
+/* As qpsk_channel_set_stream. */
+int qpsk_path_set_stream(qpsk_path *pa, void *hip_stream);
+/* Replaces the taps: taps_iq is host memory, [2 * n_taps] floats (re, im) for
+ * all streams or [n_streams][2 * n_taps] when per_stream != 0; n_taps in 1..8,
+ * else QPSK_ERR_ARGUMENT; a non-finite tap is QPSK_ERR_OUT_OF_RANGE.  Takes
+ * effect behind the calls queued so far; the history is kept. */
+int qpsk_path_set_taps(qpsk_path *pa, const float *taps_iq, int32_t n_taps, int32_t per_stream);
+/* One call: stream s takes lengths[s] samples (lengths == NULL: n_samples for
+ * all; host memory, each 0 .. n_samples) from row s of in, [n_streams][stride_in]
+ * elements of fmt_in, and writes n_out[s] samples to row s of out,
+ * [n_streams][stride_out] elements of fmt_out, stride_out >= 2 * out_cap.
+ * n_out is host memory, [n_streams], and is filled before the call returns even
+ * when the device work is only queued: the counts are a function of the call
+ * lengths and each stream's (r, tau) alone, and the handle keeps every stream's
+ * positions on the host.  A stream that would emit more than out_cap samples
+ * makes the call QPSK_ERR_ARGUMENT (qpsk_path_out_bound gives a capacity that
+ * always suffices).  out must not overlap in (the lengths differ: there is no
+ * in-place form; the test is on the two buffers' whole extents, first row to
+ * last), else QPSK_ERR_ARGUMENT.  Device rows, scales, norm_out, mem,
+ * queueing and the return follow qpsk_channel_apply_fmt: a device call without
+ * lengths is queued on the handle's stream and returns; rows 16-byte aligned
+ * with a pitch that is a multiple of 16 bytes are read with 16-byte loads.
+ * Elements past a row's n_out are not written.  A rejected call changes neither
+ * the state nor out.  The caller's current device is the same on return. */
+int qpsk_path_apply_fmt(qpsk_path *pa, int32_t fmt_in, const void *in, int64_t stride_in, float scale_in,
+                        int32_t fmt_out, int32_t norm_out, void *out, int64_t stride_out, int64_t out_cap,
+                        float scale_out, int64_t n_samples, const int64_t *lengths, int64_t *n_out, int32_t mem);
+/* Host only, no device.  The capacity that is enough for any call of n_in
+ * samples on a handle made from p: ceil(n_in / (1 - (|clock_ppm| +
+ * clock_spread) * 1e-6)) + 2; negative (an error code) for bad arguments. */
+int64_t qpsk_path_out_bound(const qpsk_path_params *p, int64_t n_in);
+/* Host only.  How many outputs a stream at (r, tau) that has emitted out_pos
+ * emits once it has taken in_end inputs: the k >= out_pos with floor(p_k) <=
+ * in_end - 3, from a division and a correction by that predicate (no loop over
+ * samples).  Negative (an error code) when r is not within 1000 ppm of 1, tau
+ * not in [0, 1), in_end outside [0, 2^50] or out_pos outside [0, 2^51]. */
+int64_t qpsk_path_count(double r, double tau, int64_t out_pos, int64_t in_end);
+/* State: per stream 256 bytes, no header,
+ *   double r, tau; int64 in_pos, out_pos; int32 n_taps; float taps[8][2];
+ *   float hist[16][2]; 28 reserved bytes (0)
+ * hist holds the widened inputs at indices in_pos-16 .. in_pos-1 (the last
+ * L - 1 + 3 <= 10 samples the next call can still need, rounded up); entries
+ * at negative indices are +0.  qpsk_path_state_size() = 256 and
+ * qpsk_path_state_init (the state qpsk_path_create leaves, buf_bytes = 256 *
+ * n_streams) need no device.  get_state / set_state / reset_streams as the
+ * channel's; set_state runs qpsk_path_state_check first and changes nothing
+ * when it fails; reset_streams gives the listed rows their created (r, tau),
+ * positions 0 and an empty history and keeps their taps. */
+int qpsk_path_state_size(void);
+int qpsk_path_state_init(const qpsk_path_params *p, int32_t n_streams, void *buf, int64_t buf_bytes);
+int qpsk_path_get_state(qpsk_path *pa, void *host_buf, int64_t buf_bytes);
+int qpsk_path_set_state(qpsk_path *pa, const void *host_buf, int64_t buf_bytes);
+int qpsk_path_reset_streams(qpsk_path *pa, const int32_t *streams, int32_t n);
+/* What a state must satisfy (host only): buf_bytes = 256 * n_streams; r finite
+ * and within [1 - 1000e-6, 1 + 1000e-6]; tau in [0, 1); in_pos in [0, 2^50],
+ * out_pos >= 0; out_pos == qpsk_path_count(r, tau, 0, in_pos) (the stream has
+ * emitted everything it could); n_taps in 1..8, taps finite, unused taps +0;
+ * hist entries at negative indices +0 (the others may hold any bits: inputs may
+ * be NaN); reserved bytes 0.  A failure is QPSK_ERR_ARGUMENT and names stream
+ * and field in qpsk_last_error. */
+int qpsk_path_state_check(int32_t n_streams, const void *buf, int64_t buf_bytes);
+/* The same call on host CF32 rows and a state blob, single-threaded, no
+ * device: state is [n_streams] records (checked first, advanced by the call),
+ * in and out float rows with strides in floats, the rest as
+ * qpsk_path_apply_fmt with both formats CF32 and both scales 1. */
+int qpsk_path_apply_host(void *state, int64_t state_bytes, int32_t n_streams, const float *in, int64_t stride_in,
+                         float *out, int64_t stride_out, int64_t out_cap, int64_t n_samples,
+                         const int64_t *lengths, int64_t *n_out);
+
 const char *qpsk_last_error(void);
 int qpsk_abi_version(void);
 

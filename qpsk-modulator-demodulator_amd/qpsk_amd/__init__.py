@@ -176,6 +176,13 @@ class ChannelParams(C.Structure):
                 ("device", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+class PathParams(C.Structure):
+    """qpsk_path_params: the sample-clock offset and the default taps of the propagation path."""
+    _fields_ = [("clock_ppm", C.c_double), ("clock_spread", C.c_double), ("clock_seed", C.c_uint64),
+                ("tau0", C.c_double), ("tau_random", C.c_int32), ("multipath", C.c_int32), ("first_stream", C.c_int64),
+                ("device", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 class LoopShape(C.Structure):
     """qpsk_loop_shape (include/qpsk_demod.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -394,6 +401,27 @@ def lib():
     L.qpsk_channel_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.qpsk_channel_reset_streams.argtypes = [C.c_void_p, _i32p, C.c_int32]
     L.qpsk_channel_state_check.argtypes = [C.POINTER(ChannelParams), C.c_int32, C.c_void_p, C.c_int64]
+    # the propagation path: multipath taps and a sample-clock offset
+    L.qpsk_path_params_init.argtypes = [C.POINTER(PathParams)]
+    L.qpsk_path_params_init.restype = None
+    L.qpsk_path_create.argtypes = [C.POINTER(PathParams), C.c_int32, C.POINTER(C.c_void_p)]
+    L.qpsk_path_destroy.argtypes = [C.c_void_p]
+    L.qpsk_path_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.qpsk_path_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+    L.qpsk_path_apply_fmt.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int64, _i64p, _i64p, C.c_int32]
+    L.qpsk_path_out_bound.argtypes = [C.POINTER(PathParams), C.c_int64]
+    L.qpsk_path_out_bound.restype = C.c_int64
+    L.qpsk_path_count.argtypes = [C.c_double, C.c_double, C.c_int64, C.c_int64]
+    L.qpsk_path_count.restype = C.c_int64
+    L.qpsk_path_state_size.restype = C.c_int
+    L.qpsk_path_state_init.argtypes = [C.POINTER(PathParams), C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_path_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_path_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_path_reset_streams.argtypes = [C.c_void_p, _i32p, C.c_int32]
+    L.qpsk_path_state_check.argtypes = [C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_path_apply_host.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_int64, C.c_int64, _i64p, _i64p]
     _lib = real
     return real
 
@@ -439,6 +467,10 @@ EXPORTED_SYMBOLS = [
     "qpsk_channel_params_init", "qpsk_channel_create", "qpsk_channel_destroy", "qpsk_channel_set_stream",
     "qpsk_channel_apply_fmt", "qpsk_channel_state_size", "qpsk_channel_get_state", "qpsk_channel_set_state",
     "qpsk_channel_reset_streams", "qpsk_channel_state_check",
+    "qpsk_path_params_init", "qpsk_path_create", "qpsk_path_destroy", "qpsk_path_set_stream", "qpsk_path_set_taps",
+    "qpsk_path_apply_fmt", "qpsk_path_out_bound", "qpsk_path_count", "qpsk_path_state_size", "qpsk_path_state_init",
+    "qpsk_path_get_state", "qpsk_path_set_state", "qpsk_path_reset_streams", "qpsk_path_state_check",
+    "qpsk_path_apply_host",
 ]
 
 _EXC = {
@@ -1871,6 +1903,199 @@ class Channel:
     def reset_streams(self, streams):
         a, n = _stream_list(streams)
         _check(lib().qpsk_channel_reset_streams(self._h, a, n))
+
+
+# the 256-byte record of a path stream's state
+PATH_STATE_DTYPE = np.dtype([("r", "f8"), ("tau", "f8"), ("in_pos", "i8"), ("out_pos", "i8"), ("n_taps", "i4"),
+                             ("taps", "f4", (8, 2)), ("hist", "f4", (16, 2)), ("reserved", "u1", (28,))])
+assert PATH_STATE_DTYPE.itemsize == 256
+PATH_TILE_OUTPUTS = 1024      # QPSK_PATH_TILE_OUTPUTS
+PATH_MAX_TAPS = 8             # QPSK_PATH_MAX_TAPS
+PATH_HIST = 16                # QPSK_PATH_HIST
+
+
+def path_state_size() -> int:
+    """qpsk_path_state_size(): 256 (needs no device)."""
+    return int(lib().qpsk_path_state_size())
+
+
+def path_params(clock_ppm=None, clock_spread=None, clock_seed=None, tau0=None, tau_random=None, multipath=None,
+                first_stream=None, device=None) -> PathParams:
+    """qpsk_path_params_init's defaults (no offset, one unit tap) with the given fields replaced."""
+    p = PathParams()
+    lib().qpsk_path_params_init(C.byref(p))
+    for name, v in (("clock_ppm", clock_ppm), ("clock_spread", clock_spread), ("tau0", tau0)):
+        if v is not None:
+            setattr(p, name, float(v))
+    if clock_seed is not None:
+        p.clock_seed = int(clock_seed) & (2 ** 64 - 1)
+    for name, v in (("tau_random", tau_random), ("multipath", multipath), ("first_stream", first_stream),
+                    ("device", device)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def path_count(r: float, tau: float, out_pos: int, in_end: int) -> int:
+    """qpsk_path_count: the outputs k >= out_pos with floor(tau + k r) <= in_end - 3 (needs no device)."""
+    return int(_check(lib().qpsk_path_count(float(r), float(tau), int(out_pos), int(in_end))))
+
+
+def path_out_bound(p: PathParams, n_in: int) -> int:
+    """qpsk_path_out_bound: an output capacity that suffices for any call of n_in samples (needs no device)."""
+    return int(_check(lib().qpsk_path_out_bound(C.byref(p), int(n_in))))
+
+
+def path_state_init(p: PathParams, n_streams: int) -> bytes:
+    """qpsk_path_state_init: the state qpsk_path_create leaves (needs no device)."""
+    buf = C.create_string_buffer(path_state_size() * int(n_streams))
+    _check(lib().qpsk_path_state_init(C.byref(p), int(n_streams), buf, len(buf)))
+    return buf.raw
+
+
+def path_state_check(n_streams: int, blob):
+    """qpsk_path_state_check: raises ValueError naming stream and field when
+    blob is no state of a path of n_streams.  Needs no device."""
+    b = bytes(blob)
+    _check(lib().qpsk_path_state_check(int(n_streams), b, len(b)))
+
+
+def path_apply_host(state, rows: np.ndarray, lengths=None, out: np.ndarray | None = None, out_cap: int | None = None,
+                    n: int | None = None):
+    """qpsk_path_apply_host: one call on host float32 rows [S, 2 n] and a state
+    blob, no device.  Returns (the new state, out rows, n_out); a refused call
+    raises and leaves out as it was."""
+    st = C.create_string_buffer(bytes(state), len(bytes(state)))
+    S = len(st) // path_state_size()
+    if rows.dtype != np.float32 or rows.ndim != 2 or rows.shape[0] != S or (rows.shape[1] > 1 and rows.strides[1] != 4):
+        raise ValueError("rows must be [n_streams, 2 n] float32 with contiguous rows")
+    n = rows.shape[1] // 2 if n is None else int(n)
+    if out is None:
+        cap = n + n // 512 + 4 if out_cap is None else int(out_cap)
+        out = np.zeros((S, max(2 * cap, 2)), np.float32)
+    cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
+    keep, lp = Channel._lengths(lengths, S)
+    n_out = np.zeros(S, np.int64)
+    _check(lib().qpsk_path_apply_host(st, len(st), S, rows.ctypes.data, rows.strides[0] // 4, out.ctypes.data,
+                                      out.strides[0] // 4, cap, n, lp, n_out.ctypes.data_as(_i64p)))
+    return st.raw, out, n_out
+
+
+class Path:
+    """The propagation path on S streams (qpsk_path_*): each stream's multipath
+    taps, then a resampler onto the receiver's sample clock
+    (MuellerMuller.CubicLagrange4 at p_k = tau + k r).  Rows of any format in,
+    rows of any format out, host or device memory; a call emits what its
+    inputs make computable and returns the counts."""
+
+    def __init__(self, n_streams: int, p: PathParams | None = None, **fields):
+        self.p = p if p is not None else path_params(**fields)
+        self.n_streams = int(n_streams)
+        h = C.c_void_p()
+        _check(lib().qpsk_path_create(C.byref(self.p), self.n_streams, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().qpsk_path_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream_ptr: int | None):
+        """Order the handle's calls on a caller's stream (torch's); None goes
+        back to the handle's own."""
+        _check(lib().qpsk_path_set_stream(self._h, C.c_void_p(hip_stream_ptr or 0)))
+        self._bound = bool(hip_stream_ptr)
+
+    def set_taps(self, taps, per_stream=False):
+        """Complex taps [L] for all streams, or [S, L] with per_stream."""
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.complex64))
+        if t.ndim != (2 if per_stream else 1) or (per_stream and t.shape[0] != self.n_streams):
+            raise ValueError("taps must be [L], or [n_streams, L] with per_stream")
+        f = t.view(np.float32)
+        _check(lib().qpsk_path_set_taps(self._h, f.ctypes.data, t.shape[-1], 1 if per_stream else 0))
+
+    def out_bound(self, n_in: int) -> int:
+        return path_out_bound(self.p, n_in)
+
+    def apply(self, rows: np.ndarray, fmt="cf32", out_fmt=None, lengths=None, scale_in=None, scale_out=None,
+              norm="fixed", out: np.ndarray | None = None, n: int | None = None, out_cap: int | None = None):
+        """One host-memory call on rows [S, 2 n] of fmt; returns (rows of
+        out_fmt (default fmt), n_out).  out: rows to write into, [S, >= 2
+        out_cap]; what lies past a row's n_out stays as it was."""
+        tag_in, dt_in, _ = _format(fmt)
+        tag_out, dt_out, _ = _format(fmt if out_fmt is None else out_fmt)
+        if rows.dtype != dt_in or rows.ndim != 2 or rows.shape[0] != self.n_streams or rows.strides[1] != rows.itemsize:
+            raise ValueError(f"rows must be [n_streams, 2 n] of {np.dtype(dt_in).name} with contiguous rows")
+        n = rows.shape[1] // 2 if n is None else int(n)
+        if out is None:
+            out = np.zeros((self.n_streams, max(2 * (self.out_bound(n) if out_cap is None else int(out_cap)), 2)),
+                           dtype=dt_out)
+        if out.dtype != dt_out or out.ndim != 2 or out.shape[0] != self.n_streams or out.strides[1] != out.itemsize:
+            raise ValueError(f"out must be [n_streams, 2 out_cap] of {np.dtype(dt_out).name} with contiguous rows")
+        cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
+        keep, lp = Channel._lengths(lengths, self.n_streams)
+        si, so = Channel._scales(tag_in, tag_out, scale_in, scale_out)
+        n_out = np.zeros(self.n_streams, np.int64)
+        _check(lib().qpsk_path_apply_fmt(self._h, tag_in, rows.ctypes.data, rows.strides[0] // rows.itemsize, si,
+                                         tag_out, _norm(norm), out.ctypes.data, out.strides[0] // out.itemsize, cap, so,
+                                         n, lp, n_out.ctypes.data_as(_i64p), MEM_HOST))
+        return out, n_out
+
+    def apply_device(self, in_dev, n: int, out_dev, fmt="cf32", out_fmt=None, lengths=None, scale_in=None,
+                     scale_out=None, norm="fixed", out_cap: int | None = None) -> np.ndarray:
+        """One device-memory call: in_dev [S, >= 2 n] of fmt, out_dev [S, >= 2
+        out_cap] of out_fmt (out_cap defaults to what out_dev holds).  Returns
+        n_out, a host array, at once.  lengths is a host array.  Ordered on the
+        handle's stream; without set_stream the caller's torch stream is
+        drained first and the call is waited for."""
+        import torch
+        tag_in = _format(fmt)[0]
+        fo = fmt if out_fmt is None else out_fmt
+        tag_out = _format(fo)[0]
+        cap = out_dev.shape[1] // 2 if out_cap is None else int(out_cap)
+        for t, f, need, what in ((in_dev, fmt, 2 * n, "in_dev"), (out_dev, fo, 2 * cap, "out_dev")):
+            if (not t.is_cuda or t.dtype != _torch_dtype(f) or t.dim() != 2 or t.shape[0] != self.n_streams or
+                    (t.shape[1] > 1 and t.stride(1) != 1) or t.shape[1] < need):
+                raise ValueError(f"{what} must be a contiguous-row [n_streams, >= 2 n] device tensor of its format")
+        keep, lp = Channel._lengths(lengths, self.n_streams)
+        si, so = Channel._scales(tag_in, tag_out, scale_in, scale_out)
+        bound = getattr(self, "_bound", False)
+        if not bound:   # the handle's own stream does not order against torch's
+            torch.cuda.current_stream(out_dev.device).synchronize()
+        n_out = np.zeros(self.n_streams, np.int64)
+        _check(lib().qpsk_path_apply_fmt(self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, tag_out,
+                                         _norm(norm), out_dev.data_ptr(), out_dev.stride(0), cap, so, int(n), lp,
+                                         n_out.ctypes.data_as(_i64p), MEM_DEVICE))
+        if not bound:
+            self.sync()
+        return n_out
+
+    def sync(self):
+        """Wait for the calls queued on the handle (reads its state)."""
+        self.get_state()
+
+    def get_state(self) -> bytes:
+        buf = C.create_string_buffer(path_state_size() * self.n_streams)
+        _check(lib().qpsk_path_get_state(self._h, buf, len(buf)))
+        return buf.raw
+
+    def states(self, blob: bytes | None = None) -> np.ndarray:
+        """The state as a PATH_STATE_DTYPE array, one record a stream."""
+        return np.frombuffer(self.get_state() if blob is None else blob, dtype=PATH_STATE_DTYPE).copy()
+
+    def set_state(self, blob):
+        b = bytes(blob)
+        _check(lib().qpsk_path_set_state(self._h, b, len(b)))
+
+    def reset_streams(self, streams):
+        a, n = _stream_list(streams)
+        _check(lib().qpsk_path_reset_streams(self._h, a, n))
 
 
 def _norm(norm):

@@ -20,6 +20,14 @@ The first --skip rounds (acquisition) are reported apart.
 Two sweeps: frame loss against noise_rms at 1 ppm, and against ppm (both LOs)
 with no noise.  Writes one JSON file (--out, default profiles/fer_curve.json).
 The values are recorded as measured; nothing here asserts them.
+
+--clock-ppm adds a third axis (off by default, the two sweeps above are then as
+they were): the propagation path (qpsk_path_apply_fmt) goes between the
+modulator and the channel with every stream's sample clock off by that many
+ppm (tau0 = 0.5, one unit tap, no noise), once beside LOs at 1 ppm and once
+beside LOs off by the same |ppm| as the clock, as one oscillator would have
+them.  A round then hands the demodulator what the path emitted in it.
+profiles/fer_curve_clock.json: --noise-rms "" --ppm "" --clock-ppm -100,...,100.
 """
 from __future__ import annotations
 
@@ -50,7 +58,9 @@ def main():
     ap.add_argument("--noise-rms", default="0,0.05,0.1,0.15,0.2,0.25,0.3,0.4,0.5")
     ap.add_argument("--ppm", default="0,1,2,5,10,20,50,100")
     ap.add_argument("--fmt", default="cf32", choices=["cf32", "cs16", "cs8"])
+    ap.add_argument("--clock-ppm", default="", help="sample-clock offsets, ppm (default: no clock sweep)")
     args = ap.parse_args()
+    clocks = [float(v) for v in args.clock_ppm.split(",") if v]
 
     import torch
     import qpsk_amd as Q
@@ -64,12 +74,15 @@ def main():
     m = Q.QPSKModulator(FS, rs, ALPHA, span, tsc=TSC, device=dev.index)
     n = m.output_floats(8 * (len(START) + P + len(STOP))) // 2
     pitch = (n + 7) // 8 * 8
+    if clocks:   # what the path can emit in a round
+        pitch = (Q.path_out_bound(Q.path_params(clock_ppm=max(abs(c) for c in clocks)), n) + 7) // 8 * 8
     d = Q.BatchDemodulator(S, Q.params(FS, rs, ALPHA, span, device=dev.index, max_samples_per_call=pitch))
     fr = Q.DeviceFramer(S, START, STOP, ring_capacity=1 << 16, device=dev.index)
     for h in (m, d, fr):
         h.set_stream(stream.cuda_stream)
     fresh = d.get_state()
     rows = torch.zeros((S, 2 * pitch), dtype=Q._torch_dtype(args.fmt), device=dev)
+    prop = torch.zeros_like(rows) if clocks else None
     n_out = torch.zeros(S, dtype=torch.int64, device=dev)
     plen = torch.full((S,), P, dtype=torch.int64, device=dev)
     ms = d.max_symbols(pitch)
@@ -83,11 +96,15 @@ def main():
            "payload_bytes": P, "samples_per_frame": n, "frames": args.frames, "skip": args.skip, "lo_hz": 100e6,
            "noise_sweep": [], "ppm_sweep": []}
 
-    def point(ppm, rms):
+    def point(ppm, rms, clock=None):
         d.set_state(fresh)
         fr.reset_streams(range(S))
         ch = Q.Channel(S, sample_rate=float(FS), tx_ppm=ppm, rx_ppm=ppm, noise_rms=rms, noise_seed=11, device=dev.index)
         ch.set_stream(stream.cuda_stream)
+        pa = None
+        if clock is not None:
+            pa = Q.Path(S, clock_ppm=clock, tau0=0.5, device=dev.index)
+            pa.set_stream(stream.cuda_stream)
         gen.manual_seed(1234)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
@@ -95,8 +112,11 @@ def main():
         for _ in range(args.frames):
             sent = torch.randint(0, 256, (S, P), dtype=torch.uint8, device=dev, generator=gen)
             m.modulate_bytes_device(sent, plen, START, STOP, rows, n_out, fmt=args.fmt, scale=full)
-            ch.apply_device(rows, n, fmt=args.fmt)
-            d.process_device_fmt(rows, n, bits, nbits, args.fmt)
+            x, k = rows, n
+            if pa is not None:   # one clock for all streams: they emit alike
+                x, k = prop, int(pa.apply_device(rows, n, prop, fmt=args.fmt, scale_out=full)[0])
+            ch.apply_device(x, k, fmt=args.fmt)
+            d.process_device_fmt(x, k, bits, nbits, args.fmt)
             Q.tsc_find_device(bits, nbits, TSC, offs, stream.cuda_stream)
             fr.push(bits, nbits, pay, npay, offs)
             good.append(((npay == P) & (pay[:, :P] == sent).all(dim=1)).sum())
@@ -104,8 +124,10 @@ def main():
         e1.synchronize()
         good = [int(g) for g in good]
         ch.close()
+        if pa is not None:
+            pa.close()
         after = good[args.skip:]
-        return dict(ppm=ppm, noise_rms=rms, frames_received_per_round=good, frames_sent_after_skip=S * len(after),
+        return dict(**({} if clock is None else {"clock_ppm": clock}), ppm=ppm, noise_rms=rms, frames_received_per_round=good, frames_sent_after_skip=S * len(after),
                     frames_lost_after_skip=S * len(after) - sum(after),
                     frame_loss_after_skip=round(1.0 - sum(after) / (S * len(after)), 6),
                     ms=round(e0.elapsed_time(e1), 1))
@@ -116,14 +138,21 @@ def main():
             json.dump(rec, f, indent=1)
             f.write("\n")
 
-    for rms in (float(v) for v in args.noise_rms.split(",")):
+    for rms in (float(v) for v in args.noise_rms.split(",") if v):
         rec["noise_sweep"].append(point(1.0, rms))
         print(json.dumps(rec["noise_sweep"][-1]), flush=True)
         save()
-    for ppm in (float(v) for v in args.ppm.split(",")):
+    for ppm in (float(v) for v in args.ppm.split(",") if v):
         rec["ppm_sweep"].append(point(ppm, 0.0))
         print(json.dumps(rec["ppm_sweep"][-1]), flush=True)
         save()
+    if clocks:
+        rec["clock_sweep"] = []
+    for clock in clocks:
+        for ppm in (1.0, abs(clock)):
+            rec["clock_sweep"].append(point(ppm, 0.0, clock))
+            print(json.dumps(rec["clock_sweep"][-1]), flush=True)
+            save()
     m.close()
     d.close()
 
