@@ -1353,6 +1353,158 @@ int qpsk_path_apply_host(void *state, int64_t state_bytes, int32_t n_streams, co
                          float *out, int64_t stride_out, int64_t out_cap, int64_t n_samples,
                          const int64_t *lengths, int64_t *n_out);
 
+/* ---------------------------------------------------------------------------
+ * The polyphase channeliser on the device: one wideband row into M streams.
+ * (Added within ABI version 3: no existing entry point, kernel or layout
+ * changed.)
+ *
+ * What stands in front of the demodulator when a radio delivers one wideband
+ * capture and not S baseband rows.  A handle holds n_bands wideband inputs at
+ * rate fs, rows of any QPSK_FMT_*.  Band b yields M = channels output rows:
+ * row b * M + c is the signal around c * fs / M at rate 2 * fs / M (an M-channel
+ * polyphase filter bank oversampled by 2), CF32, ready for
+ * qpsk_demod_process_fmt; channels c >= M / 2 are the negative frequencies.  A
+ * carrier of symbol rate fs / (2 M) comes out at 4 samples a symbol.  Every
+ * operation is float with one rounding; nothing contracts to an FMA.
+ * Let D = M / 2, K = taps_per_branch, L = M * K.
+ *
+ * Prototype taps h[0 .. L-1], real floats.  qpsk_pfb_create designs them on the
+ * host in double with glibc sin / cos (pi = 3.14159265358979323846):
+ *   h[0] = 0
+ *   for n = 1 .. L/2:   t = (double)(n - L/2) / (double)M
+ *                       sinc = t == 0 ? 1 : sin(pi * t) / (pi * t)
+ *                       g[n] = sinc * (0.54 - 0.46 * cos(2.0 * pi * (double)(n - 1) / (double)(L - 2)))
+ *   for n = L/2+1 .. L-1:  g[n] = g[L - n]        (the window is symmetric about
+ *                          L/2: g[n] of this formula at n and L - n, made equal
+ *                          bit for bit)
+ *   sum = g[1] + g[2] + .. + g[L-1], left to right;  h[n] = (float)(g[n] / sum)
+ * L - 1 taps symmetric about n = L/2: the delay is exactly K output samples
+ * (output m carries the band at input time (m - K) * D), the DC gain is 1.
+ * qpsk_pfb_set_taps replaces them.
+ *
+ * Twiddles W[q], q in [0, M/2):  W[q] = ((float)cos(a), (float)sin(a)) with
+ * a = 2.0 * pi * (double)q / (double)M in double; W[0] = (1, +0) and
+ * W[M/4] = (+0, 1) are set explicitly.
+ *
+ * Frame m, the band's absolute frame index from 0.  With x[i] the widened input
+ * at the band's absolute index i and x[i] = +0 for i < 0:
+ *   1. Polyphase sum.  v[p], p in [0, M): acc = (+0, +0); for k = 0 .. K-1 in
+ *      order  acc = acc + h[p + k*M] * x[m*D - p - k*M]  (the taps are real: re
+ *      and im apart, a product rounded, then the sum).
+ *   2. Transform, radix-2 decimation in time.  a[bitrev(p)] = v[p] (bitrev over
+ *      log2 M bits); stages half = 1, 2, .., M/2; in a stage every butterfly at
+ *      j0 (a multiple of 2*half) and j < half takes w = W[j * (M / (2*half))],
+ *      b = a[j0+j+half],
+ *        t = (w.re*b.re - w.im*b.im, w.re*b.im + w.im*b.re)
+ *        a[j0+j+half] = a[j0+j] - t;  a[j0+j] = a[j0+j] + t
+ *      The full multiply is done at every butterfly, also where w is 1 or j:
+ *      that fixes the sign of a zero.
+ *   3. Output.  y_c[m] = a[c], both parts negated when c * m is odd; then each
+ *      part times gain.
+ * This equals the mixer e^{-j 2 pi c i / M} on the absolute input index i, the
+ * lowpass h and a decimation by D; no constant phase is left over.
+ *
+ * What a call emits.  After a call the band has taken inputs 0 .. in_end-1; the
+ * call emits every not yet emitted frame m <= (in_end - 1) / D, so ceil(in_end
+ * / D) frames are out in all.  There is no flush: append zeros for the tail.
+ *
+ * Not built: a subset of the channels, an oversampling other than 2, output
+ * formats other than CF32, a channeliser behind the host-fed ring, a group
+ * form, the synthesis bank. */
+typedef struct qpsk_pfb_params {
+    int32_t channels;           /* M, a power of two in 8 .. 4096: 64                     */
+    int32_t taps_per_branch;    /* K in 1 .. 16, M * K <= 32768: 8                        */
+    float gain;                 /* finite: 1                                              */
+    int32_t device;             /* HIP device ordinal                                     */
+    int32_t reserved[12];
+} qpsk_pfb_params;
+typedef struct qpsk_pfb qpsk_pfb;
+#define QPSK_PFB_MIN_CHANNELS 8
+#define QPSK_PFB_MAX_CHANNELS 4096
+#define QPSK_PFB_MAX_BRANCH_TAPS 16
+#define QPSK_PFB_MAX_TAPS 32768
+#define QPSK_PFB_STATE_HEAD 64
+/* channels = 64, taps_per_branch = 8, gain = 1, the rest 0. */
+void qpsk_pfb_params_init(qpsk_pfb_params *p);
+/* channels, taps_per_branch or their product outside the limits above, or a
+ * gain that is not finite: QPSK_ERR_OUT_OF_RANGE; n_bands outside 1 .. 65535:
+ * QPSK_ERR_ARGUMENT; all before a device is touched. */
+int qpsk_pfb_create(const qpsk_pfb_params *p, int32_t n_bands, qpsk_pfb **out);
+int qpsk_pfb_destroy(qpsk_pfb *pf);
+/* As qpsk_path_set_stream. */
+int qpsk_pfb_set_stream(qpsk_pfb *pf, void *hip_stream);
+/* Host only.  The prototype of p into taps[n_taps], n_taps = M * K (else
+ * QPSK_ERR_ARGUMENT). */
+int qpsk_pfb_design(const qpsk_pfb_params *p, float *taps, int64_t n_taps);
+/* Host only.  W of M channels into w[n_floats], n_floats = M (re, im of M / 2
+ * twiddles; else QPSK_ERR_ARGUMENT); a bad M is QPSK_ERR_OUT_OF_RANGE. */
+int qpsk_pfb_twiddles(int32_t channels, float *w, int64_t n_floats);
+/* Replaces the prototype: taps is host memory, n_taps = M * K floats (else
+ * QPSK_ERR_ARGUMENT), all finite (else QPSK_ERR_OUT_OF_RANGE).  Takes effect
+ * behind the calls queued so far; the history is kept. */
+int qpsk_pfb_set_taps(qpsk_pfb *pf, const float *taps, int64_t n_taps);
+/* Host only.  max(0, ceil(in_end / D) - out_pos): what a band that has emitted
+ * out_pos frames emits once it has taken in_end inputs.  Negative (an error
+ * code) for a bad M, in_end outside [0, 2^50] or out_pos < 0. */
+int64_t qpsk_pfb_count(int32_t channels, int64_t out_pos, int64_t in_end);
+/* Host only.  n_in / D + 1, a capacity that suffices for any call of n_in
+ * samples; negative (an error code) for a bad M or n_in outside [0, 2^50]. */
+int64_t qpsk_pfb_out_bound(int32_t channels, int64_t n_in);
+/* Host only.  The frames one workgroup of the kernel covers, 4096 / M: the
+ * per-call frame counts at which the kernel changes tiles
+ * (tests/test_gpu_pfb.py spans them).  A bad M is QPSK_ERR_OUT_OF_RANGE. */
+int qpsk_pfb_tile_frames(int32_t channels);
+/* One call: band b takes lengths[b] samples (lengths == NULL: n_samples for
+ * all; host memory, each 0 .. n_samples) from row b of in, [n_bands][stride_in]
+ * elements of fmt_in read as qpsk_demod_process_fmt reads them (scale_in; CU8
+ * zero at 128), and writes n_out[b] samples to each of its M rows of out,
+ * [n_bands * M][stride_out] floats, stride_out >= 2 * out_cap.  n_out is host
+ * memory, [n_bands], and is filled before the call returns even when the
+ * device work is only queued: the counts are a function of the call lengths
+ * and the positions, which the handle keeps on the host.  A band that would
+ * emit more than out_cap frames makes the call QPSK_ERR_ARGUMENT
+ * (qpsk_pfb_out_bound gives a capacity that always suffices).  out must not
+ * overlap in (the test is on the two buffers' whole extents), else
+ * QPSK_ERR_ARGUMENT.  Device rows, scale_in, mem, queueing and the return
+ * follow qpsk_path_apply_fmt: a device call without lengths is queued on the
+ * handle's stream and returns; input rows 16-byte aligned with a pitch that is
+ * a multiple of 16 bytes are read with 16-byte loads; output rows 8-byte
+ * aligned are written a sample a store.  Elements past a row's n_out are not
+ * written.  A rejected call changes neither the state nor out.  The caller's
+ * current device is the same on return. */
+int qpsk_pfb_apply_fmt(qpsk_pfb *pf, int32_t fmt_in, const void *in, int64_t stride_in, float scale_in, float *out,
+                       int64_t stride_out, int64_t out_cap, int64_t n_samples, const int64_t *lengths, int64_t *n_out,
+                       int32_t mem);
+/* State: per band QPSK_PFB_STATE_HEAD = 64 bytes
+ *   int64 in_pos, out_pos; 48 reserved bytes (0)
+ * followed by float hist[L][2], the widened inputs at indices in_pos-L ..
+ * in_pos-1 (entries at negative indices are +0); no header in front of the
+ * bands.  The taps are not part of it.  qpsk_pfb_state_size(p) = 64 + 8 L
+ * (negative, an error code, for bad parameters) and qpsk_pfb_state_init (the
+ * state qpsk_pfb_create leaves: all zero; buf_bytes = n_bands * state_size)
+ * need no device.  get_state / set_state as the path's; set_state runs
+ * qpsk_pfb_state_check first and changes nothing when it fails; reset_bands
+ * gives the listed bands (a list as qpsk_stream_list_check accepts) positions
+ * 0 and an empty history. */
+int64_t qpsk_pfb_state_size(const qpsk_pfb_params *p);
+int qpsk_pfb_state_init(const qpsk_pfb_params *p, int32_t n_bands, void *buf, int64_t buf_bytes);
+int qpsk_pfb_get_state(qpsk_pfb *pf, void *host_buf, int64_t buf_bytes);
+int qpsk_pfb_set_state(qpsk_pfb *pf, const void *host_buf, int64_t buf_bytes);
+int qpsk_pfb_reset_bands(qpsk_pfb *pf, const int32_t *bands, int32_t n);
+/* What a state must satisfy (host only): buf_bytes = n_bands * state_size;
+ * in_pos in [0, 2^50]; out_pos == ceil(in_pos / D) (the band has emitted
+ * everything it could); hist entries at negative indices +0 (the others may
+ * hold any bits: inputs may be NaN); reserved bytes 0.  A failure is
+ * QPSK_ERR_ARGUMENT and names band and field in qpsk_last_error. */
+int qpsk_pfb_state_check(const qpsk_pfb_params *p, int32_t n_bands, const void *buf, int64_t buf_bytes);
+/* The same call on host CF32 rows and a state blob, single-threaded, no
+ * device: taps is the prototype, M * K floats (NULL: the design of p); state
+ * is [n_bands] records (checked first, advanced by the call), in and out float
+ * rows with strides in floats, the rest as qpsk_pfb_apply_fmt with CF32 input. */
+int qpsk_pfb_apply_host(const qpsk_pfb_params *p, const float *taps, void *state, int64_t state_bytes, int32_t n_bands,
+                        const float *in, int64_t stride_in, float *out, int64_t stride_out, int64_t out_cap,
+                        int64_t n_samples, const int64_t *lengths, int64_t *n_out);
+
 const char *qpsk_last_error(void);
 int qpsk_abi_version(void);
 

@@ -183,6 +183,12 @@ class PathParams(C.Structure):
                 ("device", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+class PfbParams(C.Structure):
+    """qpsk_pfb_params: the channels, the prototype's length and the gain of the polyphase channeliser."""
+    _fields_ = [("channels", C.c_int32), ("taps_per_branch", C.c_int32), ("gain", C.c_float), ("device", C.c_int32),
+                ("reserved", C.c_int32 * 12)]
+
+
 class LoopShape(C.Structure):
     """qpsk_loop_shape (include/qpsk_demod.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -422,6 +428,31 @@ def lib():
     L.qpsk_path_state_check.argtypes = [C.c_int32, C.c_void_p, C.c_int64]
     L.qpsk_path_apply_host.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                        C.c_int64, C.c_int64, _i64p, _i64p]
+    # the polyphase channeliser: one wideband row into M streams
+    L.qpsk_pfb_params_init.argtypes = [C.POINTER(PfbParams)]
+    L.qpsk_pfb_params_init.restype = None
+    L.qpsk_pfb_create.argtypes = [C.POINTER(PfbParams), C.c_int32, C.POINTER(C.c_void_p)]
+    L.qpsk_pfb_destroy.argtypes = [C.c_void_p]
+    L.qpsk_pfb_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.qpsk_pfb_design.argtypes = [C.POINTER(PfbParams), C.c_void_p, C.c_int64]
+    L.qpsk_pfb_twiddles.argtypes = [C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_pfb_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_pfb_count.argtypes = [C.c_int32, C.c_int64, C.c_int64]
+    L.qpsk_pfb_count.restype = C.c_int64
+    L.qpsk_pfb_out_bound.argtypes = [C.c_int32, C.c_int64]
+    L.qpsk_pfb_out_bound.restype = C.c_int64
+    L.qpsk_pfb_tile_frames.argtypes = [C.c_int32]
+    L.qpsk_pfb_apply_fmt.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64,
+                                     C.c_int64, C.c_int64, _i64p, _i64p, C.c_int32]
+    L.qpsk_pfb_state_size.argtypes = [C.POINTER(PfbParams)]
+    L.qpsk_pfb_state_size.restype = C.c_int64
+    L.qpsk_pfb_state_init.argtypes = [C.POINTER(PfbParams), C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_pfb_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_pfb_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_pfb_reset_bands.argtypes = [C.c_void_p, _i32p, C.c_int32]
+    L.qpsk_pfb_state_check.argtypes = [C.POINTER(PfbParams), C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_pfb_apply_host.argtypes = [C.POINTER(PfbParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p]
     _lib = real
     return real
 
@@ -471,6 +502,10 @@ EXPORTED_SYMBOLS = [
     "qpsk_path_apply_fmt", "qpsk_path_out_bound", "qpsk_path_count", "qpsk_path_state_size", "qpsk_path_state_init",
     "qpsk_path_get_state", "qpsk_path_set_state", "qpsk_path_reset_streams", "qpsk_path_state_check",
     "qpsk_path_apply_host",
+    "qpsk_pfb_params_init", "qpsk_pfb_create", "qpsk_pfb_destroy", "qpsk_pfb_set_stream", "qpsk_pfb_design",
+    "qpsk_pfb_twiddles", "qpsk_pfb_set_taps", "qpsk_pfb_count", "qpsk_pfb_out_bound", "qpsk_pfb_tile_frames",
+    "qpsk_pfb_apply_fmt", "qpsk_pfb_state_size", "qpsk_pfb_state_init", "qpsk_pfb_get_state", "qpsk_pfb_set_state",
+    "qpsk_pfb_reset_bands", "qpsk_pfb_state_check", "qpsk_pfb_apply_host",
 ]
 
 _EXC = {
@@ -2096,6 +2131,221 @@ class Path:
     def reset_streams(self, streams):
         a, n = _stream_list(streams)
         _check(lib().qpsk_path_reset_streams(self._h, a, n))
+
+PFB_STATE_HEAD = 64           # QPSK_PFB_STATE_HEAD
+PFB_MIN_CHANNELS, PFB_MAX_CHANNELS, PFB_MAX_BRANCH_TAPS, PFB_MAX_TAPS = 8, 4096, 16, 32768
+
+
+def pfb_state_dtype(channels: int, taps_per_branch: int) -> np.dtype:
+    """One band's state record: the 64-byte head, then hist[L][2]."""
+    dt = np.dtype([("in_pos", "i8"), ("out_pos", "i8"), ("reserved", "u1", (48,)),
+                   ("hist", "f4", (int(channels) * int(taps_per_branch), 2))])
+    assert dt.itemsize == PFB_STATE_HEAD + 8 * int(channels) * int(taps_per_branch)
+    return dt
+
+
+def pfb_params(channels=None, taps_per_branch=None, gain=None, device=None) -> PfbParams:
+    """qpsk_pfb_params_init's defaults (64 channels, 8 taps a branch, gain 1) with the given fields replaced."""
+    p = PfbParams()
+    lib().qpsk_pfb_params_init(C.byref(p))
+    for name, v in (("channels", channels), ("taps_per_branch", taps_per_branch), ("device", device)):
+        if v is not None:
+            setattr(p, name, int(v))
+    if gain is not None:
+        p.gain = float(gain)
+    return p
+
+
+def pfb_design(p: PfbParams) -> np.ndarray:
+    """qpsk_pfb_design: the prototype of p, float32 [M K] (needs no device)."""
+    h = np.zeros(max(int(p.channels) * int(p.taps_per_branch), 1), np.float32)
+    _check(lib().qpsk_pfb_design(C.byref(p), h.ctypes.data, int(p.channels) * int(p.taps_per_branch)))
+    return h
+
+
+def pfb_twiddles(channels: int) -> np.ndarray:
+    """qpsk_pfb_twiddles: W of M channels, float32 [M / 2, 2] (needs no device)."""
+    w = np.zeros((max(int(channels) // 2, 1), 2), np.float32)
+    _check(lib().qpsk_pfb_twiddles(int(channels), w.ctypes.data, int(channels)))
+    return w
+
+
+def pfb_count(channels: int, out_pos: int, in_end: int) -> int:
+    """qpsk_pfb_count: max(0, ceil(in_end / D) - out_pos) (needs no device)."""
+    return int(_check(lib().qpsk_pfb_count(int(channels), int(out_pos), int(in_end))))
+
+
+def pfb_out_bound(channels: int, n_in: int) -> int:
+    """qpsk_pfb_out_bound: n_in / D + 1 (needs no device)."""
+    return int(_check(lib().qpsk_pfb_out_bound(int(channels), int(n_in))))
+
+
+def pfb_tile_frames(channels: int) -> int:
+    """qpsk_pfb_tile_frames: the frames one workgroup of the kernel covers (needs no device)."""
+    return int(_check(lib().qpsk_pfb_tile_frames(int(channels))))
+
+
+def pfb_state_size(p: PfbParams) -> int:
+    """qpsk_pfb_state_size: the bytes of one band's state, 64 + 8 M K (needs no device)."""
+    return int(_check(lib().qpsk_pfb_state_size(C.byref(p))))
+
+
+def pfb_state_init(p: PfbParams, n_bands: int) -> bytes:
+    """qpsk_pfb_state_init: the state qpsk_pfb_create leaves (needs no device)."""
+    buf = C.create_string_buffer(pfb_state_size(p) * int(n_bands))
+    _check(lib().qpsk_pfb_state_init(C.byref(p), int(n_bands), buf, len(buf)))
+    return buf.raw
+
+
+def pfb_state_check(p: PfbParams, n_bands: int, blob):
+    """qpsk_pfb_state_check: raises ValueError naming band and field when blob
+    is no state of a channeliser of n_bands.  Needs no device."""
+    b = bytes(blob)
+    _check(lib().qpsk_pfb_state_check(C.byref(p), int(n_bands), b, len(b)))
+
+
+def pfb_apply_host(p: PfbParams, state, rows: np.ndarray, lengths=None, out: np.ndarray | None = None,
+                   out_cap: int | None = None, n: int | None = None, taps=None):
+    """qpsk_pfb_apply_host: one call on host float32 rows [n_bands, 2 n] and a
+    state blob, no device.  Returns (the new state, out rows [n_bands M, 2
+    out_cap], n_out); a refused call raises and leaves out as it was."""
+    st = C.create_string_buffer(bytes(state), len(bytes(state)))
+    B = len(st) // max(pfb_state_size(p), 1)
+    if rows.dtype != np.float32 or rows.ndim != 2 or rows.shape[0] != B or (rows.shape[1] > 1 and rows.strides[1] != 4):
+        raise ValueError("rows must be [n_bands, 2 n] float32 with contiguous rows")
+    n = rows.shape[1] // 2 if n is None else int(n)
+    if out is None:
+        cap = pfb_out_bound(p.channels, n) if out_cap is None else int(out_cap)
+        out = np.zeros((B * p.channels, max(2 * cap, 2)), np.float32)
+    cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
+    keep, lp = Channel._lengths(lengths, B)
+    t = None if taps is None else np.ascontiguousarray(taps, dtype=np.float32)
+    n_out = np.zeros(B, np.int64)
+    _check(lib().qpsk_pfb_apply_host(C.byref(p), None if t is None else t.ctypes.data, st, len(st), B, rows.ctypes.data,
+                                     rows.strides[0] // 4, out.ctypes.data, out.strides[0] // 4, cap, n, lp,
+                                     n_out.ctypes.data_as(_i64p)))
+    return st.raw, out, n_out
+
+
+class Channeliser:
+    """The polyphase channeliser on n_bands wideband rows (qpsk_pfb_*): band b's
+    M = channels output rows b M .. b M + M - 1 are the signals around c fs / M
+    at rate 2 fs / M, CF32, ready for BatchDemodulator.  Rows of any format in,
+    host or device memory; a call emits the frames its inputs make computable
+    and returns the counts."""
+
+    def __init__(self, n_bands: int, p: PfbParams | None = None, **fields):
+        self.p = p if p is not None else pfb_params(**fields)
+        self.n_bands = int(n_bands)
+        self.channels = int(self.p.channels)
+        self.n_rows = self.n_bands * self.channels
+        h = C.c_void_p()
+        _check(lib().qpsk_pfb_create(C.byref(self.p), self.n_bands, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().qpsk_pfb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream_ptr: int | None):
+        """Order the handle's calls on a caller's stream (torch's); None goes
+        back to the handle's own."""
+        _check(lib().qpsk_pfb_set_stream(self._h, C.c_void_p(hip_stream_ptr or 0)))
+        self._bound = bool(hip_stream_ptr)
+
+    def set_taps(self, taps):
+        """Replace the prototype: M K real taps."""
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1))
+        _check(lib().qpsk_pfb_set_taps(self._h, t.ctypes.data if t.size else None, t.size))
+
+    def out_bound(self, n_in: int) -> int:
+        return pfb_out_bound(self.channels, n_in)
+
+    def lengths_for_demod(self, n_out) -> np.ndarray:
+        """A band's count repeated over its M rows: the lengths of the
+        demodulator call that takes the output rows."""
+        n_out = np.asarray(n_out, np.int64).reshape(-1)
+        if n_out.size != self.n_bands:
+            raise ValueError("n_out must hold one count a band")
+        return np.repeat(n_out, self.channels)
+
+    def apply(self, rows: np.ndarray, fmt="cf32", lengths=None, scale_in=None, out: np.ndarray | None = None,
+              n: int | None = None, out_cap: int | None = None):
+        """One host-memory call on rows [n_bands, 2 n] of fmt; returns (float32
+        rows [n_bands M, 2 out_cap], n_out).  out: rows to write into; what
+        lies past a row's n_out stays as it was."""
+        tag_in, dt_in, _ = _format(fmt)
+        if rows.dtype != dt_in or rows.ndim != 2 or rows.shape[0] != self.n_bands or rows.strides[1] != rows.itemsize:
+            raise ValueError(f"rows must be [n_bands, 2 n] of {np.dtype(dt_in).name} with contiguous rows")
+        n = rows.shape[1] // 2 if n is None else int(n)
+        if out is None:
+            out = np.zeros((self.n_rows, max(2 * (self.out_bound(n) if out_cap is None else int(out_cap)), 2)), np.float32)
+        if out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != self.n_rows or out.strides[1] != 4:
+            raise ValueError("out must be [n_bands M, 2 out_cap] float32 with contiguous rows")
+        cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
+        keep, lp = Channel._lengths(lengths, self.n_bands)
+        si, _ = Channel._scales(tag_in, FMT_CF32, scale_in, None)
+        n_out = np.zeros(self.n_bands, np.int64)
+        _check(lib().qpsk_pfb_apply_fmt(self._h, tag_in, rows.ctypes.data, rows.strides[0] // rows.itemsize, si,
+                                        out.ctypes.data, out.strides[0] // 4, cap, n, lp, n_out.ctypes.data_as(_i64p),
+                                        MEM_HOST))
+        return out, n_out
+
+    def apply_device(self, in_dev, n: int, out_dev, fmt="cf32", lengths=None, scale_in=None,
+                     out_cap: int | None = None) -> np.ndarray:
+        """One device-memory call: in_dev [n_bands, >= 2 n] of fmt, out_dev
+        [n_bands M, >= 2 out_cap] float32 (out_cap defaults to what out_dev
+        holds).  Returns n_out, a host array, at once.  lengths is a host
+        array.  Ordered on the handle's stream; without set_stream the
+        caller's torch stream is drained first and the call is waited for."""
+        import torch
+        tag_in = _format(fmt)[0]
+        cap = out_dev.shape[1] // 2 if out_cap is None else int(out_cap)
+        for t, f, rows, need, what in ((in_dev, fmt, self.n_bands, 2 * n, "in_dev"),
+                                       (out_dev, "cf32", self.n_rows, 2 * cap, "out_dev")):
+            if (not t.is_cuda or t.dtype != _torch_dtype(f) or t.dim() != 2 or t.shape[0] != rows or
+                    (t.shape[1] > 1 and t.stride(1) != 1) or t.shape[1] < need):
+                raise ValueError(f"{what} must be a contiguous-row [rows, >= 2 n] device tensor of its format")
+        keep, lp = Channel._lengths(lengths, self.n_bands)
+        si, _ = Channel._scales(tag_in, FMT_CF32, scale_in, None)
+        bound = getattr(self, "_bound", False)
+        if not bound:   # the handle's own stream does not order against torch's
+            torch.cuda.current_stream(out_dev.device).synchronize()
+        n_out = np.zeros(self.n_bands, np.int64)
+        _check(lib().qpsk_pfb_apply_fmt(self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, out_dev.data_ptr(),
+                                        out_dev.stride(0), cap, int(n), lp, n_out.ctypes.data_as(_i64p), MEM_DEVICE))
+        if not bound:
+            self.sync()
+        return n_out
+
+    def sync(self):
+        """Wait for the calls queued on the handle (reads its state)."""
+        self.get_state()
+
+    def get_state(self) -> bytes:
+        buf = C.create_string_buffer(pfb_state_size(self.p) * self.n_bands)
+        _check(lib().qpsk_pfb_get_state(self._h, buf, len(buf)))
+        return buf.raw
+
+    def states(self, blob: bytes | None = None) -> np.ndarray:
+        """The state as a pfb_state_dtype array, one record a band."""
+        dt = pfb_state_dtype(self.channels, self.p.taps_per_branch)
+        return np.frombuffer(self.get_state() if blob is None else blob, dtype=dt).copy()
+
+    def set_state(self, blob):
+        b = bytes(blob)
+        _check(lib().qpsk_pfb_set_state(self._h, b, len(b)))
+
+    def reset_bands(self, bands):
+        a, n = _stream_list(bands)
+        _check(lib().qpsk_pfb_reset_bands(self._h, a, n))
 
 
 def _norm(norm):
