@@ -14,6 +14,7 @@
 
 #include "qpsk_demod.h"
 #include "qpsk_internal.h"
+#include "qpsk_row_call.h"
 
 namespace qpsk {
 namespace {
@@ -99,10 +100,8 @@ int qpsk_channel_state_check(const qpsk_channel_params *p, int32_t n_streams, co
     int rc;
     if ((rc = chan_check_params(p, n_streams))) return rc;
     if (!buf) return fail(QPSK_ERR_ARGUMENT_NULL, "channel state buffer is null");
-    const int64_t want = static_cast<int64_t>(n_streams) * static_cast<int64_t>(sizeof(ChanState));
-    if (buf_bytes != want)
-        return fail(QPSK_ERR_ARGUMENT, "channel state length does not match this handle (" + std::to_string(buf_bytes) +
-                                           " vs " + std::to_string(want) + " bytes)");
+    if ((rc = check_state_bytes("channel", buf_bytes, static_cast<int64_t>(n_streams) * static_cast<int64_t>(sizeof(ChanState)))))
+        return rc;
     const ChanNcoConst ct = chan_nco_const(p->lo_hz, p->sample_rate, p->tx_ppm);
     const ChanNcoConst cr = chan_nco_const(p->lo_hz, p->sample_rate, p->rx_ppm);
     const char *rec = static_cast<const char *>(buf);

@@ -39,15 +39,14 @@
 #include "qpsk_glibc_trig.h"
 #include "qpsk_internal.h"
 #include "qpsk_quantise.h"
+#include "qpsk_row_call.h"
+#include "qpsk_row_handle.h"
 #include "qpsk_sample_rows.h"
 
-struct qpsk_channel {
+struct qpsk_channel : qpsk::RowHandle {
     qpsk_channel_params p{};
     int S = 0;
-    qpsk::Stream stream;                     // in front of the buffers, which go first
     qpsk::DevBuf<qpsk::ChanState> d_state;   // [S]
-    qpsk::DevBuf<int64_t> d_len;             // [S]: a call's checked lengths
-    qpsk::DevBuf<uint8_t> d_in, d_out;       // host calls: 16-byte-pitched rows
 };
 
 namespace {
@@ -60,6 +59,7 @@ using qpsk::DeviceGuard;
 using qpsk::fail;
 using qpsk::load_sample;
 using qpsk::pair_rows;
+using qpsk::row_length;
 using qpsk::store_sample;
 
 constexpr int kStreams = QPSK_CHANNEL_TILE_STREAMS;
@@ -89,8 +89,6 @@ struct ChanArgs {
 
 // Math.Clamp(v, -1.0f, 1.0f): a NaN stays
 __device__ __forceinline__ float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
-
-__device__ __forceinline__ int64_t row_length(const ChanArgs &a, int s) { return a.lengths ? a.lengths[s] : a.n; }
 
 __global__ __launch_bounds__(kThreads) void channel_kernel(ChanArgs a) {
     __shared__ double tab[440];
@@ -206,8 +204,7 @@ int qpsk_channel_create(const qpsk_channel_params *p, int32_t n_streams, qpsk_ch
     ch->S = n_streams;
     std::vector<ChanState> st(n_streams);
     for (int32_t s = 0; s < n_streams; ++s) st[s] = qpsk::chan_state_new(*p, s);
-    if (hipSetDevice(p->device) != hipSuccess || ch->stream.create(hipStreamNonBlocking) != hipSuccess ||
-        ch->d_state.alloc(n_streams) != hipSuccess || ch->d_len.alloc(n_streams) != hipSuccess ||
+    if (ch->open(p->device, n_streams) != hipSuccess || ch->d_state.alloc(n_streams) != hipSuccess ||
         hipMemcpy(ch->d_state, st.data(), st.size() * sizeof(ChanState), hipMemcpyHostToDevice) != hipSuccess) {
         delete ch;
         return fail(QPSK_ERR_DEVICE, "channel device set-up failed (no GPU?)");
@@ -216,49 +213,23 @@ int qpsk_channel_create(const qpsk_channel_params *p, int32_t n_streams, qpsk_ch
     return QPSK_OK;
 }
 
-int qpsk_channel_destroy(qpsk_channel *ch) {
-    if (!ch) return QPSK_OK;
-    DeviceGuard guard;
-    (void)hipSetDevice(ch->p.device);
-    if (ch->stream) (void)hipStreamSynchronize(ch->stream);
-    delete ch;
-    return QPSK_OK;
-}
+int qpsk_channel_destroy(qpsk_channel *ch) { return qpsk::row_handle_destroy(ch); }
 
 int qpsk_channel_set_stream(qpsk_channel *ch, void *hip_stream) {
     if (!ch) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
-    QPSK_HIP_TRY(hipStreamSynchronize(ch->stream));
-    QPSK_HIP_TRY(ch->stream.rebind(hip_stream));
-    return QPSK_OK;
+    return ch->set_stream(hip_stream);
 }
 
 int qpsk_channel_apply_fmt(qpsk_channel *ch, int32_t fmt_in, const void *in, int64_t stride_in, float scale_in,
                            int32_t fmt_out, int32_t norm_out, void *out, int64_t stride_out, float scale_out,
                            int64_t n_samples, const int64_t *lengths, int32_t mem) {
     if (!ch) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    if (!qpsk::fmt_known(fmt_in) || !qpsk::fmt_known(fmt_out))
-        return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
-    if (norm_out != QPSK_MOD_NORM_FIXED)
-        return fail(QPSK_ERR_ARGUMENT, norm_out == QPSK_MOD_NORM_PEAK
-                                           ? "the channel does not normalise rows to their peak (a second pass): "
-                                             "QPSK_MOD_NORM_FIXED only"
-                                           : "unknown norm");
-    if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
-    if (fmt_in != QPSK_FMT_CF32 && !qpsk::quant_scale_ok(scale_in))
-        return fail(QPSK_ERR_OUT_OF_RANGE, "scale_in must be finite and > 0");
-    if (!qpsk::quant_scale_ok(scale_out)) return fail(QPSK_ERR_OUT_OF_RANGE, "scale_out must be finite and > 0");
+    int rc;
+    if ((rc = qpsk::check_row_formats("channel", fmt_in, scale_in, fmt_out, norm_out, scale_out, mem))) return rc;
     if (n_samples < 0) return fail(QPSK_ERR_ARGUMENT, "n_samples must not be negative");
     const int S = ch->S;
-    int64_t n_call = lengths ? 0 : n_samples;
-    if (lengths)
-        for (int s = 0; s < S; ++s) {
-            if (lengths[s] < 0 || lengths[s] > n_samples)
-                return fail(QPSK_ERR_ARGUMENT, "lengths[" + std::to_string(s) + "] = " + std::to_string(lengths[s]) +
-                                                   " outside [0, n_samples]");
-            n_call = std::max(n_call, lengths[s]);
-        }
+    int64_t n_call;
+    if ((rc = qpsk::check_lengths(S, n_samples, lengths, &n_call))) return rc;
     if (n_call == 0) return QPSK_OK;
     if (!in || !out) return fail(QPSK_ERR_ARGUMENT_NULL, "in or out is null");
     if (n_samples > (INT64_MAX >> 4) || stride_in < 2 * n_samples || stride_out < 2 * n_samples)
@@ -266,13 +237,12 @@ int qpsk_channel_apply_fmt(qpsk_channel *ch, int32_t fmt_in, const void *in, int
     if (in == out && (fmt_in != fmt_out || stride_in != stride_out))
         return fail(QPSK_ERR_ARGUMENT, "in place needs one format and one stride");
     const bool host = mem == QPSK_MEM_HOST;
-    int rc;
     if (!host && ((rc = check_device_rows("input", fmt_in, in, stride_in)) ||
                   (rc = check_device_rows("output", fmt_out, out, stride_out))))
         return rc;
 
     DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
+    QPSK_HIP_TRY(hipSetDevice(ch->device));
     hipStream_t st = ch->stream;
     ChanArgs a = base_args(ch);
     a.in = in;
@@ -284,33 +254,24 @@ int qpsk_channel_apply_fmt(qpsk_channel *ch, int32_t fmt_in, const void *in, int
     a.fmt_in = fmt_in;
     a.fmt_out = fmt_out;
     a.n = n_samples;
-    const int64_t ieb = qpsk::fmt_elem_bytes(fmt_in), oeb = qpsk::fmt_elem_bytes(fmt_out);
-    if (lengths) {
-        // the kernel reads the lengths the host checked
-        QPSK_HIP_TRY(hipMemcpyAsync(ch->d_len, lengths, S * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        a.lengths = ch->d_len;
-    }
-    const int64_t ipitch = (2 * n_call * ieb + 15) / 16 * 16, opitch = (2 * n_call * oeb + 15) / 16 * 16;
+    const int64_t oeb = qpsk::fmt_elem_bytes(fmt_out);
+    if ((rc = ch->upload_lengths(lengths, S, &a.lengths))) return rc;
     if (host) {
-        if ((rc = qpsk::alloc_status(ch->d_in.grow(static_cast<size_t>(S) * ipitch), kStaging))) return rc;
-        if ((rc = qpsk::alloc_status(ch->d_out.grow(static_cast<size_t>(S) * opitch), kStaging))) return rc;
-        QPSK_HIP_TRY(hipMemcpy2DAsync(ch->d_in, ipitch, in, stride_in * ieb, 2 * n_call * ieb, S, hipMemcpyHostToDevice, st));
+        if ((rc = ch->stage_out(kStaging, oeb, n_call, S, &a.out, &a.out_stride)) ||
+            (rc = ch->stage_in(kStaging, in, stride_in, qpsk::fmt_elem_bytes(fmt_in), n_call, S, &a.in, &a.in_stride)))
+            return rc;
         // what lies past a row's length comes back as it was
         if (lengths)
-            QPSK_HIP_TRY(hipMemcpy2DAsync(ch->d_out, opitch, out, stride_out * oeb, 2 * n_call * oeb, S,
+            QPSK_HIP_TRY(hipMemcpy2DAsync(a.out, a.out_stride * oeb, out, stride_out * oeb, 2 * n_call * oeb, S,
                                           hipMemcpyHostToDevice, st));
-        a.in = ch->d_in;
-        a.out = ch->d_out;
-        a.in_stride = ipitch / ieb;
-        a.out_stride = opitch / oeb;
     }
     a.in_pair = pair_rows(fmt_in, a.in, a.in_stride);
     a.out_pair = pair_rows(fmt_out, a.out, a.out_stride);
     hipLaunchKernelGGL(channel_kernel, dim3((S + kStreams - 1) / kStreams), dim3(kThreads), 0, st, a);
     QPSK_HIP_TRY(hipGetLastError());
     if (host)
-        QPSK_HIP_TRY(hipMemcpy2DAsync(out, stride_out * oeb, ch->d_out, opitch, 2 * n_call * oeb, S, hipMemcpyDeviceToHost,
-                                      st));
+        QPSK_HIP_TRY(hipMemcpy2DAsync(out, stride_out * oeb, a.out, a.out_stride * oeb, 2 * n_call * oeb, S,
+                                      hipMemcpyDeviceToHost, st));
     if (host || lengths) QPSK_HIP_TRY(hipStreamSynchronize(st));
     return QPSK_OK;
 }
@@ -318,25 +279,16 @@ int qpsk_channel_apply_fmt(qpsk_channel *ch, int32_t fmt_in, const void *in, int
 int qpsk_channel_get_state(qpsk_channel *ch, void *host_buf, int64_t buf_bytes) {
     if (!ch || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     const int64_t want = static_cast<int64_t>(ch->S) * static_cast<int64_t>(sizeof(ChanState));
-    if (buf_bytes != want)
-        return fail(QPSK_ERR_ARGUMENT, "channel state length does not match this handle (" + std::to_string(buf_bytes) +
-                                           " vs " + std::to_string(want) + " bytes)");
-    DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
-    QPSK_HIP_TRY(hipMemcpyAsync(host_buf, ch->d_state, want, hipMemcpyDeviceToHost, ch->stream));
-    QPSK_HIP_TRY(hipStreamSynchronize(ch->stream));
-    return QPSK_OK;
+    int rc;
+    if ((rc = qpsk::check_state_bytes("channel", buf_bytes, want))) return rc;
+    return ch->state_out(host_buf, ch->d_state, want);
 }
 
 int qpsk_channel_set_state(qpsk_channel *ch, const void *host_buf, int64_t buf_bytes) {
     if (!ch) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     int rc;
     if ((rc = qpsk_channel_state_check(&ch->p, ch->S, host_buf, buf_bytes))) return rc;
-    DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
-    QPSK_HIP_TRY(hipMemcpyAsync(ch->d_state, host_buf, buf_bytes, hipMemcpyHostToDevice, ch->stream));
-    QPSK_HIP_TRY(hipStreamSynchronize(ch->stream));
-    return QPSK_OK;
+    return ch->state_in(ch->d_state, host_buf, buf_bytes);
 }
 
 int qpsk_channel_reset_streams(qpsk_channel *ch, const int32_t *streams, int32_t n) {
@@ -344,7 +296,7 @@ int qpsk_channel_reset_streams(qpsk_channel *ch, const int32_t *streams, int32_t
     int rc;
     if ((rc = qpsk_stream_list_check(ch->S, streams, n))) return rc;
     DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(ch->p.device));
+    QPSK_HIP_TRY(hipSetDevice(ch->device));
     std::vector<ChanState> st(n);   // lives until the synchronise below
     for (int32_t k = 0; k < n; ++k) {
         st[k] = qpsk::chan_state_new(ch->p, streams[k]);

@@ -2,7 +2,8 @@
 // memory, pinned host memory, an event and a stream.  A handle holds them as
 // members, so its destructor releases them (in reverse order of declaration,
 // on the device its body made current) and a set-up that fails half way leaks
-// nothing.  Move-only.  Every call that can fail returns the hipError_t; the
+// nothing.  Move-only.  And DeviceGuard, which keeps an entry point from
+// changing its caller's current device.  Every call that can fail returns the hipError_t; the
 // file that makes the call gives it that file's error text.  Private, host-only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -125,6 +126,17 @@ class Stream {
     }
     hipStream_t s_ = nullptr;
     bool own_ = false;
+};
+
+// the caller's current device, put back when a call returns
+struct DeviceGuard {
+    int prev = -1;
+    DeviceGuard() {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
 };
 
 }  // namespace qpsk

@@ -15,6 +15,7 @@
 
 #include "qpsk_demod.h"
 #include "qpsk_internal.h"
+#include "qpsk_row_call.h"
 
 namespace qpsk {
 namespace {
@@ -121,35 +122,16 @@ void path_put_taps(PathState &st, const float *taps_iq, int32_t n_taps) {
 
 int path_check_call(const PathState *st, int32_t S, int64_t stride_in, int64_t stride_out, int64_t out_cap,
                     int64_t n_samples, const int64_t *lengths, int64_t *n_out, int64_t *n_call, int64_t *n_out_max) {
-    if (!n_out) return fail(QPSK_ERR_ARGUMENT_NULL, "n_out is null");
     if (n_samples < 0) return fail(QPSK_ERR_ARGUMENT, "n_samples must not be negative");
     if (out_cap < 0) return fail(QPSK_ERR_ARGUMENT, "out_cap must not be negative");
     if (n_samples > (INT64_MAX >> 4) || out_cap > (INT64_MAX >> 4)) return fail(QPSK_ERR_ARGUMENT, "stride too small");
-    *n_call = lengths ? 0 : n_samples;
-    if (lengths)
-        for (int s = 0; s < S; ++s) {
-            if (lengths[s] < 0 || lengths[s] > n_samples)
-                return fail(QPSK_ERR_ARGUMENT, "lengths[" + std::to_string(s) + "] = " + std::to_string(lengths[s]) +
-                                                   " outside [0, n_samples]");
-            *n_call = lengths[s] > *n_call ? lengths[s] : *n_call;
-        }
+    int rc;
+    if ((rc = check_lengths(S, n_samples, lengths, n_call))) return rc;
     if (*n_call > 0 && (stride_in < 2 * n_samples || stride_out < 2 * out_cap))
         return fail(QPSK_ERR_ARGUMENT, "stride too small");
-    // the counts, into a copy first: a rejected call leaves n_out as it was
-    std::vector<int64_t> cnt(S);
-    *n_out_max = 0;
-    for (int s = 0; s < S; ++s) {
-        const int64_t len = lengths ? lengths[s] : n_samples;
-        if (len > kPathMaxPos - st[s].in_pos)
-            return fail(QPSK_ERR_ARGUMENT, "stream " + std::to_string(s) + " would pass position 2^50");
-        cnt[s] = path_count(st[s].r, st[s].tau, st[s].out_pos, st[s].in_pos + len);
-        if (cnt[s] > out_cap)
-            return fail(QPSK_ERR_ARGUMENT, "stream " + std::to_string(s) + " would emit " + std::to_string(cnt[s]) +
-                                               " samples, out_cap is " + std::to_string(out_cap));
-        *n_out_max = cnt[s] > *n_out_max ? cnt[s] : *n_out_max;
-    }
-    std::memcpy(n_out, cnt.data(), sizeof(int64_t) * S);
-    return QPSK_OK;
+    return check_counts(st, S, n_samples, lengths, out_cap, kPathMaxPos, "stream", "samples",
+                        [](const PathState &r, int64_t in_end) { return path_count(r.r, r.tau, r.out_pos, in_end); },
+                        n_out, n_out_max);
 }
 
 void path_apply_stream(PathState &st, const float *in, int64_t len, float *out) {
@@ -231,12 +213,10 @@ int qpsk_path_state_check(int32_t n_streams, const void *buf, int64_t buf_bytes)
     using namespace qpsk;
     if (n_streams < 1) return fail(QPSK_ERR_ARGUMENT, "n_streams must be positive");
     if (!buf) return fail(QPSK_ERR_ARGUMENT_NULL, "path state buffer is null");
-    const int64_t want = static_cast<int64_t>(n_streams) * static_cast<int64_t>(sizeof(PathState));
-    if (buf_bytes != want)
-        return fail(QPSK_ERR_ARGUMENT, "path state length does not match this handle (" + std::to_string(buf_bytes) +
-                                           " vs " + std::to_string(want) + " bytes)");
-    const char *rec = static_cast<const char *>(buf);
     int rc;
+    if ((rc = check_state_bytes("path", buf_bytes, static_cast<int64_t>(n_streams) * static_cast<int64_t>(sizeof(PathState)))))
+        return rc;
+    const char *rec = static_cast<const char *>(buf);
     for (int32_t s = 0; s < n_streams; ++s, rec += sizeof(PathState)) {
         PathState st;
         std::memcpy(&st, rec, sizeof(st));
@@ -261,12 +241,9 @@ int qpsk_path_apply_host(void *state, int64_t state_bytes, int32_t n_streams, co
         return rc;
     if (n_call > 0 && !in) return fail(QPSK_ERR_ARGUMENT_NULL, "in is null");
     if (n_out_max > 0 && !out) return fail(QPSK_ERR_ARGUMENT_NULL, "out is null");
-    if (n_call > 0 && n_out_max > 0) {
-        const uintptr_t ib = reinterpret_cast<uintptr_t>(in), ob = reinterpret_cast<uintptr_t>(out);
-        const uintptr_t ie = ib + sizeof(float) * ((n_streams - 1) * stride_in + 2 * n_samples);
-        const uintptr_t oe = ob + sizeof(float) * ((n_streams - 1) * stride_out + 2 * out_cap);
-        if (ib < oe && ob < ie) return fail(QPSK_ERR_ARGUMENT, "out must not overlap in");
-    }
+    if (n_call > 0 && n_out_max > 0 &&
+        rows_overlap(in, n_streams, stride_in, n_samples, sizeof(float), out, n_streams, stride_out, out_cap, sizeof(float)))
+        return fail(QPSK_ERR_ARGUMENT, "out must not overlap in");
     std::memcpy(n_out, cnt.data(), sizeof(int64_t) * n_streams);
     for (int32_t s = 0; s < n_streams; ++s)
         path_apply_stream(st[s], in ? in + s * stride_in : nullptr, lengths ? lengths[s] : n_samples,

@@ -39,15 +39,14 @@
 #include "qpsk_internal.h"
 #include "qpsk_path.h"
 #include "qpsk_quantise.h"
+#include "qpsk_row_call.h"
+#include "qpsk_row_handle.h"
 #include "qpsk_sample_rows.h"
 
-struct qpsk_path {
+struct qpsk_path : qpsk::RowHandle {
     qpsk_path_params p{};
     int S = 0;
-    qpsk::Stream stream;                     // in front of the buffers, which go first
     qpsk::DevBuf<qpsk::PathState> d_state;   // [S]
-    qpsk::DevBuf<int64_t> d_len;             // [S]: a call's checked lengths
-    qpsk::DevBuf<uint8_t> d_in, d_out;       // host calls: 16-byte-pitched rows
     std::vector<qpsk::PathState> host;       // [S]: clock, positions and taps as the device will hold them
                                              // behind the calls queued so far (the history is not kept here)
 };
@@ -62,6 +61,7 @@ using qpsk::load_sample;
 using qpsk::pair_rows;
 using qpsk::PathC;
 using qpsk::PathState;
+using qpsk::row_length;
 using qpsk::store_sample;
 
 constexpr int kTile = QPSK_PATH_TILE_OUTPUTS;
@@ -84,8 +84,6 @@ struct PathArgs {
     PathState *state;
     int S;
 };
-
-__device__ __forceinline__ int64_t row_length(const PathArgs &a, int s) { return a.lengths ? a.lengths[s] : a.n; }
 
 __global__ __launch_bounds__(kThreads) void path_kernel(PathArgs a) {
     __shared__ float2 xs[kWin];
@@ -112,46 +110,10 @@ __global__ __launch_bounds__(kThreads) void path_kernel(PathArgs a) {
     if (L < 1 || L > QPSK_PATH_MAX_TAPS || zlen64 < 4 || zlen64 + L - 1 > kWin) return;
     const int zlen = static_cast<int>(zlen64), xlen = zlen + L - 1;
     const int64_t j0 = n_first - 1 - (L - 1) - in_pos;   // xs[0] as an index into the call's row
-    const int64_t j1 = j0 + xlen < len ? j0 + xlen : len;   // the row's part of the window: [max(j0, 0), j1)
-    const int64_t jr0 = j0 > 0 ? j0 : 0;
 
     const int64_t in_eb = qpsk::fmt_elem_bytes(a.fmt_in), out_eb = qpsk::fmt_elem_bytes(a.fmt_out);
     const char *irow = static_cast<const char *>(a.in) + static_cast<int64_t>(s) * a.in_stride * in_eb;
-    if (a.in_wide) {
-        // what precedes the row, and (never, in a checked state) what follows it
-        for (int m = tid; m < xlen; m += kThreads) {
-            const int64_t j = j0 + m;
-            if (j >= 0 && j < len) continue;
-            const int64_t h = kPathHist + j;
-            xs[m] = j < 0 && h >= 0 ? make_float2(st.hist[h][0], st.hist[h][1]) : make_float2(0.0f, 0.0f);
-        }
-        const int V = static_cast<int>(16 / (2 * in_eb));   // samples in 16 bytes: 2, 4 or 8
-        const int64_t c_hi = (j1 + V - 1) / V;
-        for (int64_t c = jr0 / V + tid; c < c_hi; c += kThreads) {
-            const int64_t jb = c * V;
-            if (jb + V <= len) {
-                // 16 bytes of the row in registers, read sample by sample as a row is
-                const uint4 w = *reinterpret_cast<const uint4 *>(irow + jb * 2 * in_eb);
-#pragma unroll
-                for (int v = 0; v < 8; ++v) {
-                    const int64_t j = jb + v;
-                    if (v < V && j >= jr0 && j < j1) xs[j - j0] = load_sample(&w, a.fmt_in, 1, v, a.scale_in);
-                }
-            } else {
-                for (int v = 0; v < V; ++v) {
-                    const int64_t j = jb + v;
-                    if (j >= jr0 && j < j1) xs[j - j0] = load_sample(irow, a.fmt_in, a.in_pair, j, a.scale_in);
-                }
-            }
-        }
-    } else {
-        for (int m = tid; m < xlen; m += kThreads) {
-            const int64_t j = j0 + m;
-            const int64_t h = kPathHist + j;
-            if (j >= 0 && j < len) xs[m] = load_sample(irow, a.fmt_in, a.in_pair, j, a.scale_in);
-            else xs[m] = j < 0 && h >= 0 ? make_float2(st.hist[h][0], st.hist[h][1]) : make_float2(0.0f, 0.0f);
-        }
-    }
+    qpsk::stage_window<kThreads>(xs, j0, xlen, len, irow, st.hist, kPathHist, a, tid);
     __syncthreads();
 
     // zs[q] is z at n_first - 1 + q, whose newest input is xs[q + L - 1]
@@ -213,10 +175,6 @@ __global__ __launch_bounds__(kThreads) void path_state_kernel(PathArgs a) {
 // what a failed grow of a staging buffer names (alloc_status)
 constexpr const char *kStaging = "path staging";
 
-bool wide_rows(int fmt, const void *rows, int64_t stride) {
-    return reinterpret_cast<uintptr_t>(rows) % 16 == 0 && (stride * qpsk::fmt_elem_bytes(fmt)) % 16 == 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -232,8 +190,7 @@ int qpsk_path_create(const qpsk_path_params *p, int32_t n_streams, qpsk_path **o
     pa->S = n_streams;
     pa->host.resize(n_streams);
     for (int32_t s = 0; s < n_streams; ++s) pa->host[s] = qpsk::path_state_new(*p, s);
-    if (hipSetDevice(p->device) != hipSuccess || pa->stream.create(hipStreamNonBlocking) != hipSuccess ||
-        pa->d_state.alloc(n_streams) != hipSuccess || pa->d_len.alloc(n_streams) != hipSuccess ||
+    if (pa->open(p->device, n_streams) != hipSuccess || pa->d_state.alloc(n_streams) != hipSuccess ||
         hipMemcpy(pa->d_state, pa->host.data(), pa->host.size() * sizeof(PathState), hipMemcpyHostToDevice) !=
             hipSuccess) {
         delete pa;
@@ -243,22 +200,11 @@ int qpsk_path_create(const qpsk_path_params *p, int32_t n_streams, qpsk_path **o
     return QPSK_OK;
 }
 
-int qpsk_path_destroy(qpsk_path *pa) {
-    if (!pa) return QPSK_OK;
-    DeviceGuard guard;
-    (void)hipSetDevice(pa->p.device);
-    if (pa->stream) (void)hipStreamSynchronize(pa->stream);
-    delete pa;
-    return QPSK_OK;
-}
+int qpsk_path_destroy(qpsk_path *pa) { return qpsk::row_handle_destroy(pa); }
 
 int qpsk_path_set_stream(qpsk_path *pa, void *hip_stream) {
     if (!pa) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pa->p.device));
-    QPSK_HIP_TRY(hipStreamSynchronize(pa->stream));
-    QPSK_HIP_TRY(pa->stream.rebind(hip_stream));
-    return QPSK_OK;
+    return pa->set_stream(hip_stream);
 }
 
 int qpsk_path_set_taps(qpsk_path *pa, const float *taps_iq, int32_t n_taps, int32_t per_stream) {
@@ -278,7 +224,7 @@ int qpsk_path_set_taps(qpsk_path *pa, const float *taps_iq, int32_t n_taps, int3
         std::memcpy(&part[s * kPart], &next[s].n_taps, kPart);
     }
     DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pa->p.device));
+    QPSK_HIP_TRY(hipSetDevice(pa->device));
     QPSK_HIP_TRY(hipMemcpy2DAsync(reinterpret_cast<char *>(pa->d_state.get()) + offsetof(PathState, n_taps),
                                   sizeof(PathState), part.data(), kPart, kPart, pa->S, hipMemcpyHostToDevice,
                                   pa->stream));
@@ -291,22 +237,12 @@ int qpsk_path_apply_fmt(qpsk_path *pa, int32_t fmt_in, const void *in, int64_t s
                         int32_t fmt_out, int32_t norm_out, void *out, int64_t stride_out, int64_t out_cap,
                         float scale_out, int64_t n_samples, const int64_t *lengths, int64_t *n_out, int32_t mem) {
     if (!pa) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    if (!qpsk::fmt_known(fmt_in) || !qpsk::fmt_known(fmt_out))
-        return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
-    if (norm_out != QPSK_MOD_NORM_FIXED)
-        return fail(QPSK_ERR_ARGUMENT, norm_out == QPSK_MOD_NORM_PEAK
-                                           ? "the path does not normalise rows to their peak (a second pass): "
-                                             "QPSK_MOD_NORM_FIXED only"
-                                           : "unknown norm");
-    if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
-    if (fmt_in != QPSK_FMT_CF32 && !qpsk::quant_scale_ok(scale_in))
-        return fail(QPSK_ERR_OUT_OF_RANGE, "scale_in must be finite and > 0");
-    if (!qpsk::quant_scale_ok(scale_out)) return fail(QPSK_ERR_OUT_OF_RANGE, "scale_out must be finite and > 0");
+    int rc;
+    if ((rc = qpsk::check_row_formats("path", fmt_in, scale_in, fmt_out, norm_out, scale_out, mem))) return rc;
     if (!n_out) return fail(QPSK_ERR_ARGUMENT_NULL, "n_out is null");
     const int S = pa->S;
     const bool host = mem == QPSK_MEM_HOST;
     const int64_t ieb = qpsk::fmt_elem_bytes(fmt_in), oeb = qpsk::fmt_elem_bytes(fmt_out);
-    int rc;
     int64_t n_call, n_out_max;
     std::vector<int64_t> cnt(S);
     if ((rc = qpsk::path_check_call(pa->host.data(), S, stride_in, stride_out, out_cap, n_samples, lengths, cnt.data(),
@@ -317,18 +253,14 @@ int qpsk_path_apply_fmt(qpsk_path *pa, int32_t fmt_in, const void *in, int64_t s
         if (!host && ((rc = check_device_rows("input", fmt_in, in, stride_in)) ||
                       (out && (rc = check_device_rows("output", fmt_out, out, stride_out)))))
             return rc;
-        if (out) {
-            const uintptr_t ib = reinterpret_cast<uintptr_t>(in), ob = reinterpret_cast<uintptr_t>(out);
-            const uintptr_t ie = ib + static_cast<uintptr_t>(((S - 1) * stride_in + 2 * n_samples) * ieb);
-            const uintptr_t oe = ob + static_cast<uintptr_t>(((S - 1) * stride_out + 2 * out_cap) * oeb);
-            if (ib < oe && ob < ie) return fail(QPSK_ERR_ARGUMENT, "out must not overlap in");
-        }
+        if (out && qpsk::rows_overlap(in, S, stride_in, n_samples, ieb, out, S, stride_out, out_cap, oeb))
+            return fail(QPSK_ERR_ARGUMENT, "out must not overlap in");
     }
     std::memcpy(n_out, cnt.data(), sizeof(int64_t) * S);
     if (n_call == 0) return QPSK_OK;   // nothing taken: nothing emitted, no state moves
 
     DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pa->p.device));
+    QPSK_HIP_TRY(hipSetDevice(pa->device));
     hipStream_t st = pa->stream;
     PathArgs a{};
     a.in = in;
@@ -342,28 +274,19 @@ int qpsk_path_apply_fmt(qpsk_path *pa, int32_t fmt_in, const void *in, int64_t s
     a.n = n_samples;
     a.state = pa->d_state;
     a.S = S;
-    if (lengths) {
-        // the kernels read the lengths the host checked
-        QPSK_HIP_TRY(hipMemcpyAsync(pa->d_len, lengths, S * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        a.lengths = pa->d_len;
-    }
-    const int64_t ipitch = (2 * n_call * ieb + 15) / 16 * 16, opitch = (2 * std::max<int64_t>(n_out_max, 1) * oeb + 15) / 16 * 16;
+    if ((rc = pa->upload_lengths(lengths, S, &a.lengths))) return rc;
     if (host) {
-        if ((rc = qpsk::alloc_status(pa->d_in.grow(static_cast<size_t>(S) * ipitch), kStaging))) return rc;
-        if ((rc = qpsk::alloc_status(pa->d_out.grow(static_cast<size_t>(S) * opitch), kStaging))) return rc;
-        QPSK_HIP_TRY(hipMemcpy2DAsync(pa->d_in, ipitch, in, stride_in * ieb, 2 * n_call * ieb, S, hipMemcpyHostToDevice, st));
+        if ((rc = pa->stage_out(kStaging, oeb, std::max<int64_t>(n_out_max, 1), S, &a.out, &a.out_stride)) ||
+            (rc = pa->stage_in(kStaging, in, stride_in, ieb, n_call, S, &a.in, &a.in_stride)))
+            return rc;
         // what lies past a row's emitted length comes back as it was
         if (n_out_max > 0)
-            QPSK_HIP_TRY(hipMemcpy2DAsync(pa->d_out, opitch, out, stride_out * oeb, 2 * n_out_max * oeb, S,
+            QPSK_HIP_TRY(hipMemcpy2DAsync(a.out, a.out_stride * oeb, out, stride_out * oeb, 2 * n_out_max * oeb, S,
                                           hipMemcpyHostToDevice, st));
-        a.in = pa->d_in;
-        a.out = pa->d_out;
-        a.in_stride = ipitch / ieb;
-        a.out_stride = opitch / oeb;
     }
     a.in_pair = pair_rows(fmt_in, a.in, a.in_stride);
     a.out_pair = pair_rows(fmt_out, a.out, a.out_stride);
-    a.in_wide = wide_rows(fmt_in, a.in, a.in_stride);
+    a.in_wide = qpsk::wide_rows(fmt_in, a.in, a.in_stride);
     if (n_out_max > 0) {
         const unsigned tiles = static_cast<unsigned>((n_out_max + kTile - 1) / kTile);
         const dim3 grid(tiles, std::min(S, kGridY), (S + kGridY - 1) / kGridY);
@@ -374,12 +297,9 @@ int qpsk_path_apply_fmt(qpsk_path *pa, int32_t fmt_in, const void *in, int64_t s
     hipLaunchKernelGGL(path_state_kernel, dim3(static_cast<unsigned>((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        st, a);
     QPSK_HIP_TRY(hipGetLastError());
-    for (int s = 0; s < S; ++s) {
-        pa->host[s].in_pos += lengths ? lengths[s] : n_samples;
-        pa->host[s].out_pos += cnt[s];
-    }
+    qpsk::advance_rows(pa->host.data(), S, n_samples, lengths, cnt.data());
     if (host && n_out_max > 0)
-        QPSK_HIP_TRY(hipMemcpy2DAsync(out, stride_out * oeb, pa->d_out, opitch, 2 * n_out_max * oeb, S,
+        QPSK_HIP_TRY(hipMemcpy2DAsync(out, stride_out * oeb, a.out, a.out_stride * oeb, 2 * n_out_max * oeb, S,
                                       hipMemcpyDeviceToHost, st));
     if (host || lengths) QPSK_HIP_TRY(hipStreamSynchronize(st));
     return QPSK_OK;
@@ -388,24 +308,16 @@ int qpsk_path_apply_fmt(qpsk_path *pa, int32_t fmt_in, const void *in, int64_t s
 int qpsk_path_get_state(qpsk_path *pa, void *host_buf, int64_t buf_bytes) {
     if (!pa || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
     const int64_t want = static_cast<int64_t>(pa->S) * static_cast<int64_t>(sizeof(PathState));
-    if (buf_bytes != want)
-        return fail(QPSK_ERR_ARGUMENT, "path state length does not match this handle (" + std::to_string(buf_bytes) +
-                                           " vs " + std::to_string(want) + " bytes)");
-    DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pa->p.device));
-    QPSK_HIP_TRY(hipMemcpyAsync(host_buf, pa->d_state, want, hipMemcpyDeviceToHost, pa->stream));
-    QPSK_HIP_TRY(hipStreamSynchronize(pa->stream));
-    return QPSK_OK;
+    int rc;
+    if ((rc = qpsk::check_state_bytes("path", buf_bytes, want))) return rc;
+    return pa->state_out(host_buf, pa->d_state, want);
 }
 
 int qpsk_path_set_state(qpsk_path *pa, const void *host_buf, int64_t buf_bytes) {
     if (!pa) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     int rc;
-    if ((rc = qpsk_path_state_check(pa->S, host_buf, buf_bytes))) return rc;
-    DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pa->p.device));
-    QPSK_HIP_TRY(hipMemcpyAsync(pa->d_state, host_buf, buf_bytes, hipMemcpyHostToDevice, pa->stream));
-    QPSK_HIP_TRY(hipStreamSynchronize(pa->stream));
+    if ((rc = qpsk_path_state_check(pa->S, host_buf, buf_bytes)) || (rc = pa->state_in(pa->d_state, host_buf, buf_bytes)))
+        return rc;
     std::memcpy(pa->host.data(), host_buf, buf_bytes);
     return QPSK_OK;
 }
@@ -415,7 +327,7 @@ int qpsk_path_reset_streams(qpsk_path *pa, const int32_t *streams, int32_t n) {
     int rc;
     if ((rc = qpsk_stream_list_check(pa->S, streams, n))) return rc;
     DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pa->p.device));
+    QPSK_HIP_TRY(hipSetDevice(pa->device));
     std::vector<PathState> st(n);   // lives until the synchronise below
     for (int32_t k = 0; k < n; ++k) {
         st[k] = qpsk::path_state_new(pa->p, streams[k]);

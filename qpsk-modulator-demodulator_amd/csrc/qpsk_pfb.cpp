@@ -15,6 +15,7 @@
 
 #include "qpsk_demod.h"
 #include "qpsk_internal.h"
+#include "qpsk_row_call.h"
 
 namespace qpsk {
 namespace {
@@ -113,35 +114,17 @@ void pfb_twiddles(int M, float *w) {
 int pfb_check_call(const qpsk_pfb_params &p, const PfbHead *heads, int32_t B, int64_t stride_in, int64_t stride_out,
                    int64_t out_cap, int64_t n_samples, const int64_t *lengths, int64_t *n_out, int64_t *n_call,
                    int64_t *n_out_max) {
-    if (!n_out) return fail(QPSK_ERR_ARGUMENT_NULL, "n_out is null");
     if (n_samples < 0) return fail(QPSK_ERR_ARGUMENT, "n_samples must not be negative");
     if (out_cap < 0) return fail(QPSK_ERR_ARGUMENT, "out_cap must not be negative");
     if (n_samples > kPfbMaxPos || out_cap > kPfbMaxPos) return fail(QPSK_ERR_ARGUMENT, "stride too small");
-    *n_call = lengths ? 0 : n_samples;
-    if (lengths)
-        for (int b = 0; b < B; ++b) {
-            if (lengths[b] < 0 || lengths[b] > n_samples)
-                return fail(QPSK_ERR_ARGUMENT, "lengths[" + std::to_string(b) + "] = " + std::to_string(lengths[b]) +
-                                                   " outside [0, n_samples]");
-            *n_call = lengths[b] > *n_call ? lengths[b] : *n_call;
-        }
+    int rc;
+    if ((rc = check_lengths(B, n_samples, lengths, n_call))) return rc;
     if (*n_call > 0 && (stride_in < 2 * n_samples || stride_out < 2 * out_cap))
         return fail(QPSK_ERR_ARGUMENT, "stride too small");
-    // the counts, into a copy first: a rejected call leaves n_out as it was
-    std::vector<int64_t> cnt(B);
-    *n_out_max = 0;
-    for (int b = 0; b < B; ++b) {
-        const int64_t len = lengths ? lengths[b] : n_samples;
-        if (len > kPfbMaxPos - heads[b].in_pos)
-            return fail(QPSK_ERR_ARGUMENT, "band " + std::to_string(b) + " would pass position 2^50");
-        cnt[b] = pfb_count(p.channels, heads[b].out_pos, heads[b].in_pos + len);
-        if (cnt[b] > out_cap)
-            return fail(QPSK_ERR_ARGUMENT, "band " + std::to_string(b) + " would emit " + std::to_string(cnt[b]) +
-                                               " frames, out_cap is " + std::to_string(out_cap));
-        *n_out_max = cnt[b] > *n_out_max ? cnt[b] : *n_out_max;
-    }
-    std::memcpy(n_out, cnt.data(), sizeof(int64_t) * B);
-    return QPSK_OK;
+    const int M = p.channels;
+    return check_counts(heads, B, n_samples, lengths, out_cap, kPfbMaxPos, "band", "frames",
+                        [M](const PfbHead &r, int64_t in_end) { return pfb_count(M, r.out_pos, in_end); }, n_out,
+                        n_out_max);
 }
 
 void pfb_apply_band(const qpsk_pfb_params &p, const float *h, const float *w, PfbHead &head, float *hist, const float *in,
@@ -266,10 +249,8 @@ int qpsk_pfb_state_check(const qpsk_pfb_params *p, int32_t n_bands, const void *
     int rc;
     if ((rc = pfb_check_params(p, n_bands))) return rc;
     if (!buf) return fail(QPSK_ERR_ARGUMENT_NULL, "pfb state buffer is null");
-    const int64_t each = pfb_state_bytes(p->channels, p->taps_per_branch), want = n_bands * each;
-    if (buf_bytes != want)
-        return fail(QPSK_ERR_ARGUMENT, "pfb state length does not match this handle (" + std::to_string(buf_bytes) +
-                                           " vs " + std::to_string(want) + " bytes)");
+    const int64_t each = pfb_state_bytes(p->channels, p->taps_per_branch);
+    if ((rc = check_state_bytes("pfb", buf_bytes, n_bands * each))) return rc;
     const char *rec = static_cast<const char *>(buf);
     for (int32_t b = 0; b < n_bands; ++b, rec += each)
         if ((rc = check_band(*p, b, rec))) return rc;
@@ -296,12 +277,10 @@ int qpsk_pfb_apply_host(const qpsk_pfb_params *p, const float *taps, void *state
         return rc;
     if (n_call > 0 && !in) return fail(QPSK_ERR_ARGUMENT_NULL, "in is null");
     if (n_out_max > 0 && !out) return fail(QPSK_ERR_ARGUMENT_NULL, "out is null");
-    if (n_call > 0 && n_out_max > 0) {
-        const uintptr_t ib = reinterpret_cast<uintptr_t>(in), ob = reinterpret_cast<uintptr_t>(out);
-        const uintptr_t ie = ib + sizeof(float) * ((n_bands - 1) * stride_in + 2 * n_samples);
-        const uintptr_t oe = ob + sizeof(float) * ((static_cast<int64_t>(n_bands) * M - 1) * stride_out + 2 * out_cap);
-        if (ib < oe && ob < ie) return fail(QPSK_ERR_ARGUMENT, "out must not overlap in");
-    }
+    if (n_call > 0 && n_out_max > 0 &&
+        rows_overlap(in, n_bands, stride_in, n_samples, sizeof(float), out, static_cast<int64_t>(n_bands) * M, stride_out,
+                     out_cap, sizeof(float)))
+        return fail(QPSK_ERR_ARGUMENT, "out must not overlap in");
     std::vector<float> h(L), w(M), hist(2 * static_cast<size_t>(L));
     if (taps) std::memcpy(h.data(), taps, sizeof(float) * L);
     else pfb_design(M, K, h.data());

@@ -47,18 +47,17 @@
 #include "qpsk_internal.h"
 #include "qpsk_pfb.h"
 #include "qpsk_quantise.h"
+#include "qpsk_row_call.h"
+#include "qpsk_row_handle.h"
 #include "qpsk_sample_rows.h"
 
-struct qpsk_pfb {
+struct qpsk_pfb : qpsk::RowHandle {
     qpsk_pfb_params p{};
     int B = 0, M = 0, K = 0, L = 0;
     int64_t each = 0;                        // bytes of one band's state
-    qpsk::Stream stream;                     // in front of the buffers, which go first
     qpsk::DevBuf<uint8_t> d_state;           // [B][64 + 8 L]
     qpsk::DevBuf<float> d_taps;              // [L]
     qpsk::DevBuf<float2> d_tw;               // [M / 2]
-    qpsk::DevBuf<int64_t> d_len;             // [B]: a call's checked lengths
-    qpsk::DevBuf<uint8_t> d_in, d_out;       // host calls: 16-byte-pitched rows
     std::vector<qpsk::PfbHead> host;         // [B]: the positions as the device will hold them behind the calls
                                              // queued so far
 };
@@ -73,6 +72,7 @@ using qpsk::load_sample;
 using qpsk::pair_rows;
 using qpsk::PfbC;
 using qpsk::PfbHead;
+using qpsk::row_length;
 
 constexpr int kThreads = 256;
 constexpr int kPer = kPfbTileElems / kThreads;                         // elements a thread
@@ -96,51 +96,6 @@ struct PfbArgs {
     const float2 *tw;
     int B, M, K, bits;
 };
-
-__device__ __forceinline__ int64_t row_length(const PfbArgs &a, int b) { return a.lengths ? a.lengths[b] : a.n; }
-
-// xs[m] = x at index j0 + m of the call's row, m in [0, xlen): the row, the
-// history in front of it, +0 before the history and behind the row
-__device__ __forceinline__ void stage_window(float2 *xs, int64_t j0, int xlen, int64_t len, const char *irow,
-                                             const float (*hist)[2], int L, const PfbArgs &a, int tid) {
-    if (a.in_wide) {
-        const int64_t j1 = j0 + xlen < len ? j0 + xlen : len;   // the row's part of the window: [jr0, j1)
-        const int64_t jr0 = j0 > 0 ? j0 : 0;
-        for (int m = tid; m < xlen; m += kThreads) {
-            const int64_t j = j0 + m;
-            if (j >= 0 && j < len) continue;
-            const int64_t h = L + j;
-            xs[m] = j < 0 && h >= 0 ? make_float2(hist[h][0], hist[h][1]) : make_float2(0.0f, 0.0f);
-        }
-        const int64_t in_eb = qpsk::fmt_elem_bytes(a.fmt_in);
-        const int V = static_cast<int>(16 / (2 * in_eb));   // samples in 16 bytes: 2, 4 or 8
-        const int64_t c_hi = (j1 + V - 1) / V;
-        for (int64_t c = jr0 / V + tid; c < c_hi; c += kThreads) {
-            const int64_t jb = c * V;
-            if (jb + V <= len) {
-                // 16 bytes of the row in registers, read sample by sample as a row is
-                const uint4 w = *reinterpret_cast<const uint4 *>(irow + jb * 2 * in_eb);
-#pragma unroll
-                for (int v = 0; v < 8; ++v) {
-                    const int64_t j = jb + v;
-                    if (v < V && j >= jr0 && j < j1) xs[j - j0] = load_sample(&w, a.fmt_in, 1, v, a.scale_in);
-                }
-            } else {
-                for (int v = 0; v < V; ++v) {
-                    const int64_t j = jb + v;
-                    if (j >= jr0 && j < j1) xs[j - j0] = load_sample(irow, a.fmt_in, a.in_pair, j, a.scale_in);
-                }
-            }
-        }
-    } else {
-        for (int m = tid; m < xlen; m += kThreads) {
-            const int64_t j = j0 + m;
-            const int64_t h = L + j;
-            if (j >= 0 && j < len) xs[m] = load_sample(irow, a.fmt_in, a.in_pair, j, a.scale_in);
-            else xs[m] = j < 0 && h >= 0 ? make_float2(hist[h][0], hist[h][1]) : make_float2(0.0f, 0.0f);
-        }
-    }
-}
 
 __global__ __launch_bounds__(kThreads) void pfb_kernel(PfbArgs a) {
     __shared__ float2 lds[kLds];
@@ -168,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void pfb_kernel(PfbArgs a) {
     for (int k = 0; k < K; ++k) {
         // lds[0] is x at (m0 - 2k - 2) D + 1 = pfb_index(M, m0, M - 1, k)
         const int64_t j0 = qpsk::pfb_index(M, m0, M - 1, k) - in_pos;
-        stage_window(lds, j0, xlen, len, irow, hist, L, a, tid);
+        qpsk::stage_window<kThreads>(lds, j0, xlen, len, irow, hist, L, a, tid);
         __syncthreads();
         const float *hk = a.taps + k * M;
 #pragma unroll
@@ -256,10 +211,6 @@ __global__ __launch_bounds__(kThreads) void pfb_state_kernel(PfbArgs a) {
 // what a failed grow of a staging buffer names (alloc_status)
 constexpr const char *kStaging = "pfb staging";
 
-bool wide_rows(int fmt, const void *rows, int64_t stride) {
-    return reinterpret_cast<uintptr_t>(rows) % 16 == 0 && (stride * qpsk::fmt_elem_bytes(fmt)) % 16 == 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -282,8 +233,7 @@ int qpsk_pfb_create(const qpsk_pfb_params *p, int32_t n_bands, qpsk_pfb **out) {
     qpsk::pfb_design(pf->M, pf->K, h.data());
     qpsk::pfb_twiddles(pf->M, w.data());
     const size_t state_bytes = static_cast<size_t>(n_bands) * pf->each;
-    if (hipSetDevice(p->device) != hipSuccess || pf->stream.create(hipStreamNonBlocking) != hipSuccess ||
-        pf->d_state.alloc(state_bytes) != hipSuccess || pf->d_len.alloc(n_bands) != hipSuccess ||
+    if (pf->open(p->device, n_bands) != hipSuccess || pf->d_state.alloc(state_bytes) != hipSuccess ||
         pf->d_taps.alloc(pf->L) != hipSuccess || pf->d_tw.alloc(pf->M / 2) != hipSuccess ||
         hipMemset(pf->d_state, 0, state_bytes) != hipSuccess ||
         hipMemcpy(pf->d_taps, h.data(), sizeof(float) * pf->L, hipMemcpyHostToDevice) != hipSuccess ||
@@ -295,22 +245,11 @@ int qpsk_pfb_create(const qpsk_pfb_params *p, int32_t n_bands, qpsk_pfb **out) {
     return QPSK_OK;
 }
 
-int qpsk_pfb_destroy(qpsk_pfb *pf) {
-    if (!pf) return QPSK_OK;
-    DeviceGuard guard;
-    (void)hipSetDevice(pf->p.device);
-    if (pf->stream) (void)hipStreamSynchronize(pf->stream);
-    delete pf;
-    return QPSK_OK;
-}
+int qpsk_pfb_destroy(qpsk_pfb *pf) { return qpsk::row_handle_destroy(pf); }
 
 int qpsk_pfb_set_stream(qpsk_pfb *pf, void *hip_stream) {
     if (!pf) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pf->p.device));
-    QPSK_HIP_TRY(hipStreamSynchronize(pf->stream));
-    QPSK_HIP_TRY(pf->stream.rebind(hip_stream));
-    return QPSK_OK;
+    return pf->set_stream(hip_stream);
 }
 
 int qpsk_pfb_set_taps(qpsk_pfb *pf, const float *taps, int64_t n_taps) {
@@ -318,7 +257,7 @@ int qpsk_pfb_set_taps(qpsk_pfb *pf, const float *taps, int64_t n_taps) {
     int rc;
     if ((rc = qpsk::pfb_check_taps(taps, n_taps, pf->L))) return rc;
     DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pf->p.device));
+    QPSK_HIP_TRY(hipSetDevice(pf->device));
     QPSK_HIP_TRY(hipMemcpyAsync(pf->d_taps, taps, sizeof(float) * pf->L, hipMemcpyHostToDevice, pf->stream));
     QPSK_HIP_TRY(hipStreamSynchronize(pf->stream));
     return QPSK_OK;
@@ -328,16 +267,15 @@ int qpsk_pfb_apply_fmt(qpsk_pfb *pf, int32_t fmt_in, const void *in, int64_t str
                        int64_t stride_out, int64_t out_cap, int64_t n_samples, const int64_t *lengths, int64_t *n_out,
                        int32_t mem) {
     if (!pf) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
-    if (!qpsk::fmt_known(fmt_in)) return fail(QPSK_ERR_ARGUMENT, "unknown sample format");
-    if (mem != QPSK_MEM_HOST && mem != QPSK_MEM_DEVICE) return fail(QPSK_ERR_ARGUMENT, "unknown mem");
-    if (fmt_in != QPSK_FMT_CF32 && !qpsk::quant_scale_ok(scale_in))
-        return fail(QPSK_ERR_OUT_OF_RANGE, "scale_in must be finite and > 0");
+    int rc;
+    // the output is CF32 rows at the handle's gain: nothing of it for a caller to get wrong
+    if ((rc = qpsk::check_row_formats("channeliser", fmt_in, scale_in, QPSK_FMT_CF32, QPSK_MOD_NORM_FIXED, 1.0f, mem)))
+        return rc;
     if (!n_out) return fail(QPSK_ERR_ARGUMENT_NULL, "n_out is null");
     const int B = pf->B, M = pf->M;
     const int64_t rows_out = static_cast<int64_t>(B) * M;
     const bool host = mem == QPSK_MEM_HOST;
     const int64_t ieb = qpsk::fmt_elem_bytes(fmt_in), oeb = sizeof(float);
-    int rc;
     int64_t n_call, n_out_max;
     std::vector<int64_t> cnt(B);
     if ((rc = qpsk::pfb_check_call(pf->p, pf->host.data(), B, stride_in, stride_out, out_cap, n_samples, lengths, cnt.data(),
@@ -348,18 +286,14 @@ int qpsk_pfb_apply_fmt(qpsk_pfb *pf, int32_t fmt_in, const void *in, int64_t str
         if (!host && ((rc = check_device_rows("input", fmt_in, in, stride_in)) ||
                       (out && (rc = check_device_rows("output", QPSK_FMT_CF32, out, stride_out)))))
             return rc;
-        if (out) {
-            const uintptr_t ib = reinterpret_cast<uintptr_t>(in), ob = reinterpret_cast<uintptr_t>(out);
-            const uintptr_t ie = ib + static_cast<uintptr_t>(((B - 1) * stride_in + 2 * n_samples) * ieb);
-            const uintptr_t oe = ob + static_cast<uintptr_t>(((rows_out - 1) * stride_out + 2 * out_cap) * oeb);
-            if (ib < oe && ob < ie) return fail(QPSK_ERR_ARGUMENT, "out must not overlap in");
-        }
+        if (out && qpsk::rows_overlap(in, B, stride_in, n_samples, ieb, out, rows_out, stride_out, out_cap, oeb))
+            return fail(QPSK_ERR_ARGUMENT, "out must not overlap in");
     }
     std::memcpy(n_out, cnt.data(), sizeof(int64_t) * B);
     if (n_call == 0) return QPSK_OK;   // nothing taken: nothing emitted, no state moves
 
     DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pf->p.device));
+    QPSK_HIP_TRY(hipSetDevice(pf->device));
     hipStream_t st = pf->stream;
     PfbArgs a{};
     a.in = in;
@@ -378,24 +312,13 @@ int qpsk_pfb_apply_fmt(qpsk_pfb *pf, int32_t fmt_in, const void *in, int64_t str
     a.M = M;
     a.K = pf->K;
     a.bits = qpsk::pfb_log2(M);
-    if (lengths) {
-        // the kernels read the lengths the host checked
-        QPSK_HIP_TRY(hipMemcpyAsync(pf->d_len, lengths, B * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        a.lengths = pf->d_len;
-    }
-    const int64_t ipitch = (2 * n_call * ieb + 15) / 16 * 16, opitch = (2 * std::max<int64_t>(n_out_max, 1) * oeb + 15) / 16 * 16;
-    if (host) {
-        if ((rc = qpsk::alloc_status(pf->d_in.grow(static_cast<size_t>(B) * ipitch), kStaging))) return rc;
-        if ((rc = qpsk::alloc_status(pf->d_out.grow(static_cast<size_t>(rows_out) * opitch), kStaging))) return rc;
-        QPSK_HIP_TRY(hipMemcpy2DAsync(pf->d_in, ipitch, in, stride_in * ieb, 2 * n_call * ieb, B, hipMemcpyHostToDevice, st));
-        a.in = pf->d_in;
-        a.out = reinterpret_cast<float *>(pf->d_out.get());
-        a.in_stride = ipitch / ieb;
-        a.out_stride = opitch / oeb;
-    }
+    if ((rc = pf->upload_lengths(lengths, B, &a.lengths))) return rc;
+    if (host && ((rc = pf->stage_out(kStaging, oeb, std::max<int64_t>(n_out_max, 1), rows_out, &a.out, &a.out_stride)) ||
+                 (rc = pf->stage_in(kStaging, in, stride_in, ieb, n_call, B, &a.in, &a.in_stride))))
+        return rc;
     a.in_pair = pair_rows(fmt_in, a.in, a.in_stride);
     a.out_pair = pair_rows(QPSK_FMT_CF32, a.out, a.out_stride);
-    a.in_wide = wide_rows(fmt_in, a.in, a.in_stride);
+    a.in_wide = qpsk::wide_rows(fmt_in, a.in, a.in_stride);
     if (n_out_max > 0) {
         const int F = qpsk::pfb_tile_frames(M);
         const dim3 grid(static_cast<unsigned>((n_out_max + F - 1) / F), B);
@@ -404,16 +327,13 @@ int qpsk_pfb_apply_fmt(qpsk_pfb *pf, int32_t fmt_in, const void *in, int64_t str
     }
     hipLaunchKernelGGL(pfb_state_kernel, dim3(B), dim3(kThreads), 0, st, a);
     QPSK_HIP_TRY(hipGetLastError());
-    for (int b = 0; b < B; ++b) {
-        pf->host[b].in_pos += lengths ? lengths[b] : n_samples;
-        pf->host[b].out_pos += cnt[b];
-    }
+    qpsk::advance_rows(pf->host.data(), B, n_samples, lengths, cnt.data());
     if (host && n_out_max > 0) {
         // row by row what each band emitted: what lies past a row's count stays as it was
         for (int b = 0; b < B; ++b)
             if (cnt[b] > 0)
                 QPSK_HIP_TRY(hipMemcpy2DAsync(out + static_cast<int64_t>(b) * M * stride_out, stride_out * oeb,
-                                              pf->d_out.get() + static_cast<int64_t>(b) * M * opitch, opitch,
+                                              a.out + static_cast<int64_t>(b) * M * a.out_stride, a.out_stride * oeb,
                                               2 * cnt[b] * oeb, M, hipMemcpyDeviceToHost, st));
     }
     if (host || lengths) QPSK_HIP_TRY(hipStreamSynchronize(st));
@@ -422,25 +342,16 @@ int qpsk_pfb_apply_fmt(qpsk_pfb *pf, int32_t fmt_in, const void *in, int64_t str
 
 int qpsk_pfb_get_state(qpsk_pfb *pf, void *host_buf, int64_t buf_bytes) {
     if (!pf || !host_buf) return fail(QPSK_ERR_ARGUMENT_NULL, "null argument");
-    const int64_t want = pf->B * pf->each;
-    if (buf_bytes != want)
-        return fail(QPSK_ERR_ARGUMENT, "pfb state length does not match this handle (" + std::to_string(buf_bytes) +
-                                           " vs " + std::to_string(want) + " bytes)");
-    DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pf->p.device));
-    QPSK_HIP_TRY(hipMemcpyAsync(host_buf, pf->d_state, want, hipMemcpyDeviceToHost, pf->stream));
-    QPSK_HIP_TRY(hipStreamSynchronize(pf->stream));
-    return QPSK_OK;
+    int rc;
+    if ((rc = qpsk::check_state_bytes("pfb", buf_bytes, pf->B * pf->each))) return rc;
+    return pf->state_out(host_buf, pf->d_state, buf_bytes);
 }
 
 int qpsk_pfb_set_state(qpsk_pfb *pf, const void *host_buf, int64_t buf_bytes) {
     if (!pf) return fail(QPSK_ERR_ARGUMENT_NULL, "null handle");
     int rc;
-    if ((rc = qpsk_pfb_state_check(&pf->p, pf->B, host_buf, buf_bytes))) return rc;
-    DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pf->p.device));
-    QPSK_HIP_TRY(hipMemcpyAsync(pf->d_state, host_buf, buf_bytes, hipMemcpyHostToDevice, pf->stream));
-    QPSK_HIP_TRY(hipStreamSynchronize(pf->stream));
+    if ((rc = qpsk_pfb_state_check(&pf->p, pf->B, host_buf, buf_bytes)) || (rc = pf->state_in(pf->d_state, host_buf, buf_bytes)))
+        return rc;
     for (int b = 0; b < pf->B; ++b)
         std::memcpy(&pf->host[b], static_cast<const char *>(host_buf) + b * pf->each, sizeof(PfbHead));
     return QPSK_OK;
@@ -451,7 +362,7 @@ int qpsk_pfb_reset_bands(qpsk_pfb *pf, const int32_t *bands, int32_t n) {
     int rc;
     if ((rc = qpsk_stream_list_check(pf->B, bands, n))) return rc;
     DeviceGuard guard;
-    QPSK_HIP_TRY(hipSetDevice(pf->p.device));
+    QPSK_HIP_TRY(hipSetDevice(pf->device));
     for (int32_t k = 0; k < n; ++k)
         QPSK_HIP_TRY(hipMemsetAsync(pf->d_state.get() + bands[k] * pf->each, 0, pf->each, pf->stream));
     QPSK_HIP_TRY(hipStreamSynchronize(pf->stream));

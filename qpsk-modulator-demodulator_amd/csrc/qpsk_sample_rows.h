@@ -1,8 +1,10 @@
-// qpsk_sample_rows.h -- rows of samples of any QPSK_FMT_* between two kernels
-// of the test bench (the channel, qpsk_channel.hip, and the propagation path,
-// qpsk_path.hip): one sample read as the demodulator reads it, one float sample
-// stored as the modulator's quantiser stores it (qpsk_quantise.h), and what the
-// host asks of device rows before a kernel sees them.  HIP files only.
+// qpsk_sample_rows.h -- rows of samples of any QPSK_FMT_* in the kernels of the
+// test bench (the channel, qpsk_channel.hip, the propagation path,
+// qpsk_path.hip, and the polyphase channeliser, qpsk_pfb.hip): one sample read
+// as the demodulator reads it, one float sample stored as the modulator's
+// quantiser stores it (qpsk_quantise.h), a row's length, a window of a row and
+// its history staged into LDS, and what the host asks of device rows before a
+// kernel sees them.  HIP files only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -66,16 +68,59 @@ __device__ __forceinline__ void store_sample(void *row, int fmt, int pair, int64
     }
 }
 
-// the caller's current device, put back when a call returns
-struct DeviceGuard {
-    int prev = -1;
-    DeviceGuard() {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+// row s of a call whose kernel arguments are a (Args has lengths and n): its
+// checked length where the call gave lengths, else n
+template <typename Args>
+__device__ __forceinline__ int64_t row_length(const Args &a, int s) { return a.lengths ? a.lengths[s] : a.n; }
+
+// xs[m] = x at index j0 + m of the call's row, m in [0, xlen): the row (irow,
+// len samples), the L samples of history in front of it, +0 before the history
+// and behind the row.  Coalesced: 16 bytes a lane where the rows are 16-byte
+// aligned and pitched (a.in_wide), else a sample a lane.  Every one of the
+// workgroup's kThreads threads calls it.  Args is the kernel's argument block,
+// with the input row's fmt_in, scale_in, in_pair and in_wide.
+template <int kThreads, typename Args>
+__device__ __forceinline__ void stage_window(float2 *xs, int64_t j0, int xlen, int64_t len, const char *irow,
+                                             const float (*hist)[2], int L, const Args &a, int tid) {
+    if (a.in_wide) {
+        const int64_t j1 = j0 + xlen < len ? j0 + xlen : len;   // the row's part of the window: [jr0, j1)
+        const int64_t jr0 = j0 > 0 ? j0 : 0;
+        // what precedes the row, and (never, in a checked state) what follows it
+        for (int m = tid; m < xlen; m += kThreads) {
+            const int64_t j = j0 + m;
+            if (j >= 0 && j < len) continue;
+            const int64_t h = L + j;
+            xs[m] = j < 0 && h >= 0 ? make_float2(hist[h][0], hist[h][1]) : make_float2(0.0f, 0.0f);
+        }
+        const int64_t eb = qpsk::fmt_elem_bytes(a.fmt_in);
+        const int V = static_cast<int>(16 / (2 * eb));   // samples in 16 bytes: 2, 4 or 8
+        const int64_t c_hi = (j1 + V - 1) / V;
+        for (int64_t c = jr0 / V + tid; c < c_hi; c += kThreads) {
+            const int64_t jb = c * V;
+            if (jb + V <= len) {
+                // 16 bytes of the row in registers, read sample by sample as a row is
+                const uint4 w = *reinterpret_cast<const uint4 *>(irow + jb * 2 * eb);
+#pragma unroll
+                for (int v = 0; v < 8; ++v) {
+                    const int64_t j = jb + v;
+                    if (v < V && j >= jr0 && j < j1) xs[j - j0] = load_sample(&w, a.fmt_in, 1, v, a.scale_in);
+                }
+            } else {
+                for (int v = 0; v < V; ++v) {
+                    const int64_t j = jb + v;
+                    if (j >= jr0 && j < j1) xs[j - j0] = load_sample(irow, a.fmt_in, a.in_pair, j, a.scale_in);
+                }
+            }
+        }
+    } else {
+        for (int m = tid; m < xlen; m += kThreads) {
+            const int64_t j = j0 + m;
+            const int64_t h = L + j;
+            if (j >= 0 && j < len) xs[m] = load_sample(irow, a.fmt_in, a.in_pair, j, a.scale_in);
+            else xs[m] = j < 0 && h >= 0 ? make_float2(hist[h][0], hist[h][1]) : make_float2(0.0f, 0.0f);
+        }
     }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+}
 
 // what device rows of fmt must satisfy (qpsk_demod_process_fmt's rules)
 inline int check_device_rows(const char *what, int fmt, const void *rows, int64_t stride) {
@@ -90,6 +135,11 @@ inline int check_device_rows(const char *what, int fmt, const void *rows, int64_
 // CF32 rows 8-byte aligned: one access a sample
 inline bool pair_rows(int fmt, const void *rows, int64_t stride) {
     return fmt != QPSK_FMT_CF32 || (reinterpret_cast<uintptr_t>(rows) % 8 == 0 && stride % 2 == 0);
+}
+
+// rows 16-byte aligned and pitched: stage_window reads 16 bytes a lane
+inline bool wide_rows(int fmt, const void *rows, int64_t stride) {
+    return reinterpret_cast<uintptr_t>(rows) % 16 == 0 && (stride * qpsk::fmt_elem_bytes(fmt)) % 16 == 0;
 }
 
 }  // namespace qpsk

@@ -1825,23 +1825,57 @@ def channel_state_check(p: ChannelParams, n_streams: int, blob):
     _check(lib().qpsk_channel_state_check(C.byref(p), int(n_streams), b, len(b)))
 
 
-class Channel:
-    """The reference test bench's channel on S streams (qpsk_channel_*): every
-    sample times txNCO.NextSample() * conj(rxNCO.NextSample())
-    (testAtDataLevel.cs:39-42), optionally with GenerateIqNoise's samples
-    added first (testFullDemodChain.cs:73).  Rows of any format in, rows of
-    any format out, host or device memory; the state carries over calls."""
+def _scales(tag_in, tag_out, scale_in, scale_out):
+    si = _CHANNEL_SCALE_IN[tag_in] if scale_in is None else scale_in
+    so = _CHANNEL_SCALE_OUT[tag_out] if scale_out is None else scale_out
+    return C.c_float(float(np.float32(si))), C.c_float(float(np.float32(so)))
 
-    def __init__(self, n_streams: int, p: ChannelParams | None = None, **fields):
-        self.p = p if p is not None else channel_params(**fields)
-        self.n_streams = int(n_streams)
+
+def _lengths(lengths, S):
+    if lengths is None:
+        return None, None
+    ln = np.ascontiguousarray(lengths, dtype=np.int64)
+    if ln.shape != (S,):
+        raise ValueError("lengths must hold one count a stream")
+    return ln, ln.ctypes.data_as(_i64p)
+
+
+def _check_host_rows(a, n_rows, dtype, must):
+    """What a host-memory call asks of an array: [n_rows, k] of dtype, a row's
+    elements side by side.  must: the text up to " with contiguous rows"."""
+    if a.dtype != dtype or a.ndim != 2 or a.shape[0] != n_rows or (a.shape[1] > 1 and a.strides[1] != a.itemsize):
+        raise ValueError(f"{must} with contiguous rows")
+
+
+def _check_device_rows(t, n_rows, need, fmt, what, rows_word="n_streams"):
+    """What a device-memory call asks of a tensor: [n_rows, >= need] of fmt's
+    element type on the device, a row's elements side by side."""
+    if (not t.is_cuda or t.dtype != _torch_dtype(fmt) or t.dim() != 2 or t.shape[0] != n_rows or
+            (t.shape[1] > 1 and t.stride(1) != 1) or t.shape[1] < need):
+        raise ValueError(f"{what} must be a contiguous-row [{rows_word}, >= 2 n] device tensor of its format")
+
+
+class _RowStage:
+    """What Channel, Path and Channeliser share: the handle's life, its stream,
+    its state and the order of a device-memory call.  A subclass names the
+    prefix of its qpsk_* functions, creates its handle with _create, and says
+    how many bytes its state takes (_state_bytes)."""
+
+    _PREFIX = ""
+    _h = None
+    _bound = False
+
+    def _fn(self, name):
+        return getattr(lib(), f"qpsk_{self._PREFIX}_{name}")
+
+    def _create(self, n_rows):
         h = C.c_void_p()
-        _check(lib().qpsk_channel_create(C.byref(self.p), self.n_streams, C.byref(h)))
+        _check(self._fn("create")(C.byref(self.p), n_rows, C.byref(h)))
         self._h = h
 
     def close(self):
-        if getattr(self, "_h", None):
-            lib().qpsk_channel_destroy(self._h)
+        if self._h:
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -1853,23 +1887,54 @@ class Channel:
     def set_stream(self, hip_stream_ptr: int | None):
         """Order the handle's calls on a caller's stream (torch's); None goes
         back to the handle's own."""
-        _check(lib().qpsk_channel_set_stream(self._h, C.c_void_p(hip_stream_ptr or 0)))
+        _check(self._fn("set_stream")(self._h, C.c_void_p(hip_stream_ptr or 0)))
         self._bound = bool(hip_stream_ptr)
 
-    @staticmethod
-    def _scales(tag_in, tag_out, scale_in, scale_out):
-        si = _CHANNEL_SCALE_IN[tag_in] if scale_in is None else scale_in
-        so = _CHANNEL_SCALE_OUT[tag_out] if scale_out is None else scale_out
-        return C.c_float(float(np.float32(si))), C.c_float(float(np.float32(so)))
+    def sync(self):
+        """Wait for the calls queued on the handle (reads its state)."""
+        self.get_state()
 
-    @staticmethod
-    def _lengths(lengths, S):
-        if lengths is None:
-            return None, None
-        ln = np.ascontiguousarray(lengths, dtype=np.int64)
-        if ln.shape != (S,):
-            raise ValueError("lengths must hold one count a stream")
-        return ln, ln.ctypes.data_as(_i64p)
+    def get_state(self) -> bytes:
+        buf = C.create_string_buffer(self._state_bytes())
+        _check(self._fn("get_state")(self._h, buf, len(buf)))
+        return buf.raw
+
+    def set_state(self, blob):
+        b = bytes(blob)
+        _check(self._fn("set_state")(self._h, b, len(b)))
+
+    def _reset(self, what, rows):
+        a, n = _stream_list(rows)
+        _check(self._fn("reset_" + what)(self._h, a, n))
+
+    def _device_call(self, out_dev, call):
+        """call() on device tensors: the handle's own stream does not order
+        against torch's, so unless a stream is bound torch's is drained first
+        and the call is waited for."""
+        import torch
+        if not self._bound:
+            torch.cuda.current_stream(out_dev.device).synchronize()
+        _check(call())
+        if not self._bound:
+            self.sync()
+
+
+class Channel(_RowStage):
+    """The reference test bench's channel on S streams (qpsk_channel_*): every
+    sample times txNCO.NextSample() * conj(rxNCO.NextSample())
+    (testAtDataLevel.cs:39-42), optionally with GenerateIqNoise's samples
+    added first (testFullDemodChain.cs:73).  Rows of any format in, rows of
+    any format out, host or device memory; the state carries over calls."""
+
+    _PREFIX = "channel"
+
+    def __init__(self, n_streams: int, p: ChannelParams | None = None, **fields):
+        self.p = p if p is not None else channel_params(**fields)
+        self.n_streams = int(n_streams)
+        self._create(self.n_streams)
+
+    def _state_bytes(self):
+        return channel_state_size() * self.n_streams
 
     def apply(self, rows: np.ndarray, fmt="cf32", out_fmt=None, lengths=None, scale_in=None, scale_out=None,
               norm="fixed", out: np.ndarray | None = None, n: int | None = None) -> np.ndarray:
@@ -1878,15 +1943,13 @@ class Channel:
         for one format).  Default scales: full scale 1.0 both ways."""
         tag_in, dt_in, _ = _format(fmt)
         tag_out, dt_out, _ = _format(fmt if out_fmt is None else out_fmt)
-        if rows.dtype != dt_in or rows.ndim != 2 or rows.shape[0] != self.n_streams or rows.strides[1] != rows.itemsize:
-            raise ValueError(f"rows must be [n_streams, 2 n] of {np.dtype(dt_in).name} with contiguous rows")
+        _check_host_rows(rows, self.n_streams, dt_in, f"rows must be [n_streams, 2 n] of {np.dtype(dt_in).name}")
         n = rows.shape[1] // 2 if n is None else int(n)
         if out is None:
             out = np.zeros((self.n_streams, max(2 * n, 2)), dtype=dt_out)
-        if out.dtype != dt_out or out.ndim != 2 or out.shape[0] != self.n_streams or out.strides[1] != out.itemsize:
-            raise ValueError(f"out must be [n_streams, 2 n] of {np.dtype(dt_out).name} with contiguous rows")
-        keep, lp = self._lengths(lengths, self.n_streams)
-        si, so = self._scales(tag_in, tag_out, scale_in, scale_out)
+        _check_host_rows(out, self.n_streams, dt_out, f"out must be [n_streams, 2 n] of {np.dtype(dt_out).name}")
+        keep, lp = _lengths(lengths, self.n_streams)
+        si, so = _scales(tag_in, tag_out, scale_in, scale_out)
         _check(lib().qpsk_channel_apply_fmt(self._h, tag_in, rows.ctypes.data, rows.strides[0] // rows.itemsize, si,
                                             tag_out, _norm(norm), out.ctypes.data, out.strides[0] // out.itemsize, so,
                                             n, lp, MEM_HOST))
@@ -1898,46 +1961,24 @@ class Channel:
         of out_fmt (default: in place).  lengths is a host array.  Ordered on
         the handle's stream; without set_stream the caller's torch stream is
         drained first and the call is waited for."""
-        import torch
-        tag_in = _format(fmt)[0]
-        tag_out = _format(fmt if out_fmt is None else out_fmt)[0]
+        fo = fmt if out_fmt is None else out_fmt
+        tag_in, tag_out = _format(fmt)[0], _format(fo)[0]
         out_dev = in_dev if out_dev is None else out_dev
-        for t, f, what in ((in_dev, fmt, "in_dev"), (out_dev, fmt if out_fmt is None else out_fmt, "out_dev")):
-            if (not t.is_cuda or t.dtype != _torch_dtype(f) or t.dim() != 2 or t.shape[0] != self.n_streams or
-                    (t.shape[1] > 1 and t.stride(1) != 1) or t.shape[1] < 2 * n):
-                raise ValueError(f"{what} must be a contiguous-row [n_streams, >= 2 n] device tensor of its format")
-        keep, lp = self._lengths(lengths, self.n_streams)
-        si, so = self._scales(tag_in, tag_out, scale_in, scale_out)
-        bound = getattr(self, "_bound", False)
-        if not bound:   # the handle's own stream does not order against torch's
-            torch.cuda.current_stream(out_dev.device).synchronize()
-        _check(lib().qpsk_channel_apply_fmt(self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, tag_out,
-                                            _norm(norm), out_dev.data_ptr(), out_dev.stride(0), so, int(n), lp,
-                                            MEM_DEVICE))
-        if not bound:
-            self.sync()
+        _check_device_rows(in_dev, self.n_streams, 2 * n, fmt, "in_dev")
+        _check_device_rows(out_dev, self.n_streams, 2 * n, fo, "out_dev")
+        keep, lp = _lengths(lengths, self.n_streams)
+        si, so = _scales(tag_in, tag_out, scale_in, scale_out)
+        self._device_call(out_dev, lambda: lib().qpsk_channel_apply_fmt(
+            self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, tag_out, _norm(norm), out_dev.data_ptr(),
+            out_dev.stride(0), so, int(n), lp, MEM_DEVICE))
         return out_dev
-
-    def sync(self):
-        """Wait for the calls queued on the handle (reads its state)."""
-        self.get_state()
-
-    def get_state(self) -> bytes:
-        buf = C.create_string_buffer(channel_state_size() * self.n_streams)
-        _check(lib().qpsk_channel_get_state(self._h, buf, len(buf)))
-        return buf.raw
 
     def states(self, blob: bytes | None = None) -> np.ndarray:
         """The state as a CHANNEL_STATE_DTYPE array, one record a stream."""
         return np.frombuffer(self.get_state() if blob is None else blob, dtype=CHANNEL_STATE_DTYPE).copy()
 
-    def set_state(self, blob):
-        b = bytes(blob)
-        _check(lib().qpsk_channel_set_state(self._h, b, len(b)))
-
     def reset_streams(self, streams):
-        a, n = _stream_list(streams)
-        _check(lib().qpsk_channel_reset_streams(self._h, a, n))
+        self._reset("streams", streams)
 
 
 # the 256-byte record of a path stream's state
@@ -2002,50 +2043,35 @@ def path_apply_host(state, rows: np.ndarray, lengths=None, out: np.ndarray | Non
     raises and leaves out as it was."""
     st = C.create_string_buffer(bytes(state), len(bytes(state)))
     S = len(st) // path_state_size()
-    if rows.dtype != np.float32 or rows.ndim != 2 or rows.shape[0] != S or (rows.shape[1] > 1 and rows.strides[1] != 4):
-        raise ValueError("rows must be [n_streams, 2 n] float32 with contiguous rows")
+    _check_host_rows(rows, S, np.float32, "rows must be [n_streams, 2 n] float32")
     n = rows.shape[1] // 2 if n is None else int(n)
     if out is None:
         cap = n + n // 512 + 4 if out_cap is None else int(out_cap)
         out = np.zeros((S, max(2 * cap, 2)), np.float32)
     cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
-    keep, lp = Channel._lengths(lengths, S)
+    keep, lp = _lengths(lengths, S)
     n_out = np.zeros(S, np.int64)
     _check(lib().qpsk_path_apply_host(st, len(st), S, rows.ctypes.data, rows.strides[0] // 4, out.ctypes.data,
                                       out.strides[0] // 4, cap, n, lp, n_out.ctypes.data_as(_i64p)))
     return st.raw, out, n_out
 
 
-class Path:
+class Path(_RowStage):
     """The propagation path on S streams (qpsk_path_*): each stream's multipath
     taps, then a resampler onto the receiver's sample clock
     (MuellerMuller.CubicLagrange4 at p_k = tau + k r).  Rows of any format in,
     rows of any format out, host or device memory; a call emits what its
     inputs make computable and returns the counts."""
 
+    _PREFIX = "path"
+
     def __init__(self, n_streams: int, p: PathParams | None = None, **fields):
         self.p = p if p is not None else path_params(**fields)
         self.n_streams = int(n_streams)
-        h = C.c_void_p()
-        _check(lib().qpsk_path_create(C.byref(self.p), self.n_streams, C.byref(h)))
-        self._h = h
+        self._create(self.n_streams)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().qpsk_path_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, hip_stream_ptr: int | None):
-        """Order the handle's calls on a caller's stream (torch's); None goes
-        back to the handle's own."""
-        _check(lib().qpsk_path_set_stream(self._h, C.c_void_p(hip_stream_ptr or 0)))
-        self._bound = bool(hip_stream_ptr)
+    def _state_bytes(self):
+        return path_state_size() * self.n_streams
 
     def set_taps(self, taps, per_stream=False):
         """Complex taps [L] for all streams, or [S, L] with per_stream."""
@@ -2065,17 +2091,15 @@ class Path:
         out_cap]; what lies past a row's n_out stays as it was."""
         tag_in, dt_in, _ = _format(fmt)
         tag_out, dt_out, _ = _format(fmt if out_fmt is None else out_fmt)
-        if rows.dtype != dt_in or rows.ndim != 2 or rows.shape[0] != self.n_streams or rows.strides[1] != rows.itemsize:
-            raise ValueError(f"rows must be [n_streams, 2 n] of {np.dtype(dt_in).name} with contiguous rows")
+        _check_host_rows(rows, self.n_streams, dt_in, f"rows must be [n_streams, 2 n] of {np.dtype(dt_in).name}")
         n = rows.shape[1] // 2 if n is None else int(n)
         if out is None:
             out = np.zeros((self.n_streams, max(2 * (self.out_bound(n) if out_cap is None else int(out_cap)), 2)),
                            dtype=dt_out)
-        if out.dtype != dt_out or out.ndim != 2 or out.shape[0] != self.n_streams or out.strides[1] != out.itemsize:
-            raise ValueError(f"out must be [n_streams, 2 out_cap] of {np.dtype(dt_out).name} with contiguous rows")
+        _check_host_rows(out, self.n_streams, dt_out, f"out must be [n_streams, 2 out_cap] of {np.dtype(dt_out).name}")
         cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
-        keep, lp = Channel._lengths(lengths, self.n_streams)
-        si, so = Channel._scales(tag_in, tag_out, scale_in, scale_out)
+        keep, lp = _lengths(lengths, self.n_streams)
+        si, so = _scales(tag_in, tag_out, scale_in, scale_out)
         n_out = np.zeros(self.n_streams, np.int64)
         _check(lib().qpsk_path_apply_fmt(self._h, tag_in, rows.ctypes.data, rows.strides[0] // rows.itemsize, si,
                                          tag_out, _norm(norm), out.ctypes.data, out.strides[0] // out.itemsize, cap, so,
@@ -2089,48 +2113,26 @@ class Path:
         n_out, a host array, at once.  lengths is a host array.  Ordered on the
         handle's stream; without set_stream the caller's torch stream is
         drained first and the call is waited for."""
-        import torch
-        tag_in = _format(fmt)[0]
         fo = fmt if out_fmt is None else out_fmt
-        tag_out = _format(fo)[0]
+        tag_in, tag_out = _format(fmt)[0], _format(fo)[0]
         cap = out_dev.shape[1] // 2 if out_cap is None else int(out_cap)
-        for t, f, need, what in ((in_dev, fmt, 2 * n, "in_dev"), (out_dev, fo, 2 * cap, "out_dev")):
-            if (not t.is_cuda or t.dtype != _torch_dtype(f) or t.dim() != 2 or t.shape[0] != self.n_streams or
-                    (t.shape[1] > 1 and t.stride(1) != 1) or t.shape[1] < need):
-                raise ValueError(f"{what} must be a contiguous-row [n_streams, >= 2 n] device tensor of its format")
-        keep, lp = Channel._lengths(lengths, self.n_streams)
-        si, so = Channel._scales(tag_in, tag_out, scale_in, scale_out)
-        bound = getattr(self, "_bound", False)
-        if not bound:   # the handle's own stream does not order against torch's
-            torch.cuda.current_stream(out_dev.device).synchronize()
+        _check_device_rows(in_dev, self.n_streams, 2 * n, fmt, "in_dev")
+        _check_device_rows(out_dev, self.n_streams, 2 * cap, fo, "out_dev")
+        keep, lp = _lengths(lengths, self.n_streams)
+        si, so = _scales(tag_in, tag_out, scale_in, scale_out)
         n_out = np.zeros(self.n_streams, np.int64)
-        _check(lib().qpsk_path_apply_fmt(self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, tag_out,
-                                         _norm(norm), out_dev.data_ptr(), out_dev.stride(0), cap, so, int(n), lp,
-                                         n_out.ctypes.data_as(_i64p), MEM_DEVICE))
-        if not bound:
-            self.sync()
+        self._device_call(out_dev, lambda: lib().qpsk_path_apply_fmt(
+            self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, tag_out, _norm(norm), out_dev.data_ptr(),
+            out_dev.stride(0), cap, so, int(n), lp, n_out.ctypes.data_as(_i64p), MEM_DEVICE))
         return n_out
-
-    def sync(self):
-        """Wait for the calls queued on the handle (reads its state)."""
-        self.get_state()
-
-    def get_state(self) -> bytes:
-        buf = C.create_string_buffer(path_state_size() * self.n_streams)
-        _check(lib().qpsk_path_get_state(self._h, buf, len(buf)))
-        return buf.raw
 
     def states(self, blob: bytes | None = None) -> np.ndarray:
         """The state as a PATH_STATE_DTYPE array, one record a stream."""
         return np.frombuffer(self.get_state() if blob is None else blob, dtype=PATH_STATE_DTYPE).copy()
 
-    def set_state(self, blob):
-        b = bytes(blob)
-        _check(lib().qpsk_path_set_state(self._h, b, len(b)))
-
     def reset_streams(self, streams):
-        a, n = _stream_list(streams)
-        _check(lib().qpsk_path_reset_streams(self._h, a, n))
+        self._reset("streams", streams)
+
 
 PFB_STATE_HEAD = 64           # QPSK_PFB_STATE_HEAD
 PFB_MIN_CHANNELS, PFB_MAX_CHANNELS, PFB_MAX_BRANCH_TAPS, PFB_MAX_TAPS = 8, 4096, 16, 32768
@@ -2211,14 +2213,13 @@ def pfb_apply_host(p: PfbParams, state, rows: np.ndarray, lengths=None, out: np.
     out_cap], n_out); a refused call raises and leaves out as it was."""
     st = C.create_string_buffer(bytes(state), len(bytes(state)))
     B = len(st) // max(pfb_state_size(p), 1)
-    if rows.dtype != np.float32 or rows.ndim != 2 or rows.shape[0] != B or (rows.shape[1] > 1 and rows.strides[1] != 4):
-        raise ValueError("rows must be [n_bands, 2 n] float32 with contiguous rows")
+    _check_host_rows(rows, B, np.float32, "rows must be [n_bands, 2 n] float32")
     n = rows.shape[1] // 2 if n is None else int(n)
     if out is None:
         cap = pfb_out_bound(p.channels, n) if out_cap is None else int(out_cap)
         out = np.zeros((B * p.channels, max(2 * cap, 2)), np.float32)
     cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
-    keep, lp = Channel._lengths(lengths, B)
+    keep, lp = _lengths(lengths, B)
     t = None if taps is None else np.ascontiguousarray(taps, dtype=np.float32)
     n_out = np.zeros(B, np.int64)
     _check(lib().qpsk_pfb_apply_host(C.byref(p), None if t is None else t.ctypes.data, st, len(st), B, rows.ctypes.data,
@@ -2227,38 +2228,24 @@ def pfb_apply_host(p: PfbParams, state, rows: np.ndarray, lengths=None, out: np.
     return st.raw, out, n_out
 
 
-class Channeliser:
+class Channeliser(_RowStage):
     """The polyphase channeliser on n_bands wideband rows (qpsk_pfb_*): band b's
     M = channels output rows b M .. b M + M - 1 are the signals around c fs / M
     at rate 2 fs / M, CF32, ready for BatchDemodulator.  Rows of any format in,
     host or device memory; a call emits the frames its inputs make computable
     and returns the counts."""
 
+    _PREFIX = "pfb"
+
     def __init__(self, n_bands: int, p: PfbParams | None = None, **fields):
         self.p = p if p is not None else pfb_params(**fields)
         self.n_bands = int(n_bands)
         self.channels = int(self.p.channels)
         self.n_rows = self.n_bands * self.channels
-        h = C.c_void_p()
-        _check(lib().qpsk_pfb_create(C.byref(self.p), self.n_bands, C.byref(h)))
-        self._h = h
+        self._create(self.n_bands)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().qpsk_pfb_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, hip_stream_ptr: int | None):
-        """Order the handle's calls on a caller's stream (torch's); None goes
-        back to the handle's own."""
-        _check(lib().qpsk_pfb_set_stream(self._h, C.c_void_p(hip_stream_ptr or 0)))
-        self._bound = bool(hip_stream_ptr)
+    def _state_bytes(self):
+        return pfb_state_size(self.p) * self.n_bands
 
     def set_taps(self, taps):
         """Replace the prototype: M K real taps."""
@@ -2282,16 +2269,14 @@ class Channeliser:
         rows [n_bands M, 2 out_cap], n_out).  out: rows to write into; what
         lies past a row's n_out stays as it was."""
         tag_in, dt_in, _ = _format(fmt)
-        if rows.dtype != dt_in or rows.ndim != 2 or rows.shape[0] != self.n_bands or rows.strides[1] != rows.itemsize:
-            raise ValueError(f"rows must be [n_bands, 2 n] of {np.dtype(dt_in).name} with contiguous rows")
+        _check_host_rows(rows, self.n_bands, dt_in, f"rows must be [n_bands, 2 n] of {np.dtype(dt_in).name}")
         n = rows.shape[1] // 2 if n is None else int(n)
         if out is None:
             out = np.zeros((self.n_rows, max(2 * (self.out_bound(n) if out_cap is None else int(out_cap)), 2)), np.float32)
-        if out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != self.n_rows or out.strides[1] != 4:
-            raise ValueError("out must be [n_bands M, 2 out_cap] float32 with contiguous rows")
+        _check_host_rows(out, self.n_rows, np.float32, "out must be [n_bands M, 2 out_cap] float32")
         cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
-        keep, lp = Channel._lengths(lengths, self.n_bands)
-        si, _ = Channel._scales(tag_in, FMT_CF32, scale_in, None)
+        keep, lp = _lengths(lengths, self.n_bands)
+        si, _ = _scales(tag_in, FMT_CF32, scale_in, None)
         n_out = np.zeros(self.n_bands, np.int64)
         _check(lib().qpsk_pfb_apply_fmt(self._h, tag_in, rows.ctypes.data, rows.strides[0] // rows.itemsize, si,
                                         out.ctypes.data, out.strides[0] // 4, cap, n, lp, n_out.ctypes.data_as(_i64p),
@@ -2305,47 +2290,25 @@ class Channeliser:
         holds).  Returns n_out, a host array, at once.  lengths is a host
         array.  Ordered on the handle's stream; without set_stream the
         caller's torch stream is drained first and the call is waited for."""
-        import torch
         tag_in = _format(fmt)[0]
         cap = out_dev.shape[1] // 2 if out_cap is None else int(out_cap)
-        for t, f, rows, need, what in ((in_dev, fmt, self.n_bands, 2 * n, "in_dev"),
-                                       (out_dev, "cf32", self.n_rows, 2 * cap, "out_dev")):
-            if (not t.is_cuda or t.dtype != _torch_dtype(f) or t.dim() != 2 or t.shape[0] != rows or
-                    (t.shape[1] > 1 and t.stride(1) != 1) or t.shape[1] < need):
-                raise ValueError(f"{what} must be a contiguous-row [rows, >= 2 n] device tensor of its format")
-        keep, lp = Channel._lengths(lengths, self.n_bands)
-        si, _ = Channel._scales(tag_in, FMT_CF32, scale_in, None)
-        bound = getattr(self, "_bound", False)
-        if not bound:   # the handle's own stream does not order against torch's
-            torch.cuda.current_stream(out_dev.device).synchronize()
+        _check_device_rows(in_dev, self.n_bands, 2 * n, fmt, "in_dev", "rows")
+        _check_device_rows(out_dev, self.n_rows, 2 * cap, "cf32", "out_dev", "rows")
+        keep, lp = _lengths(lengths, self.n_bands)
+        si, _ = _scales(tag_in, FMT_CF32, scale_in, None)
         n_out = np.zeros(self.n_bands, np.int64)
-        _check(lib().qpsk_pfb_apply_fmt(self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, out_dev.data_ptr(),
-                                        out_dev.stride(0), cap, int(n), lp, n_out.ctypes.data_as(_i64p), MEM_DEVICE))
-        if not bound:
-            self.sync()
+        self._device_call(out_dev, lambda: lib().qpsk_pfb_apply_fmt(
+            self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, out_dev.data_ptr(), out_dev.stride(0), cap, int(n),
+            lp, n_out.ctypes.data_as(_i64p), MEM_DEVICE))
         return n_out
-
-    def sync(self):
-        """Wait for the calls queued on the handle (reads its state)."""
-        self.get_state()
-
-    def get_state(self) -> bytes:
-        buf = C.create_string_buffer(pfb_state_size(self.p) * self.n_bands)
-        _check(lib().qpsk_pfb_get_state(self._h, buf, len(buf)))
-        return buf.raw
 
     def states(self, blob: bytes | None = None) -> np.ndarray:
         """The state as a pfb_state_dtype array, one record a band."""
         dt = pfb_state_dtype(self.channels, self.p.taps_per_branch)
         return np.frombuffer(self.get_state() if blob is None else blob, dtype=dt).copy()
 
-    def set_state(self, blob):
-        b = bytes(blob)
-        _check(lib().qpsk_pfb_set_state(self._h, b, len(b)))
-
     def reset_bands(self, bands):
-        a, n = _stream_list(bands)
-        _check(lib().qpsk_pfb_reset_bands(self._h, a, n))
+        self._reset("bands", bands)
 
 
 def _norm(norm):

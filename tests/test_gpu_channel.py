@@ -398,6 +398,60 @@ def test_state_after_every_call_and_restore_into_a_fresh_handle(Q, dev):
         assert_calls_equal(cont, got[k + 1:], f"restored after call {k}")
 
 
+def assert_state_after(ch, fs, S, n):
+    """The handle's state is the Python model's after n samples a stream."""
+    st = ch.states()
+    for s, (tx, rx) in enumerate(py_states(fs, S)):
+        for _ in range(n):
+            tx.next()
+            rx.next()
+        assert tuple(st["tx"][s]) == tx.fields() and tuple(st["rx"][s]) == rx.fields(), s
+        assert st["pos"][s] == n
+
+
+def test_host_rows_whose_staging_grows_and_is_reused(Q, dev):
+    """Host-memory calls of 70, 300 and 70 samples on one handle: the staging
+    buffers are made, freed for larger ones, and then serve a shorter call.
+    300 samples pass a 64-sample block edge."""
+    fs, S, lens = 8000.0, 3, [70, 300, 70]
+    x = random_rows(S, sum(lens), seed=13)
+    calls = [[n] * S for n in lens]
+    ch = Q.Channel(S, sample_rate=fs)
+    got, pos = [], 0
+    for n in lens:
+        out = ch.apply(np.ascontiguousarray(x[:, 2 * pos: 2 * (pos + n)]))
+        got.append([out[s] for s in range(S)])
+        pos += n
+    assert_state_after(ch, fs, S, sum(lens))
+    ch.close()
+    assert_calls_equal(got, oracle_calls(x, calls, fs), "host rows")
+
+
+def test_set_stream_back_to_none_after_a_bound_call(Q, dev):
+    """A device call on a bound torch stream, then set_stream(None) and a second
+    one on the handle's own stream again, then close(): the caller's stream
+    outlives the handle."""
+    torch = dev
+    fs, S, lens = 8000.0, 3, [70, 300]
+    x = random_rows(S, sum(lens), seed=14)
+    ch = Q.Channel(S, sample_rate=fs)
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        ch.set_stream(st.cuda_stream)
+        a = torch.from_numpy(np.ascontiguousarray(x[:, : 2 * lens[0]])).cuda()
+        ch.apply_device(a, lens[0])
+        first = a.cpu().numpy()
+    ch.set_stream(None)
+    b = torch.from_numpy(np.ascontiguousarray(x[:, 2 * lens[0]:])).cuda()
+    ch.apply_device(b, lens[1])
+    second = b.cpu().numpy()
+    assert_state_after(ch, fs, S, sum(lens))
+    ch.close()
+    st.synchronize()
+    got = [[first[s] for s in range(S)], [second[s] for s in range(S)]]
+    assert_calls_equal(got, oracle_calls(x, [[n] * S for n in lens], fs), "bound, then unbound")
+
+
 def test_reset_streams_and_refusals_on_a_live_handle(Q, dev):
     fs, S = 8000.0, 4
     x = random_rows(S, 300, seed=9)

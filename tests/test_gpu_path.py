@@ -327,6 +327,71 @@ def test_positions_near_2_40_through_set_state(Q, dev):
         assert_bits(joined(got, s), want, f"stream {s} across 2^40")
 
 
+def host_form_calls(Q, state, x, lens):
+    """Calls of lens[i] samples on every stream through qpsk_path_apply_host;
+    per call the [S] list of output rows, and the state behind them."""
+    out, pos = [], 0
+    for n in lens:
+        state, o, n_out = Q.path_apply_host(state, np.ascontiguousarray(x[:, 2 * pos: 2 * (pos + n)]))
+        out.append([o[s, : 2 * n_out[s]].copy() for s in range(x.shape[0])])
+        pos += n
+    return out, state
+
+
+def assert_calls_equal_the_host_form(got, want):
+    for ci, (ga, wa) in enumerate(zip(got, want)):
+        for s, (g, w) in enumerate(zip(ga, wa)):
+            assert_bits(g, w, f"call {ci} stream {s}: device vs host form")
+
+
+def test_host_rows_whose_staging_grows_and_is_reused(Q, dev):
+    """Host-memory calls of 40, 1100 and 40 samples on one handle: the staging
+    buffers are made, freed for larger ones, and then serve a shorter call.
+    1100 samples pass one tile edge."""
+    S, lens = 2, [40, 1100, 40]
+    x = random_rows(S, sum(lens), seed=11)
+    pa = make(Q, S, CLOCKS[:S], [PC.project_taps(), taps_of(8)])
+    want, state = host_form_calls(Q, pa.get_state(), x, lens)
+    assert max(w.size // 2 for w in want[1]) > T
+    got, pos = [], 0
+    for n in lens:
+        out, n_out = pa.apply(np.ascontiguousarray(x[:, 2 * pos: 2 * (pos + n)]))
+        got.append([out[s, : 2 * n_out[s]].copy() for s in range(S)])
+        pos += n
+    assert pa.get_state() == state
+    pa.close()
+    assert_calls_equal_the_host_form(got, want)
+
+
+def test_set_stream_back_to_none_after_a_bound_call(Q, dev):
+    """A device call on a bound torch stream, then set_stream(None) and a second
+    one on the handle's own stream again, then close(): the caller's stream
+    outlives the handle."""
+    torch = dev
+    S, lens = 2, [40, 1100]
+    x = random_rows(S, sum(lens), seed=12)
+    pa = make(Q, S, CLOCKS[:S], [PC.project_taps(), taps_of(8)])
+    want, state = host_form_calls(Q, pa.get_state(), x, lens)
+    cuts = [np.ascontiguousarray(x[:, : 2 * lens[0]]), np.ascontiguousarray(x[:, 2 * lens[0]:])]
+    got = []
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        pa.set_stream(st.cuda_stream)
+        o = torch.zeros((S, 2 * pa.out_bound(lens[0])), dtype=torch.float32, device="cuda")
+        n_out = pa.apply_device(torch.from_numpy(cuts[0]).cuda(), lens[0], o)
+        first = o.cpu().numpy()
+    got.append([first[s, : 2 * n_out[s]] for s in range(S)])
+    pa.set_stream(None)
+    o = torch.zeros((S, 2 * pa.out_bound(lens[1])), dtype=torch.float32, device="cuda")
+    n_out = pa.apply_device(torch.from_numpy(cuts[1]).cuda(), lens[1], o)
+    second = o.cpu().numpy()
+    got.append([second[s, : 2 * n_out[s]] for s in range(S)])
+    assert pa.get_state() == state
+    pa.close()
+    st.synchronize()
+    assert_calls_equal_the_host_form(got, want)
+
+
 def test_reset_a_subset_and_move_the_state_to_a_second_handle(Q, dev):
     S, n = 4, 900
     x = random_rows(S, n, seed=9)

@@ -261,6 +261,53 @@ def test_reset_a_subset_and_move_the_state_to_a_second_handle(Q, dev):
         assert_bits(again[0][s], PC.pfb_reference(x[s, :400], M, K_, h, W), f"reset band {s}")
 
 
+def test_host_rows_whose_staging_grows_and_is_reused(Q, dev):
+    """Host-memory calls of 40, 2100 and 40 samples on one handle: the staging
+    buffers are made, freed for larger ones, and then serve a shorter call.
+    At M = 8 a tile is 512 frames of 4 samples: 2100 samples pass one tile edge."""
+    B, M, K_, lens = 2, 8, 2, [40, 2100, 40]
+    assert PC.tile_frames(M) * (M // 2) < lens[1]
+    x = PC.random_rows(B, sum(lens), seed=51)
+    pf = Q.Channeliser(B, channels=M, taps_per_branch=K_)
+    want, state = host_calls(Q, pf.p, x, [[n] * B for n in lens])
+    pos = 0
+    for ci, n in enumerate(lens):
+        out, n_out = pf.apply(np.ascontiguousarray(x[:, 2 * pos: 2 * (pos + n)]))
+        for b in range(B):
+            assert_bits(out[b * M: (b + 1) * M, : 2 * n_out[b]], want[ci][b], f"call {ci} band {b}: device vs host form")
+        pos += n
+    assert pf.get_state() == state
+    pf.close()
+
+
+def test_set_stream_back_to_none_after_a_bound_call(Q, dev):
+    """A device call on a bound torch stream, then set_stream(None) and a second
+    one on the handle's own stream again, then close(): the caller's stream
+    outlives the handle."""
+    torch = dev
+    B, M, K_, lens = 2, 8, 2, [40, 2100]
+    x = PC.random_rows(B, sum(lens), seed=52)
+    pf = Q.Channeliser(B, channels=M, taps_per_branch=K_)
+    want, state = host_calls(Q, pf.p, x, [[n] * B for n in lens])
+    cuts = [np.ascontiguousarray(x[:, : 2 * lens[0]]), np.ascontiguousarray(x[:, 2 * lens[0]:])]
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        pf.set_stream(st.cuda_stream)
+        o = torch.zeros((B * M, 2 * pf.out_bound(lens[0])), dtype=torch.float32, device="cuda")
+        n_first = pf.apply_device(torch.from_numpy(cuts[0]).cuda(), lens[0], o)
+        first = o.cpu().numpy()
+    pf.set_stream(None)
+    o = torch.zeros((B * M, 2 * pf.out_bound(lens[1])), dtype=torch.float32, device="cuda")
+    n_second = pf.apply_device(torch.from_numpy(cuts[1]).cuda(), lens[1], o)
+    second = o.cpu().numpy()
+    assert pf.get_state() == state
+    pf.close()
+    st.synchronize()
+    for ci, (rows, n_out) in enumerate(((first, n_first), (second, n_second))):
+        for b in range(B):
+            assert_bits(rows[b * M: (b + 1) * M, : 2 * n_out[b]], want[ci][b], f"call {ci} band {b}: device vs host form")
+
+
 def test_what_a_live_handle_refuses_changes_nothing(Q, dev):
     torch = dev
     B, M, K_, n = 2, 16, 2, 40
