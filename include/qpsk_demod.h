@@ -1410,7 +1410,8 @@ int qpsk_path_apply_host(void *state, int64_t state_bytes, int32_t n_streams, co
  *
  * Not built: a subset of the channels, an oversampling other than 2, output
  * formats other than CF32, a channeliser behind the host-fed ring, a group
- * form, the synthesis bank. */
+ * form.  (The dual, M rows into one wideband row, is the synthesis bank
+ * below.) */
 typedef struct qpsk_pfb_params {
     int32_t channels;           /* M, a power of two in 8 .. 4096: 64                     */
     int32_t taps_per_branch;    /* K in 1 .. 16, M * K <= 32768: 8                        */
@@ -1504,6 +1505,141 @@ int qpsk_pfb_state_check(const qpsk_pfb_params *p, int32_t n_bands, const void *
 int qpsk_pfb_apply_host(const qpsk_pfb_params *p, const float *taps, void *state, int64_t state_bytes, int32_t n_bands,
                         const float *in, int64_t stride_in, float *out, int64_t stride_out, int64_t out_cap,
                         int64_t n_samples, const int64_t *lengths, int64_t *n_out);
+
+/* ---------------------------------------------------------------------------
+ * The polyphase synthesis bank on the device: M streams into one wideband row.
+ * (Added within ABI version 3: no existing entry point, kernel or layout
+ * changed.)
+ *
+ * The channeliser's dual, what stands behind the modulator when a radio takes
+ * one wideband row and not S baseband rows.  A handle holds n_bands bands.
+ * Band b takes M = channels input rows b * M + c at rate 2 * fs / M, rows of any
+ * QPSK_FMT_* widened as qpsk_demod_process_fmt reads them, and writes one
+ * wideband row b at rate fs, of any QPSK_FMT_*.  Row c lands around c * fs / M;
+ * rows c >= M / 2 are the negative frequencies.  A modulator row at 4 samples a
+ * symbol becomes a carrier of symbol rate fs / (2 M), which is what qpsk_pfb
+ * returns at 4 samples a symbol.  Every operation is float with one rounding;
+ * nothing contracts to an FMA.  Let D = M / 2, K = taps_per_branch, L = M * K.
+ * The limits on M, K, L and n_bands are the channeliser's (QPSK_PFB_*).
+ *
+ * The prototype g[0 .. L-1] and the twiddles W[q] are the channeliser's own
+ * (qpsk_pfb_design, qpsk_pfb_twiddles, defined above); qpsk_sfb_set_taps
+ * replaces the prototype.
+ *
+ * Frame m, the band's absolute frame index from 0, is one sample s_c[m] of each
+ * of the M rows.  The band's output sample i = f * D + r, r in [0, D):
+ *   1. Sign.  z_c[m] = s_c[m], both parts negated when c * m is odd.
+ *   2. Transform, the channeliser's step 2 verbatim.  a[bitrev(c)] = z_c[m];
+ *      stages half = 1, 2, .., M/2, every butterfly with w = W[j * (M / (2*half))]
+ *      and the full multiply everywhere; u_m[q] = a[q].
+ *   3. Polyphase sum.  acc = (+0, +0); for j = 0 .. 2K-1 in order
+ *        acc = acc + g[j*D + r] * u_{f-j}[(r + j*D) mod M]
+ *      (the taps are real: re and im apart, a product rounded, then the sum).
+ *      Frames m < 0 contribute +0; acc starts at +0 and is never -0, so the
+ *      sign of such a zero cannot show.  The sample is acc stored as the
+ *      modulator's fixed-scale quantiser stores it (qpsk_quantise_iq with
+ *      QPSK_MOD_NORM_FIXED): one multiply by scale_out, then, for the integer
+ *      formats, clamp and truncate.  There is no separate gain: scale_out = D
+ *      gives a carrier its input amplitude.
+ * This equals x[i] = sum_c sum_m s_c[m] * g[i - m*D] * e^{+j 2 pi c i / M}: an
+ * upsampling by D, the lowpass g and the mixer on the absolute output index i.
+ *
+ * What a call emits.  A band that has taken n frames has emitted exactly n * D
+ * samples, and a call of len frames emits len * D: no ragged count, no flush.
+ * The delay is L / 2 wideband samples, so bank and channeliser together delay
+ * a row by 2 K of its samples.
+ *
+ * Bank and channeliser are no perfect-reconstruction pair.  On the CPU, with
+ * M = 16, K = 8, one carrier at 4 samples a symbol, alpha = 0.4, the designed
+ * prototype and scale_out = D, the carrier comes back within 0.17 of its peak
+ * on its own channel, 0.013 leaks into each neighbour and <= 5e-4 appears
+ * elsewhere: the prototype's transition band lies over the RRC's edge.
+ *
+ * Not built: a subset of the channels, an oversampling other than 2, a bank
+ * behind the host-fed ring, a group form, a kernel that fuses transform and
+ * sum, a prototype designed for reconstruction. */
+typedef struct qpsk_sfb_params {
+    int32_t channels;           /* M, a power of two in 8 .. 4096: 64                     */
+    int32_t taps_per_branch;    /* K in 1 .. 16, M * K <= 32768: 8                        */
+    int32_t device;             /* HIP device ordinal                                     */
+    int32_t reserved[12];
+} qpsk_sfb_params;
+typedef struct qpsk_sfb qpsk_sfb;
+#define QPSK_SFB_STATE_HEAD 64
+#define QPSK_SFB_TILE_TRANSFORM 0
+#define QPSK_SFB_TILE_SUM 1
+#define QPSK_SFB_TILE_SLAB 2
+/* channels = 64, taps_per_branch = 8, the rest 0. */
+void qpsk_sfb_params_init(qpsk_sfb_params *p);
+/* channels, taps_per_branch or their product outside the channeliser's limits:
+ * QPSK_ERR_OUT_OF_RANGE; n_bands outside 1 .. 65535: QPSK_ERR_ARGUMENT; all
+ * before a device is touched. */
+int qpsk_sfb_create(const qpsk_sfb_params *p, int32_t n_bands, qpsk_sfb **out);
+int qpsk_sfb_destroy(qpsk_sfb *sf);
+/* As qpsk_path_set_stream. */
+int qpsk_sfb_set_stream(qpsk_sfb *sf, void *hip_stream);
+/* As qpsk_pfb_set_taps. */
+int qpsk_sfb_set_taps(qpsk_sfb *sf, const float *taps, int64_t n_taps);
+/* Host only.  The per-call frame counts at which a kernel takes another
+ * workgroup or the call another pass (tests/test_gpu_sfb.py spans them):
+ *   QPSK_SFB_TILE_TRANSFORM  the smallest n >= 1 for which n + 2K - 1 is a
+ *                            multiple of 4096 / M: the transform kernel's
+ *                            tiles of 4096 / M frames count from the 2K - 1
+ *                            frames of history in front of a call;
+ *   QPSK_SFB_TILE_SUM        128, the run of frames a lane of the sum kernel
+ *                            walks;
+ *   QPSK_SFB_TILE_SLAB       max(64, 2^22 / M), the frames a one-band handle
+ *                            transforms and sums in one pass; a handle of
+ *                            n_bands bands takes max(64, 2^22 / M / n_bands).
+ * A bad M or K is QPSK_ERR_OUT_OF_RANGE, a bad `which` QPSK_ERR_ARGUMENT. */
+int qpsk_sfb_tile_frames(int32_t channels, int32_t taps_per_branch, int32_t which);
+/* One call: band b takes lengths[b] frames (lengths == NULL: n_frames for all;
+ * host memory, each 0 .. n_frames), one sample of each of its M rows of in,
+ * [n_bands * M][stride_in] elements of fmt_in (scale_in; CU8 zero at 128),
+ * stride_in >= 2 * n_frames, and writes lengths[b] * D samples to row b of out,
+ * [n_bands][stride_out] elements of fmt_out, stride_out >= 2 * n_frames * D.
+ * norm_out must be QPSK_MOD_NORM_FIXED (QPSK_MOD_NORM_PEAK would need a second
+ * pass: QPSK_ERR_ARGUMENT).  out must not overlap in (the test is on the two
+ * buffers' whole extents), else QPSK_ERR_ARGUMENT.  Device rows, scales, mem,
+ * queueing and the return follow qpsk_path_apply_fmt: a device call without
+ * lengths is queued on the handle's stream and returns; rows 8-byte aligned
+ * (CF32) are read and written a sample an access.  Elements past a row's
+ * lengths[b] * D samples are not written.  The handle owns a scratch buffer of
+ * at most 2^22 + (2K - 1) * M * n_bands transform elements of 8 bytes (more
+ * where n_bands * M * 64 exceeds 2^22); when it cannot be allocated the call is
+ * QPSK_ERR_DEVICE.  A rejected call changes neither the state nor out.  The
+ * caller's current device is the same on return. */
+int qpsk_sfb_apply_fmt(qpsk_sfb *sf, int32_t fmt_in, const void *in, int64_t stride_in, float scale_in,
+                       int32_t fmt_out, int32_t norm_out, void *out, int64_t stride_out, float scale_out,
+                       int64_t n_frames, const int64_t *lengths, int32_t mem);
+/* State: per band QPSK_SFB_STATE_HEAD = 64 bytes
+ *   int64 in_pos (frames), out_pos (== in_pos * D); 48 reserved bytes (0)
+ * followed by float hist[2K-1][M][2], the widened inputs of frames
+ * in_pos-(2K-1) .. in_pos-1 before the sign, frame-major (frames at negative
+ * indices are +0); no header in front of the bands.  The taps are not part of
+ * it.  qpsk_sfb_state_size(p) = 64 + 8 M (2K - 1) (negative, an error code, for
+ * bad parameters) and qpsk_sfb_state_init (the state qpsk_sfb_create leaves:
+ * all zero; buf_bytes = n_bands * state_size) need no device.  get_state /
+ * set_state / reset_bands as the channeliser's. */
+int64_t qpsk_sfb_state_size(const qpsk_sfb_params *p);
+int qpsk_sfb_state_init(const qpsk_sfb_params *p, int32_t n_bands, void *buf, int64_t buf_bytes);
+int qpsk_sfb_get_state(qpsk_sfb *sf, void *host_buf, int64_t buf_bytes);
+int qpsk_sfb_set_state(qpsk_sfb *sf, const void *host_buf, int64_t buf_bytes);
+int qpsk_sfb_reset_bands(qpsk_sfb *sf, const int32_t *bands, int32_t n);
+/* What a state must satisfy (host only): buf_bytes = n_bands * state_size;
+ * in_pos in [0, 2^50 / D]; out_pos == in_pos * D; hist frames at negative
+ * indices +0 (the others may hold any bits: inputs may be NaN); reserved bytes
+ * 0.  A failure is QPSK_ERR_ARGUMENT and names band and field in
+ * qpsk_last_error. */
+int qpsk_sfb_state_check(const qpsk_sfb_params *p, int32_t n_bands, const void *buf, int64_t buf_bytes);
+/* The same call on host CF32 rows and a state blob, single-threaded, no
+ * device: taps is the prototype, M * K floats (NULL: the design); state is
+ * [n_bands] records (checked first, advanced by the call), in and out float
+ * rows with strides in floats, CF32 out at scale_out, the rest as
+ * qpsk_sfb_apply_fmt with CF32 input. */
+int qpsk_sfb_apply_host(const qpsk_sfb_params *p, const float *taps, void *state, int64_t state_bytes, int32_t n_bands,
+                        const float *in, int64_t stride_in, float *out, int64_t stride_out, float scale_out,
+                        int64_t n_frames, const int64_t *lengths);
 
 const char *qpsk_last_error(void);
 int qpsk_abi_version(void);

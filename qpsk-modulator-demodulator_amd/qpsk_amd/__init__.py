@@ -189,6 +189,12 @@ class PfbParams(C.Structure):
                 ("reserved", C.c_int32 * 12)]
 
 
+class SfbParams(C.Structure):
+    """qpsk_sfb_params: the channels and the prototype's length of the polyphase synthesis bank."""
+    _fields_ = [("channels", C.c_int32), ("taps_per_branch", C.c_int32), ("device", C.c_int32),
+                ("reserved", C.c_int32 * 12)]
+
+
 class LoopShape(C.Structure):
     """qpsk_loop_shape (include/qpsk_demod.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -453,6 +459,24 @@ def lib():
     L.qpsk_pfb_state_check.argtypes = [C.POINTER(PfbParams), C.c_int32, C.c_void_p, C.c_int64]
     L.qpsk_pfb_apply_host.argtypes = [C.POINTER(PfbParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                       C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p]
+    L.qpsk_sfb_params_init.argtypes = [C.POINTER(SfbParams)]
+    L.qpsk_sfb_params_init.restype = None
+    L.qpsk_sfb_create.argtypes = [C.POINTER(SfbParams), C.c_int32, C.POINTER(C.c_void_p)]
+    L.qpsk_sfb_destroy.argtypes = [C.c_void_p]
+    L.qpsk_sfb_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.qpsk_sfb_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_sfb_tile_frames.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.qpsk_sfb_apply_fmt.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_int64, C.c_float, C.c_int64, _i64p, C.c_int32]
+    L.qpsk_sfb_state_size.argtypes = [C.POINTER(SfbParams)]
+    L.qpsk_sfb_state_size.restype = C.c_int64
+    L.qpsk_sfb_state_init.argtypes = [C.POINTER(SfbParams), C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_sfb_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_sfb_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_sfb_reset_bands.argtypes = [C.c_void_p, _i32p, C.c_int32]
+    L.qpsk_sfb_state_check.argtypes = [C.POINTER(SfbParams), C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_sfb_apply_host.argtypes = [C.POINTER(SfbParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_int64, _i64p]
     _lib = real
     return real
 
@@ -506,6 +530,9 @@ EXPORTED_SYMBOLS = [
     "qpsk_pfb_twiddles", "qpsk_pfb_set_taps", "qpsk_pfb_count", "qpsk_pfb_out_bound", "qpsk_pfb_tile_frames",
     "qpsk_pfb_apply_fmt", "qpsk_pfb_state_size", "qpsk_pfb_state_init", "qpsk_pfb_get_state", "qpsk_pfb_set_state",
     "qpsk_pfb_reset_bands", "qpsk_pfb_state_check", "qpsk_pfb_apply_host",
+    "qpsk_sfb_params_init", "qpsk_sfb_create", "qpsk_sfb_destroy", "qpsk_sfb_set_stream", "qpsk_sfb_set_taps",
+    "qpsk_sfb_tile_frames", "qpsk_sfb_apply_fmt", "qpsk_sfb_state_size", "qpsk_sfb_state_init", "qpsk_sfb_get_state",
+    "qpsk_sfb_set_state", "qpsk_sfb_reset_bands", "qpsk_sfb_state_check", "qpsk_sfb_apply_host",
 ]
 
 _EXC = {
@@ -1856,7 +1883,7 @@ def _check_device_rows(t, n_rows, need, fmt, what, rows_word="n_streams"):
 
 
 class _RowStage:
-    """What Channel, Path and Channeliser share: the handle's life, its stream,
+    """What Channel, Path, Channeliser and SynthesisBank share: the handle's life, its stream,
     its state and the order of a device-memory call.  A subclass names the
     prefix of its qpsk_* functions, creates its handle with _create, and says
     how many bytes its state takes (_state_bytes)."""
@@ -2305,6 +2332,145 @@ class Channeliser(_RowStage):
     def states(self, blob: bytes | None = None) -> np.ndarray:
         """The state as a pfb_state_dtype array, one record a band."""
         dt = pfb_state_dtype(self.channels, self.p.taps_per_branch)
+        return np.frombuffer(self.get_state() if blob is None else blob, dtype=dt).copy()
+
+    def reset_bands(self, bands):
+        self._reset("bands", bands)
+
+
+SFB_STATE_HEAD = 64           # QPSK_SFB_STATE_HEAD
+SFB_TILE_TRANSFORM, SFB_TILE_SUM, SFB_TILE_SLAB = 0, 1, 2      # QPSK_SFB_TILE_*
+
+
+def sfb_state_dtype(channels: int, taps_per_branch: int) -> np.dtype:
+    """One band's state record: the 64-byte head, then hist[2K - 1][M][2]."""
+    dt = np.dtype([("in_pos", "i8"), ("out_pos", "i8"), ("reserved", "u1", (48,)),
+                   ("hist", "f4", (2 * int(taps_per_branch) - 1, int(channels), 2))])
+    assert dt.itemsize == SFB_STATE_HEAD + 8 * int(channels) * (2 * int(taps_per_branch) - 1)
+    return dt
+
+
+def sfb_params(channels=None, taps_per_branch=None, device=None) -> SfbParams:
+    """qpsk_sfb_params_init's defaults (64 channels, 8 taps a branch) with the given fields replaced."""
+    p = SfbParams()
+    lib().qpsk_sfb_params_init(C.byref(p))
+    for name, v in (("channels", channels), ("taps_per_branch", taps_per_branch), ("device", device)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def sfb_tile_frames(channels: int, taps_per_branch: int, which: int) -> int:
+    """qpsk_sfb_tile_frames: the per-call frame counts at which the kernel
+    SFB_TILE_* names takes another workgroup, or the call another pass (needs no device)."""
+    return int(_check(lib().qpsk_sfb_tile_frames(int(channels), int(taps_per_branch), int(which))))
+
+
+def sfb_state_size(p: SfbParams) -> int:
+    """qpsk_sfb_state_size: the bytes of one band's state, 64 + 8 M (2K - 1) (needs no device)."""
+    return int(_check(lib().qpsk_sfb_state_size(C.byref(p))))
+
+
+def sfb_state_init(p: SfbParams, n_bands: int) -> bytes:
+    """qpsk_sfb_state_init: the state qpsk_sfb_create leaves (needs no device)."""
+    buf = C.create_string_buffer(sfb_state_size(p) * int(n_bands))
+    _check(lib().qpsk_sfb_state_init(C.byref(p), int(n_bands), buf, len(buf)))
+    return buf.raw
+
+
+def sfb_state_check(p: SfbParams, n_bands: int, blob):
+    """qpsk_sfb_state_check: raises ValueError naming band and field when blob
+    is no state of a synthesis bank of n_bands.  Needs no device."""
+    b = bytes(blob)
+    _check(lib().qpsk_sfb_state_check(C.byref(p), int(n_bands), b, len(b)))
+
+
+def sfb_apply_host(p: SfbParams, state, rows: np.ndarray, lengths=None, out: np.ndarray | None = None,
+                   n: int | None = None, taps=None, scale_out=1.0):
+    """qpsk_sfb_apply_host: one call on host float32 rows [n_bands M, 2 n] and a
+    state blob, no device.  Returns (the new state, out rows [n_bands, 2 n D]);
+    a refused call raises and leaves out as it was."""
+    st = C.create_string_buffer(bytes(state), len(bytes(state)))
+    B = len(st) // max(sfb_state_size(p), 1)
+    D = int(p.channels) // 2
+    _check_host_rows(rows, B * int(p.channels), np.float32, "rows must be [n_bands M, 2 n] float32")
+    n = rows.shape[1] // 2 if n is None else int(n)
+    if out is None:
+        out = np.zeros((B, max(2 * n * D, 2)), np.float32)
+    _check_host_rows(out, B, np.float32, "out must be [n_bands, 2 n D] float32")
+    keep, lp = _lengths(lengths, B)
+    t = None if taps is None else np.ascontiguousarray(taps, dtype=np.float32)
+    _check(lib().qpsk_sfb_apply_host(C.byref(p), None if t is None else t.ctypes.data, st, len(st), B, rows.ctypes.data,
+                                     rows.strides[0] // 4, out.ctypes.data, out.strides[0] // 4,
+                                     C.c_float(float(np.float32(scale_out))), n, lp))
+    return st.raw, out
+
+
+class SynthesisBank(_RowStage):
+    """The polyphase synthesis bank on n_bands bands (qpsk_sfb_*), the
+    channeliser's dual: band b's M = channels input rows b M .. b M + M - 1 at
+    rate 2 fs / M become the carriers around c fs / M of its wideband row b at
+    rate fs.  Rows of any format in and out, host or device memory; a call of
+    n frames emits n M / 2 samples a band."""
+
+    _PREFIX = "sfb"
+
+    def __init__(self, n_bands: int, p: SfbParams | None = None, **fields):
+        self.p = p if p is not None else sfb_params(**fields)
+        self.n_bands = int(n_bands)
+        self.channels = int(self.p.channels)
+        self.n_rows = self.n_bands * self.channels
+        self._create(self.n_bands)
+
+    def _state_bytes(self):
+        return sfb_state_size(self.p) * self.n_bands
+
+    def set_taps(self, taps):
+        """Replace the prototype: M K real taps."""
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1))
+        _check(lib().qpsk_sfb_set_taps(self._h, t.ctypes.data if t.size else None, t.size))
+
+    def out_len(self, n_frames: int) -> int:
+        """The samples a band emits for n_frames frames: n_frames M / 2."""
+        return int(n_frames) * (self.channels // 2)
+
+    def apply_host(self, rows: np.ndarray, fmt="cf32", out_fmt="cf32", lengths=None, scale_in=None, scale_out=None,
+                   norm="fixed", out: np.ndarray | None = None, n: int | None = None) -> np.ndarray:
+        """One host-memory call on rows [n_bands M, 2 n] of fmt; returns rows
+        [n_bands, 2 n D] of out_fmt.  out: rows to write into; what lies past
+        a band's samples stays as it was."""
+        tag_in, dt_in, _ = _format(fmt)
+        tag_out, dt_out, _ = _format(out_fmt)
+        _check_host_rows(rows, self.n_rows, dt_in, f"rows must be [n_bands M, 2 n] of {np.dtype(dt_in).name}")
+        n = rows.shape[1] // 2 if n is None else int(n)
+        if out is None:
+            out = np.zeros((self.n_bands, max(2 * self.out_len(n), 2)), dtype=dt_out)
+        _check_host_rows(out, self.n_bands, dt_out, f"out must be [n_bands, 2 n D] of {np.dtype(dt_out).name}")
+        keep, lp = _lengths(lengths, self.n_bands)
+        si, so = _scales(tag_in, tag_out, scale_in, scale_out)
+        _check(lib().qpsk_sfb_apply_fmt(self._h, tag_in, rows.ctypes.data, rows.strides[0] // rows.itemsize, si, tag_out,
+                                        _norm(norm), out.ctypes.data, out.strides[0] // out.itemsize, so, n, lp, MEM_HOST))
+        return out
+
+    def apply_device(self, in_dev, n: int, out_dev, fmt="cf32", out_fmt="cf32", lengths=None, scale_in=None,
+                     scale_out=None, norm="fixed"):
+        """One device-memory call: in_dev [n_bands M, >= 2 n] of fmt, out_dev
+        [n_bands, >= 2 n D] of out_fmt.  lengths is a host array.  Ordered on
+        the handle's stream; without set_stream the caller's torch stream is
+        drained first and the call is waited for."""
+        tag_in, tag_out = _format(fmt)[0], _format(out_fmt)[0]
+        _check_device_rows(in_dev, self.n_rows, 2 * n, fmt, "in_dev", "rows")
+        _check_device_rows(out_dev, self.n_bands, 2 * self.out_len(n), out_fmt, "out_dev", "n_bands")
+        keep, lp = _lengths(lengths, self.n_bands)
+        si, so = _scales(tag_in, tag_out, scale_in, scale_out)
+        self._device_call(out_dev, lambda: lib().qpsk_sfb_apply_fmt(
+            self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, tag_out, _norm(norm), out_dev.data_ptr(),
+            out_dev.stride(0), so, int(n), lp, MEM_DEVICE))
+        return out_dev
+
+    def states(self, blob: bytes | None = None) -> np.ndarray:
+        """The state as an sfb_state_dtype array, one record a band."""
+        dt = sfb_state_dtype(self.channels, self.p.taps_per_branch)
         return np.frombuffer(self.get_state() if blob is None else blob, dtype=dt).copy()
 
     def reset_bands(self, bands):
