@@ -1641,6 +1641,182 @@ int qpsk_sfb_apply_host(const qpsk_sfb_params *p, const float *taps, void *state
                         const float *in, int64_t stride_in, float *out, int64_t stride_out, float scale_out,
                         int64_t n_frames, const int64_t *lengths);
 
+/* ---------------------------------------------------------------------------
+ * The tuner on the device: per-stream frequency shift and any-rate resampler.
+ * (Added within ABI version 3: no existing entry point, kernel or layout
+ * changed.)
+ *
+ * The digital down-converter that stands behind the channeliser, or in front
+ * of the demodulator on its own: a carrier that is off the bank's grid, or a
+ * baseband row from a radio, is moved to DC and brought to the sample rate the
+ * demodulator wants.  Per stream: a numerically controlled oscillator, a
+ * lowpass and a resampler by an arbitrary ratio, rows of any QPSK_FMT_* in and
+ * out.  Used in reverse (resample first, then shift in a second handle) two
+ * tuners make off-grid test carriers.  Every operation is float (double or
+ * integer where stated) with one rounding; nothing contracts to an FMA; no
+ * result depends on how calls cut a stream.  T = taps_per_phase.
+ *
+ * Oscillator.  fw = (int64) rint(freq * 2^64), freq in cycles per input sample
+ * (the scaling is exact).  The phase of the stream's absolute input index i is
+ *   ph(i) = ph0 + fw * i          wrapping uint64 arithmetic: exact, whatever
+ *                                 i's size and however calls cut the stream
+ *   a = ph >> 54 (10 bits),  b = (ph >> 44) & 1023;  the low 44 bits are dropped
+ * Two tables of 1024 complex floats, formed on the host in double with glibc
+ * cos / sin (pi = 3.14159265358979323846) and rounded once:
+ *   C[a] = ((float)cos(t), (float)sin(t)),  t = 2.0 * pi * (double)a / 1024.0
+ *   F[b] likewise with                      t = 2.0 * pi * (double)b / 1048576.0
+ * C[0] = F[0] = (1, +0) are set explicitly.  Then
+ *   w    = (C.re*F.re - C.im*F.im, C.re*F.im + C.im*F.re)
+ *   z[i] = x[i] * conj(w) = (x.re*w.re + x.im*w.im, x.im*w.re - x.re*w.im)
+ * so a positive freq brings a carrier at +freq to DC.  x[i] is the widened
+ * input as qpsk_demod_process_fmt reads it (scale_in; CU8 zero at 128), and +0
+ * for i < 0 (z[i] is still formed by the two lines above).
+ * |w - e^{j 2 pi ph / 2^64}| <= 2 pi 2^-20 + 2^-21: the dropped bits, then the
+ * float roundings.
+ *
+ * Prototype h[0 .. 64 T]: 64 phases of T taps and one end point, real floats.
+ * qpsk_tuner_create designs them on the host in double with glibc sin / cos,
+ * N = 64 T, fc = cutoff (cycles per input sample), g = 2.0 * fc:
+ *   for m = 0 .. N/2:  t = (double)(m - N/2) / 64.0;  x = g * t
+ *                      sinc = x == 0 ? 1 : sin(pi * x) / (pi * x)
+ *                      G[m] = g * sinc * (0.54 - 0.46 * cos(2.0 * pi * (double)m / (double)N))
+ *                             (the products left to right)
+ *   for m = N/2+1 .. N:  G[m] = G[N - m]      (symmetric about N/2 bit for bit)
+ *   sum = G[0] + G[1] + .. + G[N], left to right;  h[m] = (float)(G[m] * 64.0 / sum)
+ *   d[m] = h[m+1] - h[m], m = 0 .. N-1: one float subtraction, precomputed
+ * Every phase's T taps sum to about 1: the DC gain is 1.  The filter is centred
+ * on the output's own position p_k below: the stage adds no delay to a row.
+ * qpsk_tuner_set_taps replaces h; the library derives d again.  cutoff = 0
+ * stands for 0.4 * min(1, 1 / rate) with the params' rate.
+ *
+ * Resampler.  Output k, the stream's absolute output index from 0, sits at the
+ * path's closed form  p_k = tau + (double)k * r  (r input samples per output
+ * sample), all in double:
+ *   n = floor(p_k), mu = p_k - n;  u = mu * 64 (exact);  q = (int)floor(u);
+ *   f = (float)(u - q)
+ *   acc = (+0, +0); for j = 0 .. T-1 in order
+ *     m = 64 * (T - 1 - j) + q
+ *     c = h[m] + f * d[m]                    (the product rounded, then the sum)
+ *     acc = acc + c * z[n - T/2 + 1 + j]     (re and im apart, each product
+ *                                            rounded, then the sum)
+ * The result goes through QPSK_MOD_NORM_FIXED of qpsk_quantise_iq with
+ * scale_out, as the path stores; QPSK_MOD_NORM_PEAK is QPSK_ERR_ARGUMENT.
+ *
+ * What a call emits.  After a call the stream has taken inputs 0 .. in_end-1;
+ * the call emits every not yet emitted k with floor(p_k) <= in_end - 1 - T/2.
+ * There is no flush: append zeros for the tail.  Input positions are held to
+ * 2^50 (output positions then stay below 2^52 + 2).
+ *
+ * Not built: finding carriers, a time-varying r or a change of r on a live
+ * stream (reset the stream, or set a state), r outside [0.25, 4] (use another
+ * channeliser M), per-stream prototypes (use one handle a filter), a group
+ * form, the host-fed ring, peak normalisation. */
+typedef struct qpsk_tuner_params {
+    double freq;                /* cycles per input sample, [-0.5, 0.5): 0                */
+    double rate;                /* r, input samples per output sample, [0.25, 4]: 1       */
+    double tau0;                /* position of output 0, [0, 1): 0                        */
+    double cutoff;              /* fc in (0, 0.5]; 0: 0.4 * min(1, 1 / rate)              */
+    int32_t taps_per_phase;     /* T, even, 4 .. 32: 16                                   */
+    int32_t device;             /* HIP device ordinal                                     */
+    int64_t first_stream;       /* global id of row 0, >= 0 (carried, not interpreted)    */
+    int32_t reserved[6];
+} qpsk_tuner_params;
+typedef struct qpsk_tuner qpsk_tuner;
+#define QPSK_TUNER_PHASES 64
+#define QPSK_TUNER_MIN_TAPS 4
+#define QPSK_TUNER_MAX_TAPS 32
+#define QPSK_TUNER_HIST 32
+#define QPSK_TUNER_MIN_RATE 0.25
+#define QPSK_TUNER_MAX_RATE 4.0
+/* The outputs one workgroup of the tuner kernel covers: the per-call output
+ * counts at which the kernel changes tiles (tests/test_gpu_tuner.py spans them). */
+#define QPSK_TUNER_TILE_OUTPUTS 1024
+/* rate = 1, taps_per_phase = 16, the rest 0. */
+void qpsk_tuner_params_init(qpsk_tuner_params *p);
+/* freq and rate, both host memory, [n_streams], give per-stream values where
+ * not NULL (else the params' freq and rate hold for every stream).  One
+ * prototype, designed from T and cutoff, serves the whole handle.  A freq, rate,
+ * tau0, cutoff or T outside its range (or not finite) or first_stream < 0:
+ * QPSK_ERR_OUT_OF_RANGE; n_streams < 1: QPSK_ERR_ARGUMENT; all before a device
+ * is touched. */
+int qpsk_tuner_create(const qpsk_tuner_params *p, int32_t n_streams, const double *freq, const double *rate,
+                      qpsk_tuner **out);
+int qpsk_tuner_destroy(qpsk_tuner *tu);
+/* As qpsk_path_set_stream. */
+int qpsk_tuner_set_stream(qpsk_tuner *tu, void *hip_stream);
+/* Host only.  The prototype of (T, cutoff) into h[n_points], n_points = 64 T + 1
+ * (else QPSK_ERR_ARGUMENT); cutoff in (0, 0.5] and T as above, else
+ * QPSK_ERR_OUT_OF_RANGE. */
+int qpsk_tuner_design(int32_t taps_per_phase, double cutoff, float *h, int64_t n_points);
+/* Host only.  The oscillator's tables, [1024][2] floats each. */
+int qpsk_tuner_tables(float *coarse, float *fine);
+/* Host only.  w of each of n phases, [n][2] floats. */
+int qpsk_tuner_osc(const uint64_t *ph, int64_t n, float *w);
+/* Replaces the prototype: h is host memory, n_points = 64 T + 1 floats (else
+ * QPSK_ERR_ARGUMENT), all finite (else QPSK_ERR_OUT_OF_RANGE).  Takes effect
+ * behind the calls queued so far; the history is kept. */
+int qpsk_tuner_set_taps(qpsk_tuner *tu, const float *h, int64_t n_points);
+/* Retunes the n listed streams (a list as qpsk_stream_list_check accepts) to
+ * freqs[n], host memory, behind the calls queued so far.  The phase stays
+ * continuous: ph0' = ph0 + (fw_old - fw_new) * in_pos (wrapping), so ph(in_pos)
+ * is what it was.  A freq outside [-0.5, 0.5) is QPSK_ERR_OUT_OF_RANGE and
+ * changes nothing.  (The Costas freq of qpsk_demod_link_stats, in cycles per
+ * output sample, divided by r is what a caller adds to follow a carrier.) */
+int qpsk_tuner_set_freq(qpsk_tuner *tu, const int32_t *streams, int32_t n, const double *freqs);
+/* One call, with the argument list and every rule of qpsk_path_apply_fmt:
+ * host or device memory, per-stream lengths, n_out filled before the call
+ * returns, out_cap (qpsk_tuner_out_bound gives one that always suffices), no
+ * overlap of in and out, 16-byte rows read with 16-byte loads, a rejected call
+ * changes neither the state nor out, a device call without lengths is only
+ * queued. */
+int qpsk_tuner_apply_fmt(qpsk_tuner *tu, int32_t fmt_in, const void *in, int64_t stride_in, float scale_in,
+                         int32_t fmt_out, int32_t norm_out, void *out, int64_t stride_out, int64_t out_cap,
+                         float scale_out, int64_t n_samples, const int64_t *lengths, int64_t *n_out, int32_t mem);
+/* Host only.  A capacity that is enough for any call of n_in samples on a
+ * stream of the smallest of rates[n_streams] (rates == NULL: the params' rate):
+ * ceil(n_in / r_min) + 4; negative (an error code) for bad arguments. */
+int64_t qpsk_tuner_out_bound(const qpsk_tuner_params *p, const double *rates, int32_t n_streams, int64_t n_in);
+/* Host only.  How many outputs a stream at (r, tau) with T taps a phase that
+ * has emitted out_pos emits once it has taken in_end inputs: the k >= out_pos
+ * with floor(p_k) <= in_end - 1 - T/2, from the path's division and a
+ * correction by that predicate.  Negative (an error code) for r, tau or T
+ * outside their ranges, in_end outside [0, 2^50] or out_pos outside [0, 2^52 + 2]. */
+int64_t qpsk_tuner_count(double r, double tau, int32_t taps_per_phase, int64_t out_pos, int64_t in_end);
+/* State: per stream 320 bytes, no header,
+ *   double r, tau; int64 fw; uint64 ph0; int64 in_pos, out_pos; 16 reserved
+ *   bytes (0); float hist[32][2]
+ * hist holds the widened, unmixed inputs at indices in_pos-32 .. in_pos-1 (the
+ * next call can need T - 1 <= 31 of them); entries at negative indices are +0.
+ * The mixer is redone from the absolute index: no oscillator history exists.
+ * The prototype is not part of it.  qpsk_tuner_state_size() = 320 and
+ * qpsk_tuner_state_init (the state qpsk_tuner_create leaves for the same
+ * arguments, buf_bytes = 320 * n_streams) need no device.  get_state /
+ * set_state / reset_streams as the path's; set_state runs
+ * qpsk_tuner_state_check first and changes nothing when it fails;
+ * reset_streams gives the listed rows their created (r, tau), ph0 = 0,
+ * positions 0 and an empty history and keeps their fw as set_freq left it. */
+int qpsk_tuner_state_size(void);
+int qpsk_tuner_state_init(const qpsk_tuner_params *p, int32_t n_streams, const double *freq, const double *rate,
+                          void *buf, int64_t buf_bytes);
+int qpsk_tuner_get_state(qpsk_tuner *tu, void *host_buf, int64_t buf_bytes);
+int qpsk_tuner_set_state(qpsk_tuner *tu, const void *host_buf, int64_t buf_bytes);
+int qpsk_tuner_reset_streams(qpsk_tuner *tu, const int32_t *streams, int32_t n);
+/* What a state must satisfy (host only; p gives T): buf_bytes = 320 *
+ * n_streams; r in [0.25, 4]; tau in [0, 1); in_pos in [0, 2^50]; out_pos ==
+ * qpsk_tuner_count(r, tau, T, 0, in_pos) (the stream has emitted everything it
+ * could); hist entries at negative indices +0 (the others may hold any bits);
+ * reserved bytes 0; fw and ph0 may hold any value.  A failure is
+ * QPSK_ERR_ARGUMENT and names stream and field in qpsk_last_error. */
+int qpsk_tuner_state_check(const qpsk_tuner_params *p, int32_t n_streams, const void *buf, int64_t buf_bytes);
+/* The same call on host CF32 rows and a state blob, single-threaded, no
+ * device: h is the prototype, 64 T + 1 floats (NULL: the design of p); state is
+ * [n_streams] records (checked first, advanced by the call), in and out float
+ * rows with strides in floats, the rest as qpsk_tuner_apply_fmt with both
+ * formats CF32 and both scales 1. */
+int qpsk_tuner_apply_host(const qpsk_tuner_params *p, const float *h, void *state, int64_t state_bytes,
+                          int32_t n_streams, const float *in, int64_t stride_in, float *out, int64_t stride_out,
+                          int64_t out_cap, int64_t n_samples, const int64_t *lengths, int64_t *n_out);
+
 const char *qpsk_last_error(void);
 int qpsk_abi_version(void);
 

@@ -195,6 +195,13 @@ class SfbParams(C.Structure):
                 ("reserved", C.c_int32 * 12)]
 
 
+class TunerParams(C.Structure):
+    """qpsk_tuner_params: the default tuning, the rate, the prototype's length and cutoff of the tuner."""
+    _fields_ = [("freq", C.c_double), ("rate", C.c_double), ("tau0", C.c_double), ("cutoff", C.c_double),
+                ("taps_per_phase", C.c_int32), ("device", C.c_int32), ("first_stream", C.c_int64),
+                ("reserved", C.c_int32 * 6)]
+
+
 class LoopShape(C.Structure):
     """qpsk_loop_shape (include/qpsk_demod.h)"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -477,6 +484,30 @@ def lib():
     L.qpsk_sfb_state_check.argtypes = [C.POINTER(SfbParams), C.c_int32, C.c_void_p, C.c_int64]
     L.qpsk_sfb_apply_host.argtypes = [C.POINTER(SfbParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                       C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_int64, _i64p]
+    # the tuner: per-stream frequency shift and any-rate resampler
+    L.qpsk_tuner_params_init.argtypes = [C.POINTER(TunerParams)]
+    L.qpsk_tuner_params_init.restype = None
+    L.qpsk_tuner_create.argtypes = [C.POINTER(TunerParams), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.qpsk_tuner_destroy.argtypes = [C.c_void_p]
+    L.qpsk_tuner_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.qpsk_tuner_design.argtypes = [C.c_int32, C.c_double, C.c_void_p, C.c_int64]
+    L.qpsk_tuner_tables.argtypes = [C.c_void_p, C.c_void_p]
+    L.qpsk_tuner_osc.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.qpsk_tuner_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_tuner_set_freq.argtypes = [C.c_void_p, _i32p, C.c_int32, C.c_void_p]
+    L.qpsk_tuner_apply_fmt.argtypes = L.qpsk_path_apply_fmt.argtypes
+    L.qpsk_tuner_out_bound.argtypes = [C.POINTER(TunerParams), C.c_void_p, C.c_int32, C.c_int64]
+    L.qpsk_tuner_out_bound.restype = C.c_int64
+    L.qpsk_tuner_count.argtypes = [C.c_double, C.c_double, C.c_int32, C.c_int64, C.c_int64]
+    L.qpsk_tuner_count.restype = C.c_int64
+    L.qpsk_tuner_state_size.restype = C.c_int
+    L.qpsk_tuner_state_init.argtypes = [C.POINTER(TunerParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_tuner_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_tuner_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.qpsk_tuner_reset_streams.argtypes = [C.c_void_p, _i32p, C.c_int32]
+    L.qpsk_tuner_state_check.argtypes = [C.POINTER(TunerParams), C.c_int32, C.c_void_p, C.c_int64]
+    L.qpsk_tuner_apply_host.argtypes = [C.POINTER(TunerParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                        C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p]
     _lib = real
     return real
 
@@ -533,6 +564,11 @@ EXPORTED_SYMBOLS = [
     "qpsk_sfb_params_init", "qpsk_sfb_create", "qpsk_sfb_destroy", "qpsk_sfb_set_stream", "qpsk_sfb_set_taps",
     "qpsk_sfb_tile_frames", "qpsk_sfb_apply_fmt", "qpsk_sfb_state_size", "qpsk_sfb_state_init", "qpsk_sfb_get_state",
     "qpsk_sfb_set_state", "qpsk_sfb_reset_bands", "qpsk_sfb_state_check", "qpsk_sfb_apply_host",
+    "qpsk_tuner_params_init", "qpsk_tuner_create", "qpsk_tuner_destroy", "qpsk_tuner_set_stream", "qpsk_tuner_design",
+    "qpsk_tuner_tables", "qpsk_tuner_osc", "qpsk_tuner_set_taps", "qpsk_tuner_set_freq", "qpsk_tuner_apply_fmt",
+    "qpsk_tuner_out_bound", "qpsk_tuner_count", "qpsk_tuner_state_size", "qpsk_tuner_state_init",
+    "qpsk_tuner_get_state", "qpsk_tuner_set_state", "qpsk_tuner_reset_streams", "qpsk_tuner_state_check",
+    "qpsk_tuner_apply_host",
 ]
 
 _EXC = {
@@ -1883,7 +1919,7 @@ def _check_device_rows(t, n_rows, need, fmt, what, rows_word="n_streams"):
 
 
 class _RowStage:
-    """What Channel, Path, Channeliser and SynthesisBank share: the handle's life, its stream,
+    """What Channel, Path, Channeliser, SynthesisBank and Tuner share: the handle's life, its stream,
     its state and the order of a device-memory call.  A subclass names the
     prefix of its qpsk_* functions, creates its handle with _create, and says
     how many bytes its state takes (_state_bytes)."""
@@ -2475,6 +2511,226 @@ class SynthesisBank(_RowStage):
 
     def reset_bands(self, bands):
         self._reset("bands", bands)
+
+
+# the 320-byte record of a tuner stream's state
+TUNER_STATE_DTYPE = np.dtype([("r", "f8"), ("tau", "f8"), ("fw", "i8"), ("ph0", "u8"), ("in_pos", "i8"),
+                              ("out_pos", "i8"), ("reserved", "u1", (16,)), ("hist", "f4", (32, 2))])
+assert TUNER_STATE_DTYPE.itemsize == 320
+TUNER_TILE_OUTPUTS = 1024     # QPSK_TUNER_TILE_OUTPUTS
+TUNER_PHASES = 64             # QPSK_TUNER_PHASES
+TUNER_HIST = 32               # QPSK_TUNER_HIST
+
+
+def _f64_row(v, n, name):
+    """An optional per-stream double array as the C ABI takes it: (keep-alive, pointer)."""
+    if v is None:
+        return None, None
+    a = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+    if a.size != n:
+        raise ValueError(f"{name} must hold one value a stream")
+    return a, a.ctypes.data
+
+
+def tuner_state_size() -> int:
+    """qpsk_tuner_state_size(): 320 (needs no device)."""
+    return int(lib().qpsk_tuner_state_size())
+
+
+def tuner_params(freq=None, rate=None, tau0=None, cutoff=None, taps_per_phase=None, first_stream=None,
+                 device=None) -> TunerParams:
+    """qpsk_tuner_params_init's defaults (no shift, rate 1, 16 taps a phase) with the given fields replaced."""
+    p = TunerParams()
+    lib().qpsk_tuner_params_init(C.byref(p))
+    for name, v in (("freq", freq), ("rate", rate), ("tau0", tau0), ("cutoff", cutoff)):
+        if v is not None:
+            setattr(p, name, float(v))
+    for name, v in (("taps_per_phase", taps_per_phase), ("first_stream", first_stream), ("device", device)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def tuner_cutoff(p: TunerParams) -> float:
+    """The cutoff a handle of p designs for: cutoff, or 0.4 * min(1, 1 / rate) where it is 0."""
+    return float(p.cutoff) if p.cutoff != 0.0 else 0.4 * (1.0 / p.rate if p.rate > 1.0 else 1.0)
+
+
+def tuner_design(taps_per_phase: int, cutoff: float) -> np.ndarray:
+    """qpsk_tuner_design: the prototype, float32 [64 T + 1] (needs no device)."""
+    n = TUNER_PHASES * int(taps_per_phase) + 1
+    h = np.zeros(max(n, 1), np.float32)
+    _check(lib().qpsk_tuner_design(int(taps_per_phase), float(cutoff), h.ctypes.data, n))
+    return h
+
+
+def tuner_tables():
+    """qpsk_tuner_tables: the oscillator's coarse and fine tables, float32 [1024, 2] each (needs no device)."""
+    c, f = np.zeros((1024, 2), np.float32), np.zeros((1024, 2), np.float32)
+    _check(lib().qpsk_tuner_tables(c.ctypes.data, f.ctypes.data))
+    return c, f
+
+
+def tuner_osc(ph) -> np.ndarray:
+    """qpsk_tuner_osc: w of each uint64 phase, float32 [n, 2] (needs no device)."""
+    a = np.ascontiguousarray(ph, dtype=np.uint64).reshape(-1)
+    w = np.zeros((max(a.size, 1), 2), np.float32)
+    _check(lib().qpsk_tuner_osc(a.ctypes.data, a.size, w.ctypes.data))
+    return w[: a.size]
+
+
+def tuner_count(r: float, tau: float, taps_per_phase: int, out_pos: int, in_end: int) -> int:
+    """qpsk_tuner_count: the outputs k >= out_pos with floor(tau + k r) <= in_end - 1 - T/2 (needs no device)."""
+    return int(_check(lib().qpsk_tuner_count(float(r), float(tau), int(taps_per_phase), int(out_pos), int(in_end))))
+
+
+def tuner_out_bound(p: TunerParams, n_in: int, rates=None) -> int:
+    """qpsk_tuner_out_bound: an output capacity that suffices for any call of n_in samples (needs no device)."""
+    n = 1 if rates is None else np.asarray(rates).size
+    keep, rp = _f64_row(rates, n, "rates")
+    return int(_check(lib().qpsk_tuner_out_bound(C.byref(p), rp, n, int(n_in))))
+
+
+def tuner_state_init(p: TunerParams, n_streams: int, freq=None, rate=None) -> bytes:
+    """qpsk_tuner_state_init: the state qpsk_tuner_create leaves (needs no device)."""
+    buf = C.create_string_buffer(tuner_state_size() * int(n_streams))
+    kf, fp = _f64_row(freq, int(n_streams), "freq")
+    kr, rp = _f64_row(rate, int(n_streams), "rate")
+    _check(lib().qpsk_tuner_state_init(C.byref(p), int(n_streams), fp, rp, buf, len(buf)))
+    return buf.raw
+
+
+def tuner_state_check(p: TunerParams, n_streams: int, blob):
+    """qpsk_tuner_state_check: raises ValueError naming stream and field when
+    blob is no state of a tuner of n_streams.  Needs no device."""
+    b = bytes(blob)
+    _check(lib().qpsk_tuner_state_check(C.byref(p), int(n_streams), b, len(b)))
+
+
+def tuner_apply_host(p: TunerParams, state, rows: np.ndarray, lengths=None, out: np.ndarray | None = None,
+                     out_cap: int | None = None, n: int | None = None, taps=None):
+    """qpsk_tuner_apply_host: one call on host float32 rows [S, 2 n] and a state
+    blob, no device.  Returns (the new state, out rows, n_out); a refused call
+    raises and leaves out as it was."""
+    st = C.create_string_buffer(bytes(state), len(bytes(state)))
+    S = len(st) // tuner_state_size()
+    _check_host_rows(rows, S, np.float32, "rows must be [n_streams, 2 n] float32")
+    n = rows.shape[1] // 2 if n is None else int(n)
+    if out is None:
+        cap = 4 * n + 4 if out_cap is None else int(out_cap)
+        out = np.zeros((S, max(2 * cap, 2)), np.float32)
+    cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
+    keep, lp = _lengths(lengths, S)
+    t = None if taps is None else np.ascontiguousarray(taps, dtype=np.float32)
+    if t is not None and t.size != TUNER_PHASES * int(p.taps_per_phase) + 1:
+        raise ValueError("taps must hold 64 T + 1 floats")
+    n_out = np.zeros(S, np.int64)
+    _check(lib().qpsk_tuner_apply_host(C.byref(p), None if t is None else t.ctypes.data, st, len(st), S,
+                                       rows.ctypes.data, rows.strides[0] // 4, out.ctypes.data, out.strides[0] // 4, cap,
+                                       n, lp, n_out.ctypes.data_as(_i64p)))
+    return st.raw, out, n_out
+
+
+class Tuner(_RowStage):
+    """The tuner on S streams (qpsk_tuner_*): each stream's oscillator brings a
+    carrier at +freq to DC, then a 64-phase polyphase lowpass resamples by r
+    input samples an output.  Rows of any format in, rows of any format out,
+    host or device memory; a call emits what its inputs make computable and
+    returns the counts."""
+
+    _PREFIX = "tuner"
+
+    def __init__(self, n_streams: int, p: TunerParams | None = None, freq=None, rate=None, **fields):
+        """freq, rate: one value for every stream (the params' field) or one a stream."""
+        if freq is not None and np.ndim(freq) == 0:
+            fields["freq"], freq = freq, None
+        if rate is not None and np.ndim(rate) == 0:
+            fields["rate"], rate = rate, None
+        self.p = p if p is not None else tuner_params(**fields)
+        self.n_streams = int(n_streams)
+        kf, fp = _f64_row(freq, self.n_streams, "freq")
+        kr, rp = _f64_row(rate, self.n_streams, "rate")
+        self.rates = kr.copy() if kr is not None else np.full(self.n_streams, float(self.p.rate))
+        h = C.c_void_p()
+        _check(lib().qpsk_tuner_create(C.byref(self.p), self.n_streams, fp, rp, C.byref(h)))
+        self._h = h
+
+    def _state_bytes(self):
+        return tuner_state_size() * self.n_streams
+
+    def set_taps(self, taps):
+        """Replace the prototype: 64 T + 1 real points."""
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1))
+        _check(lib().qpsk_tuner_set_taps(self._h, t.ctypes.data if t.size else None, t.size))
+
+    def set_freq(self, streams, freqs):
+        """Retune the listed streams behind the calls queued so far; the phase stays continuous."""
+        a, n = _stream_list(streams)
+        keep, fp = _f64_row(freqs, n, "freqs")
+        _check(lib().qpsk_tuner_set_freq(self._h, a, n, fp))
+
+    def out_bound(self, n_in: int) -> int:
+        return tuner_out_bound(self.p, n_in, self.rates)
+
+    def lengths_for_demod(self, n_out) -> np.ndarray:
+        """The counts of a call as the lengths of the demodulator call that takes the output rows."""
+        n_out = np.asarray(n_out, np.int64).reshape(-1)
+        if n_out.size != self.n_streams:
+            raise ValueError("n_out must hold one count a stream")
+        return n_out.copy()
+
+    def apply_host(self, rows: np.ndarray, fmt="cf32", out_fmt=None, lengths=None, scale_in=None, scale_out=None,
+                   norm="fixed", out: np.ndarray | None = None, n: int | None = None, out_cap: int | None = None):
+        """One host-memory call on rows [S, 2 n] of fmt; returns (rows of
+        out_fmt (default fmt), n_out).  out: rows to write into, [S, >= 2
+        out_cap]; what lies past a row's n_out stays as it was."""
+        tag_in, dt_in, _ = _format(fmt)
+        tag_out, dt_out, _ = _format(fmt if out_fmt is None else out_fmt)
+        _check_host_rows(rows, self.n_streams, dt_in, f"rows must be [n_streams, 2 n] of {np.dtype(dt_in).name}")
+        n = rows.shape[1] // 2 if n is None else int(n)
+        if out is None:
+            out = np.zeros((self.n_streams, max(2 * (self.out_bound(n) if out_cap is None else int(out_cap)), 2)),
+                           dtype=dt_out)
+        _check_host_rows(out, self.n_streams, dt_out, f"out must be [n_streams, 2 out_cap] of {np.dtype(dt_out).name}")
+        cap = out.shape[1] // 2 if out_cap is None else int(out_cap)
+        keep, lp = _lengths(lengths, self.n_streams)
+        si, so = _scales(tag_in, tag_out, scale_in, scale_out)
+        n_out = np.zeros(self.n_streams, np.int64)
+        _check(lib().qpsk_tuner_apply_fmt(self._h, tag_in, rows.ctypes.data, rows.strides[0] // rows.itemsize, si,
+                                          tag_out, _norm(norm), out.ctypes.data, out.strides[0] // out.itemsize, cap, so,
+                                          n, lp, n_out.ctypes.data_as(_i64p), MEM_HOST))
+        return out, n_out
+
+    def apply_device(self, in_dev, n: int, out_dev, fmt="cf32", out_fmt=None, lengths=None, scale_in=None,
+                     scale_out=None, norm="fixed", out_cap: int | None = None) -> np.ndarray:
+        """One device-memory call: in_dev [S, >= 2 n] of fmt, out_dev [S, >= 2
+        out_cap] of out_fmt (out_cap defaults to what out_dev holds).  Returns
+        n_out, a host array, at once.  lengths is a host array.  Ordered on the
+        handle's stream; without set_stream the caller's torch stream is
+        drained first and the call is waited for."""
+        fo = fmt if out_fmt is None else out_fmt
+        tag_in, tag_out = _format(fmt)[0], _format(fo)[0]
+        cap = out_dev.shape[1] // 2 if out_cap is None else int(out_cap)
+        _check_device_rows(in_dev, self.n_streams, 2 * n, fmt, "in_dev")
+        _check_device_rows(out_dev, self.n_streams, 2 * cap, fo, "out_dev")
+        keep, lp = _lengths(lengths, self.n_streams)
+        si, so = _scales(tag_in, tag_out, scale_in, scale_out)
+        n_out = np.zeros(self.n_streams, np.int64)
+        self._device_call(out_dev, lambda: lib().qpsk_tuner_apply_fmt(
+            self._h, tag_in, in_dev.data_ptr(), in_dev.stride(0), si, tag_out, _norm(norm), out_dev.data_ptr(),
+            out_dev.stride(0), cap, so, int(n), lp, n_out.ctypes.data_as(_i64p), MEM_DEVICE))
+        return n_out
+
+    def state(self) -> bytes:
+        """The state blob behind the calls queued so far."""
+        return self.get_state()
+
+    def states(self, blob: bytes | None = None) -> np.ndarray:
+        """The state as a TUNER_STATE_DTYPE array, one record a stream."""
+        return np.frombuffer(self.get_state() if blob is None else blob, dtype=TUNER_STATE_DTYPE).copy()
+
+    def reset_streams(self, streams):
+        self._reset("streams", streams)
 
 
 def _norm(norm):
